@@ -9,16 +9,21 @@ ekf_slam.cpp:137-192); filter steps/s are reported next to it.  Inputs (twists, 
 before the timed region.  Multi-GPU: one process per GPU, filters sharded by global id, no data-path
 collective; RCCL carries only the final throughput reduction ("scaling": "weak").
 
-The same JSON line carries, as separately reported sub-objects (never mixed into `value` / `roofline`):
-  delayed_update, active_set_update, unknown_association (+ its full-map variant), small_map_monte_carlo,
-  and at N = 1 the other BASELINE.json configurations, each with its own roofline and CPU baseline:
+A plain run does only that: set up, warm up, time the K steps, print the line (the contract leg's own roofline comes
+from the same timed steps).  With --full the same JSON line also carries the Monte-Carlo consistency of the pool, a CPU
+baseline that doubles as a parity spot-check, and, as separately reported sub-objects (never mixed into `value` /
+`roofline`): delayed_update, call_fused_update, active_set_update, unknown_association (+ its full-map variant),
+small_map_monte_carlo, and at N = 1 the other BASELINE.json configurations, each with its own roofline and CPU baseline:
   configs_1 (single filter n = 200 known, through the C ABI), configs_2 (single filter n = 1000 unknown),
   configs_3 (dense F Sigma F^T + Q, N = 10003, fp32 MFMA).
 
-At N > 1 only the contract leg and the delayed leg run (an 8-rank job is ~20 s); the line then also carries the
-per-rank spread of the timed region (rank_ms_per_step_min / _max) next to the MAX-reduced ms_per_step.
+At N > 1 --full runs the contract leg and the delayed leg only (an 8-rank job is ~20 s); the line then also carries
+the per-rank spread of the timed region (rank_ms_per_step_min / _max) next to the MAX-reduced ms_per_step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--filters B]
+--dump-outputs DIR writes what the contract leg computed in its last timed step (dump_outputs()); the inputs depend on
+the arguments only, so two builds can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--filters B] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 (`python bench.py --gpus N` with N > 1 outside torchrun starts that launcher as a child process itself.)
 """
@@ -41,7 +46,7 @@ FULL_MAP_SEED = 36         # configs_2's full-map phase: noise of the two survey
                            # scored pairs 8.9e-7 (relative) from the 10.0 gate; tools/configs2_margins.py: 36 -> 7.2e-5
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)
@@ -65,10 +70,18 @@ def parse():
                     help="generate the synthetic log on the host (numpy) and upload it, instead of on the device")
     ap.add_argument("--rows", type=int, default=0)
     ap.add_argument("--nt", type=int, default=-1)
-    a = ap.parse_args()
-    if a.only_main:
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs, the CPU baseline and the Monte-Carlo / parity checks (off: the contract "
+                         "leg only -- set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the contract leg computed (poses, a seeded sample of states "
+                         "and covariances) as DIR/<name>.npy, float64")
+    a = ap.parse_args(argv)
+    if a.only_main or not a.full:
         a.no_active_set = a.no_unknown = a.no_small = a.no_configs = a.no_call_fused = True
         a.delayed_k = 0
+    if not a.full:
+        a.no_cpu_baseline = True
     return a
 
 
@@ -127,6 +140,33 @@ def pmc_traffic(kernel, B, n):
     if tj.get("filters") != B or tj.get("n") != n:
         return None, "PMC record was taken on another pool shape"
     return tj.get("hbm_bytes_per_launch"), None
+
+
+DUMP_SEED = 20240607       # --dump-outputs: which filters / covariance entries are sampled (fixed, so runs compare)
+DUMP_STATES = 256          # filters whose whole state vector is written
+DUMP_COVS = 16             # ... of which the first few also give DUMP_COV_ENTRIES sampled covariance entries each
+DUMP_COV_ENTRIES = 32768
+DUMP_FULL_COV_BYTES = 40 << 20   # the first sampled filter's whole covariance up to this size (n = 1000: 32 MB)
+
+
+def dump_outputs(bt, first_id, path):
+    """What a caller of the contract leg receives after its last timed step, as float64 .npy files (~41 MB at n = 1000,
+    under 64 MB for any map size): every filter's pose, the state vectors of a seeded sample of filters, seeded entries of
+    the covariances of the first DUMP_COVS sampled filters and the whole covariance of the first one."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    ids = np.sort(rng.choice(bt.B, size=max(1, min(bt.B, DUMP_STATES, (16 << 20) // (8 * bt.N))), replace=False))
+    ii, jj = rng.integers(0, bt.N, size=(2, DUMP_COV_ENTRIES))
+    covs = [bt.cov(int(b)) for b in ids[:DUMP_COVS]]
+    out = {"pose": bt.poses(),
+           "filter_ids": (ids + first_id).astype(np.float64),
+           "state": np.stack([bt.state(int(b)) for b in ids]),
+           "cov_entries": np.stack([c[ii, jj] for c in covs])}
+    if covs[0].nbytes <= DUMP_FULL_COV_BYTES:
+        out["cov"] = covs[0]
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def cpu_baseline(sub, K, t_warm, cores, gpu_state):
@@ -514,9 +554,11 @@ def main():
     wall_min, wall_max = shard.wall_spread(wall, device=red_dev)
     wall, corr, fsteps = shard.reduce_throughput(wall, corr, fsteps, device=red_dev)
     ranks_seen = shard.count_ranks(device=red_dev)
+    if a.dump_outputs and rank == 0:   # (rank 0's share of the pool; filter_ids are global)
+        dump_outputs(bt, first_id, a.dump_outputs)
     # Monte-Carlo consistency of the batch against the simulated ground truth (f4), at the step the pool stands at
     # NOW: the last step it ran is W + K (step 0 = the initialising call)
-    mc_main = bt.mc_stats(W + K) if (rank == 0 and not a.host_log) else None
+    mc_main = bt.mc_stats(W + K) if (rank == 0 and not a.host_log and a.full) else None
     if world > 1:   # an N-rank job runs the contract leg and the delayed leg only
         a.no_active_set = a.no_unknown = a.no_small = a.no_configs = a.no_call_fused = True
     cores = int(os.environ.get("EKF_CPU_THREADS", min(len(os.sched_getaffinity(0)), 16)))
@@ -528,7 +570,7 @@ def main():
     cpu_ids = np.unique(np.linspace(0, B - 1, Bc).round().astype(np.int64))
     Bc = len(cpu_ids)
     eager_state = eager_first = None
-    if rank == 0:
+    if rank == 0 and a.full:
         eager_first = np.stack([bt.state(b) for b in range(min(B, 4))])   # what the other legs compare against
         if want_cpu:
             eager_state = np.stack([bt.state(int(b)) for b in cpu_ids])

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -103,7 +104,7 @@ def test_consistency_and_delayed_parity_on_the_drivers_command_line():
     contract leg's run: the Monte-Carlo consistency figures must still be taken at the step the pool stands at (NEES of
     the same order as for `--steps 16 --warmup 4`, where both legs run the same steps), and the delayed leg must carry its
     own parity figures at its own step count."""
-    side = ["--filters", "64", "--no-active-set", "--no-unknown", "--no-small", "--no-configs", "--no-call-fused",
+    side = ["--full", "--filters", "64", "--no-active-set", "--no-unknown", "--no-small", "--no-configs", "--no-call-fused",
             "--cpu-filters", "4"]
     a = _bench(["--steps", "20", "--warmup", "5"] + side)
     b = _bench(["--steps", "16", "--warmup", "4"] + side)
@@ -125,7 +126,7 @@ def test_four_ranks_with_unequal_shards():
     24 filters by global id; the aggregate counts every filter once and the line shows the per-rank spread."""
     total = 4 * 24 + 3
     env = dict(os.environ, EKF_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    args = ["--steps", "3", "--warmup", "1", "--filters", "25", "--total-filters", str(total), "--landmarks", "300",
+    args = ["--full", "--steps", "3", "--warmup", "1", "--filters", "25", "--total-filters", str(total), "--landmarks", "300",
             "--delayed-k", "0", "--no-cpu-baseline"]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"),
@@ -144,7 +145,8 @@ def test_two_ranks_run_the_delayed_legs():
     """At N > 1 the job runs the contract leg plus the delayed leg and its symmetric variant: every rank takes part in their
     reductions (no rank-0-only collective), and the aggregate counts both ranks' corrections."""
     env = dict(os.environ, EKF_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    args = ["--steps", "4", "--warmup", "1", "--filters", "40", "--landmarks", "300", "--delayed-k", "4", "--no-cpu-baseline"]
+    args = ["--full", "--steps", "4", "--warmup", "1", "--filters", "40", "--landmarks", "300", "--delayed-k", "4",
+            "--no-cpu-baseline"]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"),
                         "--gpus", "2"] + args, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -166,7 +168,7 @@ def test_one_rank_under_the_launcher_runs_the_rccl_path():
     The line must equal the launcher-less run's in everything but time."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("EKF_DIST_BACKEND", None)
-    args = ["--steps", "4", "--warmup", "1", "--filters", "96", "--landmarks", "300", "--no-cpu-baseline", "--no-active-set",
+    args = ["--full", "--steps", "4", "--warmup", "1", "--filters", "96", "--landmarks", "300", "--no-cpu-baseline", "--no-active-set",
             "--no-unknown", "--no-small", "--no-configs", "--no-call-fused", "--delayed-k", "8"]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"),
@@ -184,3 +186,28 @@ def test_one_rank_under_the_launcher_runs_the_rccl_path():
     assert p["config"]["collectives"] is None
     assert p["mc_consistency"] == d["mc_consistency"]            # same filters, same inputs, same end state
     assert p["delayed_update"]["max_abs_state_diff_vs_eager"] == dl["max_abs_state_diff_vs_eager"]
+
+
+def test_plain_run_times_the_contract_leg_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) prints the contract keys with `steps` = --steps and no side leg; --dump-outputs writes the
+    contract leg's end state as float64 .npy files, under 64 MB, identical from run to run with the same arguments."""
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--filters", "96", "--landmarks", "300"]
+    lines = [_bench(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for d in lines:
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / (96 * 2) - 1.0) < 1e-6
+        for key in ("delayed_update", "call_fused_update", "active_set_update", "unknown_association", "small_map_monte_carlo",
+                    "configs_1", "cpu_baseline", "mc_consistency"):
+            assert key not in d, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"pose.npy", "state.npy", "cov.npy"} <= set(names)
+    total = 0
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float64 and np.array_equal(x, y), name
+        total += os.path.getsize(tmp_path / "a" / name)
+    assert total <= 64 << 20
+    ids = np.load(tmp_path / "a" / "filter_ids.npy").astype(np.int64)
+    pose, state, cov = (np.load(tmp_path / "a" / f) for f in ("pose.npy", "state.npy", "cov.npy"))
+    assert pose.shape == (96, 3) and state.shape == (len(ids), 603) and cov.shape == (603, 603)
+    assert np.array_equal(pose[ids], state[:, :3]) and np.isfinite(state).all() and np.allclose(cov, cov.T)

@@ -1,7 +1,8 @@
 """CPU: the drop-in files shim/rigid2d/{include/rigid2d/ekf_slam.hpp, src/ekf_slam.cpp} really
-compile -- against the reference's REAL rigid2d.hpp (rigid2d::Twist2D / Vector2D) when /root/reference is present, and
-against a matrix type with the members of arma::Mat<double> (tests/cpp/arma_double/armadillo, a tests-only double:
-Armadillo is absent from the image).  A compile check of OUR forwarding code; it pins nothing about parity.
+compile -- against the reference's REAL rigid2d.hpp (rigid2d::Twist2D / Vector2D), by build() into oracle/_ref/ where the
+reference sources lie at build time, and against a matrix type with the members of arma::Mat<double>
+(tests/cpp/arma_double/armadillo, a tests-only double: Armadillo is not a dependency of this project).  A compile check of
+OUR forwarding code; it pins nothing about parity.
 Reference surface: rigid2d/include/rigid2d/ekf_slam.hpp:19-57; callers nuslam/src/slam.cpp:213,428,433-434."""
 import os
 import subprocess
@@ -9,24 +10,30 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_INC = "/root/reference/rigid2d/include"
-ARMA_DOUBLE = os.path.join(ROOT, "tests", "cpp", "arma_double")
+REF_OBJ = os.path.join(ROOT, "oracle", "_ref")
 
 
 def _gxx(args, **kw):
     return subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + args, capture_output=True, text=True, **kw)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_INC, "rigid2d", "rigid2d.hpp")),
-                    reason="reference headers not present (GPU box)")
-def test_shim_compiles_against_the_real_rigid2d_headers(tmp_path):
-    obj = tmp_path / "ekf_slam_shim.o"
-    r = _gxx(["-c", "-I" + ROOT, "-I" + os.path.join(ROOT, "shim", "rigid2d", "include"), "-I" + REF_INC,
-              "-I" + os.path.join(REF_INC, "rigid2d"), "-I" + ARMA_DOUBLE,
-              os.path.join(ROOT, "shim", "rigid2d", "src", "ekf_slam.cpp"), "-o", str(obj)])
-    assert r.returncode == 0, r.stderr
+def _ref_object(name):
+    """oracle/_ref/<name>: compiled by build() (oracle/Makefile, target `ref`) against the reference's real rigid2d.hpp
+    with -Wall -Werror, where the reference sources lie at build time."""
+    path = os.path.join(REF_OBJ, name)
+    if not os.path.exists(path):
+        pytest.skip(f"oracle/_ref/{name} not built (reference sources absent at build time)")
+    return path
+
+
+def _nm(path, *flags):
+    return subprocess.run(["nm", "-C"] + list(flags) + [path], capture_output=True, text=True, check=True).stdout
+
+
+def test_shim_compiles_against_the_real_rigid2d_headers():
+    obj = _ref_object("ekf_slam_shim.o")
     # the object defines exactly the reference's public member functions
-    syms = subprocess.run(["nm", "-C", "--defined-only", str(obj)], capture_output=True, text=True, check=True).stdout
+    syms = _nm(obj, "--defined-only")
     for want in ["rigid2d::EKF_SLAM::EKF_SLAM()", "rigid2d::EKF_SLAM::EKF_SLAM(int)",
                  "rigid2d::EKF_SLAM::prediction(rigid2d::Twist2D const&)",
                  "rigid2d::EKF_SLAM::measurement(arma::mat, std::vector<bool",
@@ -36,32 +43,16 @@ def test_shim_compiles_against_the_real_rigid2d_headers(tmp_path):
         assert want in syms, f"shim object lacks {want}"
 
 
-def test_a_caller_like_nuslam_compiles_against_the_shim_header(tmp_path):
-    """slam.cpp's usage pattern: by-value member, copy-assignment from a temporary (:213,428), bare `mat` (:217,380)."""
-    if not os.path.exists(os.path.join(REF_INC, "rigid2d", "rigid2d.hpp")):
-        pytest.skip("reference headers not present (GPU box)")
-    src = tmp_path / "caller.cpp"
-    src.write_text('''
-#include "rigid2d/ekf_slam.hpp"
-struct Node {
-    rigid2d::EKF_SLAM slam_agent;              // slam.cpp:213
-    mat sensor_reading = zeros<mat>(40, 1);    // slam.cpp:217,259 (bare `mat`: the header's using-directive)
-    std::vector<bool> visible_list = std::vector<bool>(20, false), known_list = std::vector<bool>(20, false);
-    std::vector<rigid2d::Vector2D> scan_measures;
-    void tick(const rigid2d::Twist2D& tw) {
-        slam_agent = rigid2d::EKF_SLAM(20);    // slam.cpp:428
-        slam_agent.prediction(tw);             // slam.cpp:433
-        slam_agent.measurement(sensor_reading, visible_list, known_list);   // slam.cpp:434
-        slam_agent.data_association(scan_measures, known_list);            // unknown_data_assoc.cpp:415
-        mat lm = slam_agent.getStateLandmark();                             // slam.cpp:380
-        (void)lm; (void)slam_agent.getStateX(); (void)slam_agent.getStateY(); (void)slam_agent.getStateTheta();
-    }
-};
-int main() { return 0; }
-''')
-    r = _gxx(["-fsyntax-only", "-I" + ROOT, "-I" + os.path.join(ROOT, "shim", "rigid2d", "include"), "-I" + REF_INC,
-              "-I" + os.path.join(REF_INC, "rigid2d"), "-I" + ARMA_DOUBLE, str(src)])
-    assert r.returncode == 0, r.stderr
+def test_a_caller_like_nuslam_compiles_against_the_shim_header():
+    """slam.cpp's usage pattern (tests/cpp/nuslam_caller.cpp): by-value member, copy-assignment from a temporary
+    (:213,428), bare `mat` (:217,380) -- and every shim member it calls is one the shim object defines."""
+    caller = _ref_object("nuslam_caller.o")
+    shim = _ref_object("ekf_slam_shim.o")
+    defined = {l.split(" ", 2)[2] for l in _nm(shim, "--defined-only").splitlines() if l.count(" ") >= 2}
+    called = [l.split("U ", 1)[1] for l in _nm(caller, "--undefined-only").splitlines() if "rigid2d::EKF_SLAM::" in l]
+    assert len(called) >= 8, called
+    for sym in called:
+        assert sym in defined, f"the caller needs {sym}, which the shim does not define"
 
 
 def test_mirror_accepts_a_type_with_both_arma_and_std_spellings(tmp_path):
