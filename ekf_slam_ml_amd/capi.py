@@ -40,7 +40,9 @@ SYMBOLS = [
     "ekf_circle_fit_scans", "ekf_normalize_angles",
     "ekf_default_lidar_params", "ekf_batch_simulate_unknown_log", "ekf_batch_download_unknown_log", "ekf_simulate_scans",
     "ekf_dense_create", "ekf_dense_destroy", "ekf_dense_set", "ekf_dense_propagate", "ekf_dense_get_sigma",
-    "ekf_dense_launch_info", "ekf_dense_tile_map", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
+    "ekf_dense_launch_info", "ekf_dense_tile_map",
+    "ekf_dense64_create", "ekf_dense64_destroy", "ekf_dense64_set", "ekf_dense64_propagate", "ekf_dense64_get_sigma",
+    "ekf_dense64_launch_info", "ekf_dense64_tile_map", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
     "ekf_phase_trace", "ekf_test_raise_device_error",
@@ -185,6 +187,13 @@ def load():
         "ekf_dense_get_sigma": [h, _fp],
         "ekf_dense_launch_info": [h, _ip, _ip, _ip, _ip],
         "ekf_dense_tile_map": [h, _bp],
+        "ekf_dense64_create": [C.c_int, C.c_int, C.POINTER(h)],
+        "ekf_dense64_destroy": [h],
+        "ekf_dense64_set": [h, _dp, _dp, _dp],
+        "ekf_dense64_propagate": [h, C.c_int, _dp],
+        "ekf_dense64_get_sigma": [h, _dp],
+        "ekf_dense64_launch_info": [h, _ip, _ip, _ip, _ip],
+        "ekf_dense64_tile_map": [h, _bp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_set_known_counts": [h, _ip],
@@ -693,6 +702,62 @@ class DensePropagator:
         t = self.launch_info()["tiles"]
         m = np.zeros(t * t, dtype=np.uint8)
         _check(self._lib.ekf_dense_tile_map(self._h, m.ctypes.data_as(_bp)))
+        assert set(np.unique(m)) <= {0, 1}, "a block of the result is computed by no kernel"
+        return m.reshape(t, t).astype(bool)
+
+
+class DensePropagator64:
+    """The fp64 twin of DensePropagator: Sigma <- F Sigma F^T + Q with fp64 operands and fp64 accumulation on the matrix
+    cores, within the library's 1e-9 contract.  Takes and returns np.float64."""
+
+    def __init__(self, N, device=-1):
+        self._lib = load()
+        self.N = int(N)
+        h = C.c_void_p()
+        _check(self._lib.ekf_dense64_create(self.N, device, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ekf_dense64_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _f(self, a):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (self.N, self.N):
+            raise ValueError("matrices must be N x N")
+        return a, a.ctypes.data_as(_dp)
+
+    def set(self, F=None, Sigma=None, Q=None):
+        keep = [self._f(x) for x in (F, Sigma, Q)]
+        _check(self._lib.ekf_dense64_set(self._h, keep[0][1], keep[1][1], keep[2][1]))
+
+    def propagate(self, iterations=1):
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_propagate(self._h, int(iterations), C.byref(ms)))
+        return ms.value
+
+    @property
+    def sigma(self):
+        out = np.empty((self.N, self.N), dtype=np.float64)
+        _check(self._lib.ekf_dense64_get_sigma(self._h, out.ctypes.data_as(_dp)))
+        return out
+
+    def launch_info(self):
+        """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""
+        v = [C.c_int() for _ in range(4)]
+        _check(self._lib.ekf_dense64_launch_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("ld", "tiles", "n_big", "n_tail"), (x.value for x in v)))
+
+    def tile_map(self):
+        """bool [tiles][tiles] over the 128 x 128 blocks of the result: True = computed by the tail kernel"""
+        t = self.launch_info()["tiles"]
+        m = np.zeros(t * t, dtype=np.uint8)
+        _check(self._lib.ekf_dense64_tile_map(self._h, m.ctypes.data_as(_bp)))
         assert set(np.unique(m)) <= {0, 1}, "a block of the result is computed by no kernel"
         return m.reshape(t, t).astype(bool)
 

@@ -1,19 +1,58 @@
-// ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation (configs[3], fp32 MFMA).
+// ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: fp32 MFMA (configs[3],
+// ekf_dense.hip) and its fp64 twin (ekf_dense64.hip).  The host side of the two handles is one template over the element
+// type; the kernels stay separate.
 #include "ekf_runtime.hpp"
 
 using namespace ekfrt;
 
-struct ekf_dense_s {
+template <class E>
+struct DenseHandle {
     int device = -1, N = 0, ld = 0;
     hipStream_t stream = nullptr;
-    float *F = nullptr, *S = nullptr, *T = nullptr, *Q = nullptr;
+    E *F = nullptr, *S = nullptr, *T = nullptr, *Q = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
+struct ekf_dense_s : DenseHandle<float> {};
+struct ekf_dense64_s : DenseHandle<double> {};
 
-extern "C" {
+namespace {
 
-ekf_status ekf_dense_create(int N, int device, ekf_dense_handle* out) {
-    if (!out || N <= 0) return fail(EKF_ERR_INVALID, "ekf_dense_create: bad argument");
+// per element type: the launcher, the split report and the LDS-limit set-up of ekf_dense.hpp
+struct DenseOps32 {
+    static hipError_t prepare() { return ekf::dense_gemm_prepare(); }
+    static void gemm(const float* A, const float* B, float* C, const float* Qadd, int ld, bool bt, hipStream_t s, int n) {
+        ekf::launch_dense_gemm(A, B, C, Qadd, ld, bt, s, n);
+    }
+    static void split(int ld, int* tiles, int* n_big, int* n_tail) { ekf::dense_gemm_split(ld, tiles, n_big, n_tail); }
+    static void tile_map(int ld, unsigned char* map) { ekf::dense_gemm_tile_map(ld, map); }
+};
+struct DenseOps64 {
+    static hipError_t prepare() { return ekf::dense64_gemm_prepare(); }
+    static void gemm(const double* A, const double* B, double* C, const double* Qadd, int ld, bool bt, hipStream_t s,
+                     int n) {
+        ekf::launch_dense64_gemm(A, B, C, Qadd, ld, bt, s, n);
+    }
+    static void split(int ld, int* tiles, int* n_big, int* n_tail) { ekf::dense64_gemm_split(ld, tiles, n_big, n_tail); }
+    static void tile_map(int ld, unsigned char* map) { ekf::dense64_gemm_tile_map(ld, map); }
+};
+
+template <class H>
+ekf_status dense_destroy(H* d) {
+    if (!d) return EKF_OK;
+    if (d->device >= 0) (void)hipSetDevice(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    for (auto* p : {d->F, d->S, d->T, d->Q})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : {d->e0, d->e1})
+        if (e) (void)hipEventDestroy(e);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+    return EKF_OK;
+}
+
+template <class H, class Ops>
+ekf_status dense_create(const char* name, int N, int device, H** out) {
+    if (!out || N <= 0) return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
     *out = nullptr;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
@@ -24,18 +63,18 @@ ekf_status ekf_dense_create(int N, int device, ekf_dense_handle* out) {
     HIPC(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(EKF_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
-    ekf_dense_s* d = new (std::nothrow) ekf_dense_s();
+    H* d = new (std::nothrow) H();
     if (!d) return fail(EKF_ERR_NOMEM, "host allocation failed");
     d->device = device;
     d->N = N;
     d->ld = round_up(N, ekf::kDenseTile);
-    const size_t bytes = sizeof(float) * (size_t)d->ld * d->ld;
+    const size_t bytes = sizeof(*d->F) * (size_t)d->ld * d->ld;
     ekf_status st = EKF_OK;
     auto body = [&]() -> ekf_status {
         HIPC(hipSetDevice(device));
         HIPC(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-        HIPC(ekf::dense_gemm_prepare());
-        for (float** p : {&d->F, &d->S, &d->T, &d->Q}) {
+        HIPC(Ops::prepare());
+        for (auto** p : {&d->F, &d->S, &d->T, &d->Q}) {
             HIPC(hipMalloc((void**)p, bytes));
             HIPC(hipMemsetAsync(*p, 0, bytes, d->stream));
         }
@@ -46,45 +85,34 @@ ekf_status ekf_dense_create(int N, int device, ekf_dense_handle* out) {
     };
     st = body();
     if (st != EKF_OK) {
-        ekf_dense_destroy(d);
+        dense_destroy(d);
         return st;
     }
     *out = d;
     return EKF_OK;
 }
 
-ekf_status ekf_dense_destroy(ekf_dense_handle d) {
-    if (!d) return EKF_OK;
-    if (d->device >= 0) (void)hipSetDevice(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    for (float* p : {d->F, d->S, d->T, d->Q})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : {d->e0, d->e1})
-        if (e) (void)hipEventDestroy(e);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
-    delete d;
-    return EKF_OK;
-}
-
-ekf_status ekf_dense_set(ekf_dense_handle d, const float* F, const float* Sigma, const float* Q) {
+template <class H, class E>
+ekf_status dense_set(H* d, const E* F, const E* Sigma, const E* Q) {
     if (!d) return fail(EKF_ERR_INVALID, "null handle");
     HIPC(hipSetDevice(d->device));
-    const size_t w = sizeof(float) * d->N, pitch = sizeof(float) * d->ld;
-    const float* src[3] = {F, Sigma, Q};
-    float* dst[3] = {d->F, d->S, d->Q};
+    const size_t w = sizeof(E) * d->N, pitch = sizeof(E) * d->ld;
+    const E* src[3] = {F, Sigma, Q};
+    E* dst[3] = {d->F, d->S, d->Q};
     for (int i = 0; i < 3; i++)
         if (src[i]) HIPC(hipMemcpy2DAsync(dst[i], pitch, src[i], w, w, d->N, hipMemcpyHostToDevice, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
     return EKF_OK;
 }
 
-ekf_status ekf_dense_propagate(ekf_dense_handle d, int iterations, double* elapsed_ms) {
-    if (!d || iterations < 0) return fail(EKF_ERR_INVALID, "ekf_dense_propagate: bad argument");
+template <class Ops, class H>
+ekf_status dense_propagate(const char* name, H* d, int iterations, double* elapsed_ms) {
+    if (!d || iterations < 0) return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
     HIPC(hipSetDevice(d->device));
     HIPC(hipEventRecord(d->e0, d->stream));
     for (int it = 0; it < iterations; it++) {
-        ekf::launch_dense_gemm(d->F, d->S, d->T, nullptr, d->ld, false, d->stream, d->N);  // T = At*sigma (:102)
-        ekf::launch_dense_gemm(d->T, d->F, d->S, d->Q, d->ld, true, d->stream, d->N);      // sigma = T*At.t() + Q
+        Ops::gemm(d->F, d->S, d->T, nullptr, d->ld, false, d->stream, d->N);  // T = At*sigma (:102)
+        Ops::gemm(d->T, d->F, d->S, d->Q, d->ld, true, d->stream, d->N);      // sigma = T*At.t() + Q
     }
     HIPC(hipEventRecord(d->e1, d->stream));
     HIPC(hipGetLastError());
@@ -97,26 +125,65 @@ ekf_status ekf_dense_propagate(ekf_dense_handle d, int iterations, double* elaps
     return EKF_OK;
 }
 
-ekf_status ekf_dense_launch_info(ekf_dense_handle d, int* ld, int* tiles, int* n_big, int* n_tail) {
+template <class Ops, class H>
+ekf_status dense_launch_info(H* d, int* ld, int* tiles, int* n_big, int* n_tail) {
     if (!d) return fail(EKF_ERR_INVALID, "null handle");
     if (ld) *ld = d->ld;
-    ekf::dense_gemm_split(d->ld, tiles, n_big, n_tail);
+    Ops::split(d->ld, tiles, n_big, n_tail);
     return EKF_OK;
 }
 
-ekf_status ekf_dense_tile_map(ekf_dense_handle d, unsigned char* map) {
+template <class Ops, class H>
+ekf_status dense_tile_map(H* d, unsigned char* map) {
     if (!d || !map) return fail(EKF_ERR_INVALID, "null argument");
-    ekf::dense_gemm_tile_map(d->ld, map);
+    Ops::tile_map(d->ld, map);
     return EKF_OK;
 }
 
-ekf_status ekf_dense_get_sigma(ekf_dense_handle d, float* out) {
+template <class H, class E>
+ekf_status dense_get_sigma(H* d, E* out) {
     if (!d || !out) return fail(EKF_ERR_INVALID, "null argument");
     HIPC(hipSetDevice(d->device));
-    const size_t w = sizeof(float) * d->N, pitch = sizeof(float) * d->ld;
+    const size_t w = sizeof(E) * d->N, pitch = sizeof(E) * d->ld;
     HIPC(hipMemcpy2DAsync(out, w, d->S, pitch, w, d->N, hipMemcpyDeviceToHost, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
     return EKF_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+ekf_status ekf_dense_create(int N, int device, ekf_dense_handle* out) {
+    return dense_create<ekf_dense_s, DenseOps32>("ekf_dense_create", N, device, out);
+}
+ekf_status ekf_dense_destroy(ekf_dense_handle d) { return dense_destroy(d); }
+ekf_status ekf_dense_set(ekf_dense_handle d, const float* F, const float* Sigma, const float* Q) {
+    return dense_set(d, F, Sigma, Q);
+}
+ekf_status ekf_dense_propagate(ekf_dense_handle d, int iterations, double* elapsed_ms) {
+    return dense_propagate<DenseOps32>("ekf_dense_propagate", d, iterations, elapsed_ms);
+}
+ekf_status ekf_dense_launch_info(ekf_dense_handle d, int* ld, int* tiles, int* n_big, int* n_tail) {
+    return dense_launch_info<DenseOps32>(d, ld, tiles, n_big, n_tail);
+}
+ekf_status ekf_dense_tile_map(ekf_dense_handle d, unsigned char* map) { return dense_tile_map<DenseOps32>(d, map); }
+ekf_status ekf_dense_get_sigma(ekf_dense_handle d, float* out) { return dense_get_sigma(d, out); }
+
+ekf_status ekf_dense64_create(int N, int device, ekf_dense64_handle* out) {
+    return dense_create<ekf_dense64_s, DenseOps64>("ekf_dense64_create", N, device, out);
+}
+ekf_status ekf_dense64_destroy(ekf_dense64_handle d) { return dense_destroy(d); }
+ekf_status ekf_dense64_set(ekf_dense64_handle d, const double* F, const double* Sigma, const double* Q) {
+    return dense_set(d, F, Sigma, Q);
+}
+ekf_status ekf_dense64_propagate(ekf_dense64_handle d, int iterations, double* elapsed_ms) {
+    return dense_propagate<DenseOps64>("ekf_dense64_propagate", d, iterations, elapsed_ms);
+}
+ekf_status ekf_dense64_launch_info(ekf_dense64_handle d, int* ld, int* tiles, int* n_big, int* n_tail) {
+    return dense_launch_info<DenseOps64>(d, ld, tiles, n_big, n_tail);
+}
+ekf_status ekf_dense64_tile_map(ekf_dense64_handle d, unsigned char* map) { return dense_tile_map<DenseOps64>(d, map); }
+ekf_status ekf_dense64_get_sigma(ekf_dense64_handle d, double* out) { return dense_get_sigma(d, out); }
 
 }  // extern "C"

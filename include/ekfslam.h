@@ -424,6 +424,30 @@ ekf_status ekf_dense_launch_info(ekf_dense_handle h, int* ld, int* tiles, int* n
  * 0 = main kernel, 1 = tail kernel (the tests sample rows inside tail tiles with it). */
 ekf_status ekf_dense_tile_map(ekf_dense_handle h, unsigned char* map);
 
+/* ---- dense general-F covariance propagation, fp64 on the matrix cores ----
+ * The same Sigma <- F * Sigma * F^T + Q with every value and every accumulation in fp64 (v_mfma_f64_16x16x4_f64), so a
+ * caller with an fp64 covariance keeps the library's contract: tests/test_gpu_dense64.py holds it to 1e-12 relative per
+ * block against numpy fp64 (1e-9 = FP64_TOL against the checker's prediction()), integer operands bit-exact.
+ * A separate handle type, so fp32 and fp64 buffers cannot be mixed.  Same meaning and status codes as the fp32 functions
+ * (N <= 0 or a NULL out: EKF_ERR_INVALID; no device, or a device that is not gfx950: EKF_ERR_NO_DEVICE; no CPU path).
+ * Device matrices are ld x ld with ld = N rounded up to 128 and zero padding; the handle holds four of them
+ * (F, Sigma, the product F * Sigma, Q): 32 ld^2 bytes, about 3.3 GB at N = 10003 (ld = 10112).
+ * All host matrices are row-major N x N fp64. */
+typedef struct ekf_dense64_s* ekf_dense64_handle;
+ekf_status ekf_dense64_create(int N, int device, ekf_dense64_handle* out);
+ekf_status ekf_dense64_destroy(ekf_dense64_handle h);
+/* Any of F, Sigma, Q may be NULL to keep the current device contents (initially all zero). */
+ekf_status ekf_dense64_set(ekf_dense64_handle h, const double* F, const double* Sigma, const double* Q);
+/* Applies the propagation `iterations` times; elapsed_ms (nullable) = HIP-event time of the launches. */
+ekf_status ekf_dense64_propagate(ekf_dense64_handle h, int iterations, double* elapsed_ms);
+ekf_status ekf_dense64_get_sigma(ekf_dense64_handle h, double* out);
+/* Test / report hook: ld, tiles = ld / 128 per side, n_big = 128 x 128 tiles run by the main kernel (whole rounds of two
+ * resident workgroups per CU), n_tail = 128 x 128 tiles left over, cut into 64 x 64 quarters for the tail kernel behind
+ * it.  Any pointer may be NULL. */
+ekf_status ekf_dense64_launch_info(ekf_dense64_handle h, int* ld, int* tiles, int* n_big, int* n_tail);
+/* ... and which kernel computes which 128 x 128 block: map[tiles * tiles], 0 = main kernel, 1 = tail kernel. */
+ekf_status ekf_dense64_tile_map(ekf_dense64_handle h, unsigned char* map);
+
 /* ---- laser-scan front end: rigid2d::CircleFitting, batched ----------
  * std::vector<Vector2D> approxCirclePositions(std::vector<double> ranges)
  *                                          circle_fitting.hpp:27, circle_fitting.cpp:298-304
