@@ -234,6 +234,104 @@ class RefRigid2D:
         return self._call3("ref_update_pose", wb, wr, left, right)
 
 
+class RefEKF:
+    """oracle/_ref/libekf_slam_ref.so: the reference's own rigid2d::EKF_SLAM (ekf_slam.cpp) compiled against the
+    tests-only Armadillo subset (tests/cpp/arma_double), behind oracle/ref_ekf_shim.cpp.  Duck-types OracleEKF;
+    data_association() returns nothing (the reference reports no per-reading decision), known is updated in place."""
+
+    _lib = None
+
+    @classmethod
+    def _load(cls):
+        if cls._lib is None:
+            p = os.path.join(_HERE, "_ref", "libekf_slam_ref.so")
+            if not os.path.exists(p):
+                raise FileNotFoundError(p)
+            L = C.CDLL(p)
+            L.ekfr_last_error.restype = C.c_char_p
+            L.ekfr_create.restype = C.c_void_p
+            L.ekfr_create.argtypes = [C.c_int]
+            L.ekfr_destroy.argtypes = [C.c_void_p]
+            L.ekfr_prediction.argtypes = [C.c_void_p, C.c_double, C.c_double]
+            L.ekfr_measurement.argtypes = [C.c_void_p, _dp, _bp]
+            L.ekfr_data_association.argtypes = [C.c_void_p, _dp, C.c_int, _bp]
+            L.ekfr_maha.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, _dp]
+            L.ekfr_dim.argtypes = [C.c_void_p]
+            for f in ("ekfr_get_state", "ekfr_set_state", "ekfr_get_cov", "ekfr_set_cov"):
+                getattr(L, f).argtypes = [C.c_void_p, _dp]
+            L.ekfr_get_init_flag.argtypes = [C.c_void_p]
+            L.ekfr_set_init_flag.argtypes = [C.c_void_p, C.c_int]
+            cls._lib = L
+        return cls._lib
+
+    def __init__(self, n):
+        self._lib = self._load()
+        self.n, self.N = n, 3 + 2 * n
+        self._h = self._lib.ekfr_create(int(n))
+        if not self._h:
+            raise RuntimeError("EKF_SLAM(%d): %s" % (n, self._lib.ekfr_last_error().decode()))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.ekfr_destroy(self._h)
+            self._h = None
+
+    def _ok(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"reference {what}: {self._lib.ekfr_last_error().decode()}")
+
+    def prediction(self, dtheta, dx):
+        self._ok(self._lib.ekfr_prediction(self._h, float(dtheta), float(dx)), "prediction")
+
+    def measurement(self, sensor_xy, visible):
+        s = np.ascontiguousarray(sensor_xy, dtype=np.float64)
+        v = np.ascontiguousarray(visible, dtype=np.uint8)
+        assert s.size == 2 * self.n and v.size == self.n
+        self._ok(self._lib.ekfr_measurement(self._h, _d(s), v.ctypes.data_as(_bp)), "measurement")
+
+    def data_association(self, meas_xy, known):
+        m = np.ascontiguousarray(meas_xy, dtype=np.float64).reshape(-1, 2)
+        assert known.dtype == np.uint8 and known.size == self.n and known.flags.c_contiguous
+        self._ok(self._lib.ekfr_data_association(self._h, _d(m), len(m), known.ctypes.data_as(_bp)),
+                 "data_association")
+
+    def maha(self, mx, my, i):
+        out = C.c_double()
+        self._ok(self._lib.ekfr_maha(self._h, float(mx), float(my), int(i), C.byref(out)), "calculate_maha_dis")
+        return out.value
+
+    @property
+    def state(self):
+        out = np.empty(self.N)
+        self._ok(self._lib.ekfr_get_state(self._h, _d(out)), "state")
+        return out
+
+    @state.setter
+    def state(self, v):
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert v.size == self.N
+        self._ok(self._lib.ekfr_set_state(self._h, _d(v)), "state")
+
+    @property
+    def cov(self):
+        out = np.empty((self.N, self.N))
+        self._ok(self._lib.ekfr_get_cov(self._h, _d(out)), "cov")
+        return out
+
+    @cov.setter
+    def cov(self, v):
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        assert v.shape == (self.N, self.N)
+        self._ok(self._lib.ekfr_set_cov(self._h, _d(v)), "cov")
+
+    @property
+    def init_flag(self):
+        return bool(self._lib.ekfr_get_init_flag(self._h))
+
+    def set_init_flag(self, f):
+        self._lib.ekfr_set_init_flag(self._h, int(bool(f)))
+
+
 # ---- rigid2d::CircleFitting (oracle/circle_oracle.c) -------------------------------------------------
 
 def circle_regress(xy):

@@ -10,12 +10,13 @@
  *   - normalize_angle / body twist: PINNED.  Checked against the reference's
  *     own KATs (rigid2d/tests/tests.cpp:322-331) and against oracle/_ref, the
  *     reference's rigid2d.cpp + diff_drive.cpp compiled as they lie.
- *   - EKF_SLAM itself: PARITY UNPINNED.  The reference's ekf_slam.cpp needs
- *     Armadillo (ekf_slam.hpp:10; version unpinned, linked as bare `armadillo`
- *     in rigid2d/CMakeLists.txt:179-181), which is absent from this image, so
- *     the reference is unbuildable here; and no reference test or fixture
- *     touches EKF_SLAM (rigid2d/tests/tests.cpp:2-3 include only rigid2d.hpp
- *     and diff_drive.hpp).  This file restates the algorithm twice:
+ *   - EKF_SLAM itself: PINNED on the reference's own ekf_slam.cpp, compiled
+ *     (oracle/Makefile -> oracle/_ref/libekf_slam_ref.so) against the
+ *     tests-only Armadillo subset tests/cpp/arma_double/armadillo, Armadillo
+ *     being absent from this image; tests/test_reference_ekf.py holds both
+ *     modes to it.  Not pinned: Armadillo's own arithmetic (restated by the
+ *     subset, rounding-level), singular / NaN .i(), non-default ekfo_params.
+ *     This file restates the algorithm twice:
  *       mode 0 "dense literal": every arma expression executed as the dense
  *              matrix product it denotes (N^3 loops, dense 2xN H, dense Q,
  *              dense (I-KH)), in the reference's operand order;
@@ -482,7 +483,7 @@ int ekfo_data_association_m(ekfo *o, const double *meas_xy, int J, unsigned char
                 if (b < margins[4]) margins[4] = b;
             }
         }
-        if (min_maha_idx == known_count && min_maha_idx < o->n) { /* :318-327 */
+        if (known_count == min_maha_idx && min_maha_idx < o->n) { /* :318-327 */
             initialize_landmark(o, mx, my, min_maha_idx);
             known[known_count] = 1;
             known_count++;

@@ -2,8 +2,8 @@
 
 Written literally from rigid2d/src/ekf_slam.cpp with dense ``@`` products and
 ``np.linalg.inv`` -- a second opinion on oracle/ekf_oracle.c (the two must agree to
-<= 1e-12 per block, tests/test_oracle.py).  PARITY UNPINNED for the same reason as the C
-oracle: the reference needs Armadillo and holds no EKF_SLAM fixtures."""
+<= 1e-12 per block, tests/test_oracle.py).  Pinned, like the C
+oracle, on the reference's own ekf_slam.cpp built against the tests-only Armadillo subset (tests/test_reference_ekf.py)."""
 from __future__ import annotations
 
 import math

@@ -2,8 +2,8 @@
 // extern "C" doors into the reference's OWN rigid2d.cpp / diff_drive.cpp, which
 // oracle/Makefile compiles from where they lie under /root/reference (they need
 // libm only).  Used to pin oracle/ekf_oracle.c's normalize_angle and body-twist
-// restatements against the real reference code.  ekf_slam.cpp itself cannot be
-// built here (needs Armadillo), see oracle/ekf_oracle.c header.
+// restatements against the real reference code.  ekf_slam.cpp has its own doors in
+// oracle/ref_ekf_shim.cpp (built against the tests-only Armadillo subset).
 #include "rigid2d/rigid2d.hpp"
 #include "rigid2d/diff_drive.hpp"
 

@@ -18,6 +18,9 @@
 // the drop-in class shim/rigid2d/{include,src} with the reference's own value types and kinematics --
 // rigid2d::Twist2D / Vector2D / DiffDrive compiled from /root/reference where they lie; `mat` is the tests-only
 // double tests/cpp/arma_double/armadillo (Armadillo is absent from the image).
+// With EKF_REPLAY_REFERENCE (oracle/_ref/slam_replay_reference) the reference's include directory comes first, so the
+// class below is the reference's own rigid2d::EKF_SLAM compiled from its ekf_slam.cpp; no libekfslam_hip is linked
+// and the scan pipeline (mode 2, CircleFitting) is not available.
 #include "rigid2d/ekf_slam.hpp"
 #include "rigid2d/diff_drive.hpp"
 using rigid2d::EKF_SLAM;
@@ -74,7 +77,9 @@ struct SLAM {
     SensorVec sensor_reading;            // zeros<mat>(max_n_tubes*2, 1), slam.cpp:259
     std::vector<Vector2D> scan_measures;
     EKF_SLAM slam_agent;                 // by-value member, slam.cpp:213
+#ifndef EKF_REPLAY_REFERENCE
     ekfslam::CircleFitting circle_fitting;
+#endif
 
     SLAM(int n, bool unknown, Odometer& odo)
         : max_n_tubes(n), unknown_assoc(unknown), odometer(odo), visible_list(n, false), known_list(n, false),
@@ -93,10 +98,15 @@ struct SLAM {
     }
     // landmarks node (nuslam/src/landmarks.cpp:60-72,129-149): scan -> CircleFitting -> scan_sensor markers
     void callback_scan(const std::vector<double>& ranges) {
+#ifdef EKF_REPLAY_REFERENCE
+        (void)ranges;
+        throw std::logic_error("the reference replay has no circle fitting (scan logs are mirror / shim only)");
+#else
         std::vector<Vector2D> circles = circle_fitting.approxCirclePositions<Vector2D>(ranges);
         std::vector<Marker> ms;
         for (size_t i = 0; i < circles.size(); i++) ms.push_back(Marker{(int)i, circles[i].x, circles[i].y, 1});
         callback_scan_sensor(ms);
+#endif
     }
     void callback_scan_sensor(const std::vector<Marker>& tubes) {  // unknown_data_assoc.cpp:309-320
         scan_measures.clear();

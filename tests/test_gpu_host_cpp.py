@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from ekf_slam_ml_amd import synth
-from parity import FP64_TOL, assert_parity
+from parity import FP64_TOL, assert_parity, worst
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,7 +17,10 @@ BIN = os.path.join(HERE, "cpp", "slam_replay")
 # the same replay over the DROP-IN class shim/rigid2d/{include,src} with the reference's own Twist2D / Vector2D /
 # DiffDrive (built in the authoring container by oracle/Makefile; it links reference objects, so it lives in oracle/_ref)
 SHIM_BIN = os.path.join(HERE, "..", "oracle", "_ref", "slam_replay_shim")
-VARIANTS = ["mirror", "shim"]
+# the same replay over the reference's OWN class (ekf_slam.cpp against the tests-only Armadillo subset, no HIP): the
+# mirror and shim variants are also compared with it directly.  It has no circle fitting, so the scan test leaves it out.
+REF_BIN = os.path.join(HERE, "..", "oracle", "_ref", "slam_replay_reference")
+VARIANTS = ["mirror", "shim", "reference"]
 
 
 def _hex(v):
@@ -27,15 +30,17 @@ def _hex(v):
 def _run(tmp_path, lines, n, variant="mirror"):
     """-> state, cov (None for the shim: the reference's class has no covariance accessor), known_list, tail"""
     exe = BIN
-    if variant == "shim":
-        exe = SHIM_BIN
+    if variant in ("shim", "reference"):
+        exe = SHIM_BIN if variant == "shim" else REF_BIN
         if not os.path.exists(exe):
-            pytest.skip("oracle/_ref/slam_replay_shim not built (needs /root/reference at build time)")
+            pytest.skip(f"oracle/_ref/{os.path.basename(exe)} not built (needs the reference sources at build time)")
     elif not os.path.exists(BIN):
         subprocess.run(["make", "-C", os.path.join(HERE, "cpp"), "-s"], check=True)
     log, out = tmp_path / "log.txt", tmp_path / "out.txt"
     log.write_text("\n".join(lines) + "\n")
-    subprocess.run([exe, str(log), str(out)], check=True, timeout=300)
+    # the reference's class prints its association trace to stdout (ekf_slam.cpp:290-399)
+    subprocess.run([exe, str(log), str(out)], check=True, timeout=300,
+                   stdout=subprocess.DEVNULL if variant == "reference" else None)
     vals = out.read_text().split()
     N = int(vals[0])
     has_cov = N > 0
@@ -48,6 +53,18 @@ def _run(tmp_path, lines, n, variant="mirror"):
     known = np.array(nums[N + ncov:N + ncov + n], dtype=np.uint8)
     tail = nums[N + ncov + n:]
     return state, cov, known, tail
+
+
+def _against_reference(tmp_path, lines, n, variant, state, known, tail):
+    """pose, landmarks and known_list of the mirror / shim replay against the reference replay of the same log"""
+    if variant == "reference" or not os.path.exists(REF_BIN):
+        return
+    sub = tmp_path / "reference"
+    sub.mkdir()
+    rs_, _, rk, rtail = _run(sub, lines, n, "reference")
+    assert np.array_equal(known, rk), f"{variant}: known_list {known} vs reference {rk}"
+    assert worst(state, np.zeros((1, 1)), rs_, np.zeros((1, 1)))[0] <= FP64_TOL, f"{variant} state vs the reference replay"
+    assert np.abs(np.array(tail[:3]) - np.array(rtail[:3])).max() < 1e-9
 
 
 def _check(state, cov, o, what):
@@ -79,6 +96,7 @@ def test_known_association_node_loop(hip, oracle, tmp_path, variant):
         seen |= log.expand_step(t)[1]
     assert np.array_equal(known, seen)  # known_list bookkeeping of callback_fake_sensor (slam.cpp:320-322)
     assert abs(tail[0] - o.state[0]) < 1e-9 and abs(tail[1] - o.state[1]) < 1e-9 and abs(tail[3] - o.state[-1]) < 1e-9
+    _against_reference(tmp_path, lines, n, variant, state, known, tail)
 
 
 @pytest.mark.parametrize("variant", VARIANTS)
@@ -97,12 +115,13 @@ def test_unknown_association_node_loop(hip, oracle, tmp_path, variant):
             lines.append(f"{j} {_hex(log.meas_xy[t, 0, j, 0])} {_hex(log.meas_xy[t, 0, j, 1])} 1")
         o.prediction(*log.twist[t, 0])
         o.data_association(log.meas_xy[t, 0, :J], known)
-    state, cov, known_cpp, _ = _run(tmp_path, lines, n, variant)
+    state, cov, known_cpp, tail = _run(tmp_path, lines, n, variant)
     assert np.array_equal(known_cpp, known) and known.sum() >= 5
     _check(state, cov, o, f"C++ node loop ({variant}), unknown association")
+    _against_reference(tmp_path, lines, n, variant, state, known_cpp, tail)
 
 
-@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("variant", ["mirror", "shim"])
 def test_scan_pipeline_node_loop(hip, oracle, tmp_path, variant):
     """landmarks node + unknown_data_assoc node in C++: laser ranges -> ekfslam::CircleFitting ->
     EKF_SLAM::data_association, against the checker's circle fitting + filter."""

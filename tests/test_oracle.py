@@ -2,9 +2,9 @@
 
 * normalize_angle / DiffDrive: the reference's own KATs (rigid2d/tests/tests.cpp:322-331, :334-383) and
   the reference's own rigid2d.cpp / diff_drive.cpp compiled as they lie (oracle/_ref) -- PINNED.
-* EKF_SLAM: PARITY UNPINNED (reference unbuildable without Armadillo, no reference fixtures): the
-  dense-literal C restatement, the structured C restatement and the NumPy restatement must agree with
-  each other and with the committed golden vectors."""
+* EKF_SLAM: the dense-literal C restatement, the structured C restatement and the NumPy restatement must
+  agree with each other and with the committed golden vectors; tests/test_reference_ekf.py pins all three
+  on the reference's own ekf_slam.cpp (built against the tests-only Armadillo subset)."""
 import math
 import os
 

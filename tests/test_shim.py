@@ -2,7 +2,8 @@
 compile -- against the reference's REAL rigid2d.hpp (rigid2d::Twist2D / Vector2D), by build() into oracle/_ref/ where the
 reference sources lie at build time, and against a matrix type with the members of arma::Mat<double>
 (tests/cpp/arma_double/armadillo, a tests-only double: Armadillo is not a dependency of this project).  A compile check of
-OUR forwarding code; it pins nothing about parity.
+OUR forwarding code.  Parity is pinned elsewhere: tests/test_reference_ekf.py builds the reference's own ekf_slam.cpp
+against an extended form of the same double.
 Reference surface: rigid2d/include/rigid2d/ekf_slam.hpp:19-57; callers nuslam/src/slam.cpp:213,428,433-434."""
 import os
 import subprocess
