@@ -42,7 +42,8 @@ SYMBOLS = [
     "ekf_dense_create", "ekf_dense_destroy", "ekf_dense_set", "ekf_dense_propagate", "ekf_dense_get_sigma",
     "ekf_dense_launch_info", "ekf_dense_tile_map",
     "ekf_dense64_create", "ekf_dense64_destroy", "ekf_dense64_set", "ekf_dense64_propagate", "ekf_dense64_get_sigma",
-    "ekf_dense64_launch_info", "ekf_dense64_tile_map", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
+    "ekf_dense64_launch_info", "ekf_dense64_tile_map",
+    "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
     "ekf_phase_trace", "ekf_test_raise_device_error",
@@ -194,6 +195,9 @@ def load():
         "ekf_dense64_get_sigma": [h, _dp],
         "ekf_dense64_launch_info": [h, _ip, _ip, _ip, _ip],
         "ekf_dense64_tile_map": [h, _bp],
+        "ekf_dense64_set_state": [h, _dp],
+        "ekf_dense64_get_state": [h, _dp],
+        "ekf_dense64_correct": [h, C.c_int, _dp, _dp, _dp, _dp, _dp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_set_known_counts": [h, _ip],
@@ -708,7 +712,10 @@ class DensePropagator:
 
 class DensePropagator64:
     """The fp64 twin of DensePropagator: Sigma <- F Sigma F^T + Q with fp64 operands and fp64 accumulation on the matrix
-    cores, within the library's 1e-9 contract.  Takes and returns np.float64."""
+    cores, within the library's 1e-9 contract.  Takes and returns np.float64.  The handle also owns a state vector and
+    the other half of a Kalman step, correct(): the measurement update for an arbitrary dense Jacobian."""
+
+    MAX_M = 64   # EKF_DENSE64_MAX_M
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -746,6 +753,43 @@ class DensePropagator64:
         out = np.empty((self.N, self.N), dtype=np.float64)
         _check(self._lib.ekf_dense64_get_sigma(self._h, out.ctypes.data_as(_dp)))
         return out
+
+    @property
+    def state(self):
+        out = np.empty(self.N, dtype=np.float64)
+        _check(self._lib.ekf_dense64_get_state(self._h, out.ctypes.data_as(_dp)))
+        return out
+
+    @state.setter
+    def state(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.N,):
+            raise ValueError("state must have length N")
+        _check(self._lib.ekf_dense64_set_state(self._h, x.ctypes.data_as(_dp)))
+
+    def correct(self, H, R, nu=None):
+        """One measurement update (ekf_slam.cpp:178,186,191-192 for general operands): K = Sigma H^T (H Sigma H^T + R)^-1,
+        state += K nu, Sigma <- (I - K H) Sigma.  H: m x N, R: m x m, nu: m or None (state untouched).
+        Returns (nu^T S^-1 nu or None, elapsed_ms).  A singular or non-finite S raises EkfError (EKF_ERR_STATE) and
+        leaves state and Sigma as they were."""
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        if H.ndim != 2 or H.shape[1] != self.N or not 1 <= H.shape[0] <= min(self.N, self.MAX_M):
+            raise ValueError(f"H must be m x N with 1 <= m <= min(N, {self.MAX_M})")
+        m = H.shape[0]
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.shape != (m, m):
+            raise ValueError("R must be m x m")
+        nis, pnu, pnis = None, None, None
+        if nu is not None:
+            nu = np.ascontiguousarray(nu, dtype=np.float64)
+            if nu.shape != (m,):
+                raise ValueError("nu must have length m")
+            nis = C.c_double()
+            pnu, pnis = nu.ctypes.data_as(_dp), C.byref(nis)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_correct(self._h, m, H.ctypes.data_as(_dp), R.ctypes.data_as(_dp), pnu, pnis,
+                                             C.byref(ms)))
+        return (nis.value if nis is not None else None), ms.value
 
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""

@@ -1,7 +1,10 @@
 // ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: fp32 MFMA (configs[3],
 // ekf_dense.hip) and its fp64 twin (ekf_dense64.hip).  The host side of the two handles is one template over the element
-// type; the kernels stay separate.
+// type; the kernels stay separate.  The fp64 handle also owns a state vector and the dense measurement update for a
+// general Jacobian (ekf_dense64_correct.hip).
 #include "ekf_runtime.hpp"
+
+#include <type_traits>
 
 using namespace ekfrt;
 
@@ -13,7 +16,14 @@ struct DenseHandle {
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 struct ekf_dense_s : DenseHandle<float> {};
-struct ekf_dense64_s : DenseHandle<double> {};
+struct ekf_dense64_s : DenseHandle<double> {
+    // measurement update (ekf_dense64_correct): the state vector, the operands of one correction, its verdict and score
+    double* x = nullptr;        // [ld], zero beyond N
+    double* corr_in = nullptr;  // H [64][ld] | H^T [ld][m rounded up to 16] (room for 64) | R [64 * 64] | nu [64]
+    double* corr_out = nullptr; // nis | verdict (an int in the second double)
+    double* ws_own = nullptr;   // workspace of a handle too small for it to fit the product buffer T
+    std::vector<double> host_in;
+};
 
 namespace {
 
@@ -36,6 +46,9 @@ struct DenseOps64 {
     static void tile_map(int ld, unsigned char* map) { ekf::dense64_gemm_tile_map(ld, map); }
 };
 
+constexpr int kMaxM = ekf::kDense64MaxM;
+inline size_t corr_in_doubles(int ld) { return (size_t)2 * kMaxM * ld + kMaxM * kMaxM + kMaxM; }
+
 template <class H>
 ekf_status dense_destroy(H* d) {
     if (!d) return EKF_OK;
@@ -43,6 +56,9 @@ ekf_status dense_destroy(H* d) {
     if (d->stream) (void)hipStreamSynchronize(d->stream);
     for (auto* p : {d->F, d->S, d->T, d->Q})
         if (p) (void)hipFree(p);
+    if constexpr (std::is_same<H, ekf_dense64_s>::value)
+        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own})
+            if (p) (void)hipFree(p);
     for (hipEvent_t e : {d->e0, d->e1})
         if (e) (void)hipEventDestroy(e);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -77,6 +93,17 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
         for (auto** p : {&d->F, &d->S, &d->T, &d->Q}) {
             HIPC(hipMalloc((void**)p, bytes));
             HIPC(hipMemsetAsync(*p, 0, bytes, d->stream));
+        }
+        if constexpr (std::is_same<H, ekf_dense64_s>::value) {
+            HIPC(ekf::dense64_correct_prepare());
+            const size_t in = sizeof(double) * corr_in_doubles(d->ld);
+            HIPC(hipMalloc((void**)&d->x, sizeof(double) * d->ld));
+            HIPC(hipMemsetAsync(d->x, 0, sizeof(double) * d->ld, d->stream));
+            HIPC(hipMalloc((void**)&d->corr_in, in));
+            HIPC(hipMemsetAsync(d->corr_in, 0, in, d->stream));
+            HIPC(hipMalloc((void**)&d->corr_out, 2 * sizeof(double)));
+            const size_t ws = ekf::dense64_correct_plan(N, d->ld).ws_doubles;
+            if (ws > (size_t)d->ld * d->ld) HIPC(hipMalloc((void**)&d->ws_own, sizeof(double) * ws));
         }
         HIPC(hipEventCreate(&d->e0));
         HIPC(hipEventCreate(&d->e1));
@@ -150,6 +177,54 @@ ekf_status dense_get_sigma(H* d, E* out) {
     return EKF_OK;
 }
 
+// One correction: the operands go up (H twice: as given, zero padded to ld, and transposed with m rounded up to 16), the six
+// launches are timed by the handle's events, the verdict and nis come back in one copy.
+ekf_status dense64_correct(ekf_dense64_s* d, int m, const double* H, const double* R, const double* nu, double* nis_out,
+                           double* elapsed_ms) {
+    if (!d || !H || !R || m < 1 || m > kMaxM || m > d->N || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_correct: bad argument");
+    HIPC(hipSetDevice(d->device));
+    const int N = d->N, ld = d->ld;
+    const size_t oHt = (size_t)kMaxM * ld, oR = 2 * oHt, oNu = oR + kMaxM * kMaxM;
+    const int mp = round_up(m, 16);   // row length of the transposed copy
+    d->host_in.assign(corr_in_doubles(ld), 0.0);
+    double* in = d->host_in.data();
+    for (int k = 0; k < m; k++)
+        for (int j = 0; j < N; j++) {
+            const double v = H[(size_t)k * N + j];
+            in[(size_t)k * ld + j] = v;
+            in[oHt + (size_t)j * mp + k] = v;
+        }
+    std::memcpy(in + oR, R, sizeof(double) * m * m);
+    if (nu) std::memcpy(in + oNu, nu, sizeof(double) * m);
+    const size_t piece[3][2] = {{0, (size_t)m * ld}, {oHt, (size_t)ld * mp}, {oR, (size_t)kMaxM * kMaxM + kMaxM}};
+    for (const auto& pc : piece)
+        HIPC(hipMemcpyAsync(d->corr_in + pc[0], in + pc[0], sizeof(double) * pc[1], hipMemcpyHostToDevice, d->stream));
+    const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
+    double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_correct(pl, d->S, d->x, ws, d->corr_in, d->corr_in + oHt, d->corr_in + oR,
+                                nu ? d->corr_in + oNu : nullptr, m, d->corr_out, reinterpret_cast<int*>(d->corr_out + 1),
+                                d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    double out[2] = {0.0, 0.0};
+    HIPC(hipMemcpyAsync(out, d->corr_out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    int verdict = 0;
+    std::memcpy(&verdict, &out[1], sizeof(int));
+    if (verdict != 0)
+        return fail(EKF_ERR_STATE, "ekf_dense64_correct: H Sigma H^T + R is singular or not finite (zero or non-finite "
+                                   "pivot); state and Sigma are unchanged");
+    if (nis_out) *nis_out = out[0];
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -185,5 +260,23 @@ ekf_status ekf_dense64_launch_info(ekf_dense64_handle d, int* ld, int* tiles, in
 }
 ekf_status ekf_dense64_tile_map(ekf_dense64_handle d, unsigned char* map) { return dense_tile_map<DenseOps64>(d, map); }
 ekf_status ekf_dense64_get_sigma(ekf_dense64_handle d, double* out) { return dense_get_sigma(d, out); }
+ekf_status ekf_dense64_set_state(ekf_dense64_handle d, const double* x) {
+    if (!d || !x) return fail(EKF_ERR_INVALID, "ekf_dense64_set_state: null argument");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipMemcpyAsync(d->x, x, sizeof(double) * d->N, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+ekf_status ekf_dense64_get_state(ekf_dense64_handle d, double* out) {
+    if (!d || !out) return fail(EKF_ERR_INVALID, "ekf_dense64_get_state: null argument");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipMemcpyAsync(out, d->x, sizeof(double) * d->N, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+ekf_status ekf_dense64_correct(ekf_dense64_handle d, int m, const double* H, const double* R, const double* nu,
+                               double* nis_out, double* elapsed_ms) {
+    return dense64_correct(d, m, H, R, nu, nis_out, elapsed_ms);
+}
 
 }  // extern "C"

@@ -26,4 +26,25 @@ void launch_dense64_gemm(const double* A, const double* B, double* C, const doub
 void dense64_gemm_split(int ld, int* tiles, int* n_big, int* n_rem);
 void dense64_gemm_tile_map(int ld, unsigned char* map);   // as dense_gemm_tile_map
 hipError_t dense64_gemm_prepare();  // raises the dynamic-LDS limit of the main kernel (64.8 KiB per workgroup)
+
+// ---- fp64 dense measurement update for a general m x N Jacobian (ekf_dense64_correct.hip), on the same ld x ld Sigma:
+//   T = H Sigma, U = Sigma H^T, S = T H^T + R, K = U S^-1, state += K nu, Sigma <- Sigma - K T, nis = nu^T S^-1 nu.
+constexpr int kDense64MaxM = 64;   // EKF_DENSE64_MAX_M
+// How one correction of an N x N covariance is cut, and where its panels sit in the workspace (offsets in doubles).
+struct Dense64CorrectPlan {
+    int N, ld;
+    int n_strips, n_chunks, tiles_per_chunk;   // panel pass: strips of 256 columns x chunks of 64-row tiles
+    int n_sparts;                              // 128-column chunks of S = T H^T
+    int upd_strips, upd_chunks, upd_blocks_per_chunk;   // update: strips of 128 columns x chunks of 16-row blocks
+    size_t off_T, off_Ut, off_Kt, off_Tpart, off_Upart, off_Spart, off_Sinv, ws_doubles;
+};
+Dense64CorrectPlan dense64_correct_plan(int N, int ld);
+hipError_t dense64_correct_prepare();   // raises the dynamic-LDS limits (panel pass: up to 99 KiB per workgroup at m > 48)
+// The six launches of one correction on stream s.  Sigma: ld x ld with zero padding (kept); state: ld doubles;
+// ws: pl.ws_doubles doubles; Hd: H as [m][ld] and Ht: H^T as [ld][m rounded up to 16], both zero padded; R: m x m; nu: m or NULL (state
+// and *nis untouched); verdict: device word, 0 = applied, 1 = S singular or non-finite (then nothing was written to
+// state or Sigma).
+void launch_dense64_correct(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws, const double* Hd,
+                            const double* Ht, const double* R, const double* nu, int m, double* nis, int* verdict,
+                            hipStream_t s);
 }  // namespace ekf

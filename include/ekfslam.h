@@ -431,7 +431,10 @@ ekf_status ekf_dense_tile_map(ekf_dense_handle h, unsigned char* map);
  * A separate handle type, so fp32 and fp64 buffers cannot be mixed.  Same meaning and status codes as the fp32 functions
  * (N <= 0 or a NULL out: EKF_ERR_INVALID; no device, or a device that is not gfx950: EKF_ERR_NO_DEVICE; no CPU path).
  * Device matrices are ld x ld with ld = N rounded up to 128 and zero padding; the handle holds four of them
- * (F, Sigma, the product F * Sigma, Q): 32 ld^2 bytes, about 3.3 GB at N = 10003 (ld = 10112).
+ * (F, Sigma, the product F * Sigma, Q): 32 ld^2 bytes, about 3.3 GB at N = 10003 (ld = 10112) -- plus, for the measurement
+ * update below, the state vector and one correction's operands: 8 ld (1 + 2 * 64) + 33 KB, i.e. 10.5 MB at N = 10003.
+ * The update's panels and partial sums live in the product buffer, which is dead between propagations; only a small
+ * handle (ld below about 3000), where they do not fit, allocates them separately (46 MB at N = 2003, less below).
  * All host matrices are row-major N x N fp64. */
 typedef struct ekf_dense64_s* ekf_dense64_handle;
 ekf_status ekf_dense64_create(int N, int device, ekf_dense64_handle* out);
@@ -447,6 +450,26 @@ ekf_status ekf_dense64_get_sigma(ekf_dense64_handle h, double* out);
 ekf_status ekf_dense64_launch_info(ekf_dense64_handle h, int* ld, int* tiles, int* n_big, int* n_tail);
 /* ... and which kernel computes which 128 x 128 block: map[tiles * tiles], 0 = main kernel, 1 = tail kernel. */
 ekf_status ekf_dense64_tile_map(ekf_dense64_handle h, unsigned char* map);
+#define EKF_DENSE64_MAX_M 64
+/* state vector of the handle (N doubles, initially zero) */
+ekf_status ekf_dense64_set_state(ekf_dense64_handle h, const double* x /* N */);
+ekf_status ekf_dense64_get_state(ekf_dense64_handle h, double* out /* N */);
+/* One measurement update with an arbitrary dense Jacobian -- ekf_slam.cpp:178,186,191-192 for general operands:
+ *   T = H Sigma (m x N, rows of Sigma)      U = Sigma H^T (N x m, COLUMNS of Sigma: Sigma is never symmetrised)
+ *   S = T H^T + R      K = U S^-1      state += K nu      Sigma <- Sigma - K T   ( = (I - K H) Sigma to rounding )
+ *   *nis_out = nu^T S^-1 nu   (the score of calculate_maha_dis, :267-269)
+ * H: m x N row-major, R: m x m row-major (need not be diagonal or symmetric), nu: m (NULL: state untouched, nis_out
+ * must then be NULL), 1 <= m <= min(N, EKF_DENSE64_MAX_M).  Synchronous.  elapsed_ms (nullable) = HIP-event time of
+ * the launches only (no H2D of H / R / nu).
+ * S is inverted by elimination with partial pivoting in fp64.  A zero or non-finite pivot (or a non-finite entry of S
+ * or of S^-1) returns EKF_ERR_STATE and leaves state and Sigma exactly as they were: the verdict is a device word the
+ * writing launches read before their first store.  The padding of Sigma stays zero, so ekf_dense64_propagate and
+ * ekf_dense64_correct alternate without Sigma leaving the device.  Bad arguments (NULL handle, NULL H or R, m < 1,
+ * m > EKF_DENSE64_MAX_M, m > N, nis_out without nu) return EKF_ERR_INVALID before the device is looked at.
+ * No floating-point atomics: the same inputs give the same bits every time.  The wrapping of an angle in nu or in the
+ * state (:183,187) is the caller's business: the entry point is model-free. */
+ekf_status ekf_dense64_correct(ekf_dense64_handle h, int m, const double* H, const double* R, const double* nu,
+                               double* nis_out, double* elapsed_ms);
 
 /* ---- laser-scan front end: rigid2d::CircleFitting, batched ----------
  * std::vector<Vector2D> approxCirclePositions(std::vector<double> ranges)
