@@ -43,7 +43,7 @@ SYMBOLS = [
     "ekf_dense_launch_info", "ekf_dense_tile_map",
     "ekf_dense64_create", "ekf_dense64_destroy", "ekf_dense64_set", "ekf_dense64_propagate", "ekf_dense64_get_sigma",
     "ekf_dense64_launch_info", "ekf_dense64_tile_map",
-    "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
+    "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
     "ekf_phase_trace", "ekf_test_raise_device_error",
@@ -198,6 +198,7 @@ def load():
         "ekf_dense64_set_state": [h, _dp],
         "ekf_dense64_get_state": [h, _dp],
         "ekf_dense64_correct": [h, C.c_int, _dp, _dp, _dp, _dp, _dp],
+        "ekf_dense64_score": [h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_set_known_counts": [h, _ip],
@@ -716,6 +717,7 @@ class DensePropagator64:
     the other half of a Kalman step, correct(): the measurement update for an arbitrary dense Jacobian."""
 
     MAX_M = 64   # EKF_DENSE64_MAX_M
+    SCORE_MAX_ROWS = 2048   # EKF_DENSE64_SCORE_MAX_ROWS
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -790,6 +792,38 @@ class DensePropagator64:
         _check(self._lib.ekf_dense64_correct(self._h, m, H.ctypes.data_as(_dp), R.ctypes.data_as(_dp), pnu, pnis,
                                              C.byref(ms)))
         return (nis.value if nis is not None else None), ms.value
+
+    def score(self, H, R, nu=None, want_S=False):
+        """Score J candidate measurements without touching Sigma or the state (calculate_maha_dis, ekf_slam.cpp:217-276,
+        for general operands): S_j = H_j Sigma H_j^T + R_j, nis_j = nu_j^T S_j^-1 nu_j.  H: (J, m, N); R: (m, m) shared by
+        all candidates or (J, m, m); nu: (J, m) or None (no scores).  Returns (nis (J,) or None, S (J, m, m) or None,
+        flags (J,) int32, elapsed_ms); a candidate whose S is singular or not finite has flag 1 and nis NaN."""
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        if H.ndim != 3 or H.shape[2] != self.N or H.shape[0] < 1 or not 1 <= H.shape[1] <= min(self.N, self.MAX_M):
+            raise ValueError(f"H must be J x m x N with J >= 1 and 1 <= m <= min(N, {self.MAX_M})")
+        J, m = H.shape[0], H.shape[1]
+        if J * m > self.SCORE_MAX_ROWS:
+            raise ValueError(f"J * m must not exceed {self.SCORE_MAX_ROWS}")
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.shape != (m, m) and R.shape != (J, m, m):
+            raise ValueError("R must be m x m or J x m x m")
+        nis, S, pnu = None, None, None
+        if nu is not None:
+            nu = np.ascontiguousarray(nu, dtype=np.float64)
+            if nu.shape != (J, m):
+                raise ValueError("nu must be J x m")
+            nis = np.empty(J, dtype=np.float64)
+            pnu = nu.ctypes.data_as(_dp)
+        if want_S:
+            S = np.empty((J, m, m), dtype=np.float64)
+        flags = np.empty(J, dtype=np.int32)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_score(self._h, J, m, H.ctypes.data_as(_dp), R.ctypes.data_as(_dp),
+                                           1 if R.ndim == 2 else 0, pnu,
+                                           nis.ctypes.data_as(_dp) if nis is not None else None,
+                                           S.ctypes.data_as(_dp) if S is not None else None,
+                                           flags.ctypes.data_as(_ip), C.byref(ms)))
+        return nis, S, flags, ms.value
 
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""

@@ -1,7 +1,7 @@
 // ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: fp32 MFMA (configs[3],
 // ekf_dense.hip) and its fp64 twin (ekf_dense64.hip).  The host side of the two handles is one template over the element
-// type; the kernels stay separate.  The fp64 handle also owns a state vector and the dense measurement update for a
-// general Jacobian (ekf_dense64_correct.hip).
+// type; the kernels stay separate.  The fp64 handle also owns a state vector, the dense measurement update for a
+// general Jacobian (ekf_dense64_correct.hip) and the read-only scoring of candidate measurements (ekf_dense64_score.hip).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -23,6 +23,11 @@ struct ekf_dense64_s : DenseHandle<double> {
     double* corr_out = nullptr; // nis | verdict (an int in the second double)
     double* ws_own = nullptr;   // workspace of a handle too small for it to fit the product buffer T
     std::vector<double> host_in;
+    // candidate scoring (ekf_dense64_score): nothing until the first call; the two large buffers grow with the calls
+    double* sc_small = nullptr;  // R [2048 * 64] | nu [2048] | nis [2048] | S [2048 * 64] | flags (ints) [2048]
+    double* sc_H = nullptr;      // the stacked Jacobians, [groups * 64][ld], columns N .. ld zero
+    double* sc_ws = nullptr;     // the partial S blocks of a call that do not fit the product buffer T
+    size_t sc_H_doubles = 0, sc_ws_doubles = 0;
 };
 
 namespace {
@@ -57,7 +62,7 @@ ekf_status dense_destroy(H* d) {
     for (auto* p : {d->F, d->S, d->T, d->Q})
         if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
-        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own})
+        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws})
             if (p) (void)hipFree(p);
     for (hipEvent_t e : {d->e0, d->e1})
         if (e) (void)hipEventDestroy(e);
@@ -225,6 +230,92 @@ ekf_status dense64_correct(ekf_dense64_s* d, int m, const double* H, const doubl
     return EKF_OK;
 }
 
+// Scoring of J candidates.  The Jacobians go straight from the caller's array into their row groups on the device (one
+// strided copy when m divides 64, one per group otherwise); the outputs come straight back into the caller's arrays.
+constexpr int kScoreRows = ekf::kDense64ScoreMaxRows;
+constexpr size_t kScR = 0, kScNu = (size_t)kScoreRows * kMaxM, kScNis = kScNu + kScoreRows, kScS = kScNis + kScoreRows,
+                 kScFlag = kScS + (size_t)kScoreRows * kMaxM, kScSmall = kScFlag + kScoreRows / 2;
+
+// Buffers of the first / a larger call: allocated into locals, the members change only when everything succeeded.
+ekf_status score_reserve(ekf_dense64_s* d, const ekf::Dense64ScorePlan& sp) {
+    const bool own_ws = sp.spart_doubles > (size_t)d->ld * d->ld;   // else the product buffer, dead between propagations
+    double *small = nullptr, *Hs = nullptr, *ws = nullptr;
+    hipError_t e = hipSuccess;
+    if (!d->sc_small) {
+        e = ekf::dense64_score_prepare();
+        if (e == hipSuccess) e = hipMalloc((void**)&small, sizeof(double) * kScSmall);
+    }
+    if (e == hipSuccess && sp.h_doubles > d->sc_H_doubles) {
+        e = hipMalloc((void**)&Hs, sizeof(double) * sp.h_doubles);
+        if (e == hipSuccess) e = hipMemsetAsync(Hs, 0, sizeof(double) * sp.h_doubles, d->stream);
+    }
+    if (e == hipSuccess && own_ws && sp.spart_doubles > d->sc_ws_doubles)
+        e = hipMalloc((void**)&ws, sizeof(double) * sp.spart_doubles);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(d->stream);
+        for (double* p : {small, Hs, ws})
+            if (p) (void)hipFree(p);
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                    std::string("ekf_dense64_score: ") + hipGetErrorString(e) + " while reserving the candidates' buffers");
+    }
+    if (small) d->sc_small = small;
+    if (Hs) {
+        if (d->sc_H) (void)hipFree(d->sc_H);   // (synchronises; no scoring call is in flight)
+        d->sc_H = Hs;
+        d->sc_H_doubles = sp.h_doubles;
+    }
+    if (ws) {
+        if (d->sc_ws) (void)hipFree(d->sc_ws);
+        d->sc_ws = ws;
+        d->sc_ws_doubles = sp.spart_doubles;
+    }
+    return EKF_OK;
+}
+
+ekf_status dense64_score(ekf_dense64_s* d, int J, int m, const double* H, const double* R, int r_shared,
+                         const double* nu, double* nis_out, double* S_out, int* flag_out, double* elapsed_ms) {
+    if (!d || !H || !R || J < 1 || m < 1 || m > kMaxM || m > d->N || (long long)J * m > kScoreRows ||
+        (nis_out && !nu) || (!nis_out && !S_out && !flag_out))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score: bad argument");
+    HIPC(hipSetDevice(d->device));
+    const int N = d->N, ld = d->ld;
+    const ekf::Dense64ScorePlan sp = ekf::dense64_score_plan(N, ld, J, m);
+    const ekf_status st = score_reserve(d, sp);
+    if (st != EKF_OK) return st;
+    const size_t mm = (size_t)m * m, w = sizeof(double) * N;
+    const int per = sp.cpg * m;   // rows of a full group
+    if (per == ekf::kDense64ScoreGroup) {
+        HIPC(hipMemcpy2DAsync(d->sc_H, sizeof(double) * ld, H, w, w, (size_t)J * m, hipMemcpyHostToDevice, d->stream));
+    } else {
+        for (int g = 0; g < sp.n_groups; g++) {
+            const int rows = std::min(sp.cpg, J - g * sp.cpg) * m;
+            HIPC(hipMemcpy2DAsync(d->sc_H + (size_t)g * ekf::kDense64ScoreGroup * ld, sizeof(double) * ld,
+                                  H + (size_t)g * per * N, w, w, rows, hipMemcpyHostToDevice, d->stream));
+        }
+    }
+    double* sm = d->sc_small;
+    HIPC(hipMemcpyAsync(sm + kScR, R, sizeof(double) * (r_shared ? mm : J * mm), hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(sm + kScNu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
+    double* ws = sp.spart_doubles > (size_t)ld * ld ? d->sc_ws : d->T;
+    int* flags = reinterpret_cast<int*>(sm + kScFlag);
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_score(sp, d->S, d->sc_H, ws, sm + kScR, r_shared ? 1 : 0, nu ? sm + kScNu : nullptr, J, m,
+                              nis_out ? sm + kScNis : nullptr, sm + kScS, flags, d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    if (nis_out) HIPC(hipMemcpyAsync(nis_out, sm + kScNis, sizeof(double) * J, hipMemcpyDeviceToHost, d->stream));
+    if (S_out) HIPC(hipMemcpyAsync(S_out, sm + kScS, sizeof(double) * J * mm, hipMemcpyDeviceToHost, d->stream));
+    if (flag_out) HIPC(hipMemcpyAsync(flag_out, flags, sizeof(int) * J, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -277,6 +368,10 @@ ekf_status ekf_dense64_get_state(ekf_dense64_handle d, double* out) {
 ekf_status ekf_dense64_correct(ekf_dense64_handle d, int m, const double* H, const double* R, const double* nu,
                                double* nis_out, double* elapsed_ms) {
     return dense64_correct(d, m, H, R, nu, nis_out, elapsed_ms);
+}
+ekf_status ekf_dense64_score(ekf_dense64_handle d, int J, int m, const double* H, const double* R, int r_shared,
+                             const double* nu, double* nis_out, double* S_out, int* flag_out, double* elapsed_ms) {
+    return dense64_score(d, J, m, H, R, r_shared, nu, nis_out, S_out, flag_out, elapsed_ms);
 }
 
 }  // extern "C"

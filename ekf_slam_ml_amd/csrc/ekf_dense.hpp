@@ -47,4 +47,25 @@ hipError_t dense64_correct_prepare();   // raises the dynamic-LDS limits (panel 
 void launch_dense64_correct(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws, const double* Hd,
                             const double* Ht, const double* R, const double* nu, int m, double* nis, int* verdict,
                             hipStream_t s);
+
+// ---- fp64 batched scoring of J candidate measurements (ekf_dense64_score.hip), read-only on the same Sigma:
+//   S_j = (H_j Sigma) H_j^T + R_j, nis_j = nu_j^T S_j^-1 nu_j, flag_j = S_j singular or not finite.
+constexpr int kDense64ScoreGroup = 64;      // rows of stacked Jacobians per row group; candidates are packed whole
+constexpr int kDense64ScoreMaxRows = 2048;  // EKF_DENSE64_SCORE_MAX_ROWS
+struct Dense64ScorePlan {
+    Dense64CorrectPlan panels;   // strips / chunks of the pass over Sigma: those of the correction, a function of (N, ld)
+    int cpg, n_groups;           // candidates per group = 64 / m, groups = ceil(J / cpg)
+    int n_parts;                 // partial S blocks per candidate = n_chunks * n_strips
+    size_t h_doubles;            // the stacked Jacobians on the device: [n_groups * 64][ld]
+    size_t spart_doubles;        // the partial blocks: [n_parts][J][m * m]
+};
+Dense64ScorePlan dense64_score_plan(int N, int ld, int J, int m);
+hipError_t dense64_score_prepare();   // raises the dynamic-LDS limits (panel pass 65 KiB at 64 rows, inversion 67 KiB)
+// The three launches of one scoring call on stream s.  Hs: [n_groups * 64][ld], row g * 64 + q * m + r = row r of candidate
+// g * cpg + q, columns N .. ld zero (rows without a candidate may hold anything); Spart: sp.spart_doubles doubles;
+// R: [J][m][m] or [m][m] (r_shared); nu: [J][m] or NULL with nis NULL; nis [J] nullable; S_io [J][m][m]: workspace that
+// holds the S_j on return; flag [J].
+void launch_dense64_score(const Dense64ScorePlan& sp, const double* Sigma, const double* Hs, double* Spart,
+                          const double* R, int r_shared, const double* nu, int J, int m, double* nis, double* S_io,
+                          int* flag, hipStream_t s);
 }  // namespace ekf

@@ -14,7 +14,8 @@
 //                   and per strip (U).
 //   2 k_dc_sum      partial panels summed in index order -> T [m][ld], U^T [m][ld] (entries >= N written as zeros)
 //   3 k_dc_spart    per 128-column chunk: T[:, chunk] H[:, chunk]^T (m x m)
-//   4 k_dc_invert   one workgroup: S = (sum of the chunks, in order) + R, Gauss-Jordan with partial pivoting in LDS, the
+//   4 k_dc_invert   one workgroup: S = (sum of the chunks, in order) + R, Gauss-Jordan with partial pivoting in LDS (the
+//                   routine of ekf_dense64_invert.hpp, shared with the candidate scoring of ekf_dense64_score.hip), the
 //                   verdict (zero / non-finite pivot, non-finite S or S^-1) into a device word, S^-1, nis
 //   5 k_dc_gain     K = U S^-1 (stored as K^T [m][ld]), state += K nu
 //   6 k_dc_update   Sigma <- Sigma - K T in place on v_mfma_f64_16x16x4_f64: the Sigma tile is the accumulator, -K comes
@@ -26,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ekf_dense.hpp"
+#include "ekf_dense64_invert.hpp"
 
 namespace ekf {
 
@@ -206,11 +208,10 @@ __global__ __launch_bounds__(256) void k_dc_invert(const double* __restrict__ Sp
                                                    int* __restrict__ verdict, int m) {
     extern __shared__ __attribute__((aligned(16))) double dc_smem[];
     double* M = dc_smem;                    // [m][kInvS]
-    double* prow = M + kMaxM * kInvS;       // [2 m] the scaled pivot row
-    double* fcol = prow + 2 * kMaxM;        // [m]   the column being eliminated
-    double* wv = fcol + kMaxM;              // [m]   S^-1 nu
-    __shared__ int s_bad, s_pr;   // s_bad: written by wave 0 before a barrier, read by everyone after it
+    __shared__ int s_ctl[2];
     __shared__ double s_pv;
+    // [2 m] the scaled pivot row | [m] the column being eliminated | [m] S^-1 nu
+    const GjScratch sc{M + kMaxM * kInvS, M + kMaxM * kInvS + 2 * kMaxM, M + kMaxM * kInvS + 3 * kMaxM, &s_pv, s_ctl};
     const int t = threadIdx.x;
     int bad = 0;
     for (int e = t; e < m * m; e += 256) {
@@ -222,72 +223,14 @@ __global__ __launch_bounds__(256) void k_dc_invert(const double* __restrict__ Sp
         M[k * kInvS + l] = v;
         M[k * kInvS + m + l] = k == l ? 1.0 : 0.0;
     }
-    if (__syncthreads_or(bad)) {   // a non-finite S
-        if (t == 0) verdict[0] = 1;
-        return;
-    }
-    for (int p = 0; p < m; p++) {
-        if (t < 64) {   // wave 0: the row with the largest |entry| of column p at or below the diagonal (lowest index on a tie)
-            const bool in = t >= p && t < m;
-            const double x = in ? M[t * kInvS + p] : 0.0;
-            double best = in ? fabs(x) : -1.0;
-            int bi = t;
-            const bool nonfinite = __any(in && !isfinite(x));
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const double ob = __shfl_xor(best, d);
-                const int oi = __shfl_xor(bi, d);
-                if (ob > best || (ob == best && oi < bi)) best = ob, bi = oi;
-            }
-            if (t == 0) {
-                s_pr = bi;
-                s_pv = M[bi * kInvS + p];
-                s_bad = (nonfinite || !(best > 0.0)) ? 1 : 0;
-            }
-        }
-        __syncthreads();
-        if (s_bad) {   // (uniform: read after the barrier, not written again) a zero or non-finite pivot
-            if (t == 0) verdict[0] = 1;
-            return;
-        }
-        const int pr = s_pr;
-        const double pv = s_pv;
-        if (t < 2 * m) {   // swap rows p and pr, scale the pivot row
-            const double x = M[pr * kInvS + t], y = M[p * kInvS + t];
-            const double v = x / pv;
-            M[pr * kInvS + t] = y;
-            M[p * kInvS + t] = v;
-            prow[t] = v;
-        }
-        __syncthreads();
-        if (t < m) fcol[t] = t == p ? 0.0 : M[t * kInvS + p];
-        __syncthreads();
-        for (int e = t; e < m * 2 * m; e += 256) {
-            const int r = e / (2 * m), c = e % (2 * m);
-            if (r != p) M[r * kInvS + c] = M[r * kInvS + c] - fcol[r] * prow[c];
-        }
-        __syncthreads();
-    }
-    bad = 0;
-    for (int e = t; e < m * m; e += 256)
-        if (!isfinite(M[(e / m) * kInvS + m + e % m])) bad = 1;
-    if (__syncthreads_or(bad)) {   // an inverse that overflowed
+    if (gj_invert<256>(M, kInvS, sc, m, t, bad)) {   // (uniform) the elimination of ekf_dense64_invert.hpp
         if (t == 0) verdict[0] = 1;
         return;
     }
     for (int e = t; e < m * m; e += 256) Sinv[(e / m) * kMaxM + e % m] = M[(e / m) * kInvS + m + e % m];
     if (nu) {   // nis = nu^T S^-1 nu, the score of calculate_maha_dis (:267-269)
-        if (t < m) {
-            double v = 0.0;
-            for (int l = 0; l < m; l++) v += M[t * kInvS + m + l] * nu[l];
-            wv[t] = v;
-        }
-        __syncthreads();
-        if (t == 0) {
-            double v = 0.0;
-            for (int k = 0; k < m; k++) v += nu[k] * wv[k];
-            nis[0] = v;
-        }
+        const double v = gj_quadratic<256>(M, kInvS, sc, m, t, nu);
+        if (t == 0) nis[0] = v;
     }
     if (t == 0) verdict[0] = 0;
 }

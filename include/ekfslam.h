@@ -471,6 +471,39 @@ ekf_status ekf_dense64_get_state(ekf_dense64_handle h, double* out /* N */);
 ekf_status ekf_dense64_correct(ekf_dense64_handle h, int m, const double* H, const double* R, const double* nu,
                                double* nis_out, double* elapsed_ms);
 
+/* Scoring of J candidate measurements against the covariance WITHOUT changing it -- the reference's calculate_maha_dis
+ * (ekf_slam.cpp:217-276: psi = Hj*sigma*Hj.t() + R, d = nu^T psi^-1 nu), called once per known landmark by
+ * data_association() (:300-314) before it decides which one to correct -- for J arbitrary dense m x N Jacobians at once:
+ *   S_j = (H_j Sigma) H_j^T + R_j      nis_j = nu_j^T S_j^-1 nu_j
+ * with the operand order of ekf_dense64_correct (rows of Sigma weighted by H_j first; Sigma is never symmetrised) and
+ * the same elimination with partial pivoting (one device routine serves both).
+ * H: [J][m][N] row-major; R: [J][m][m], or one [m][m] for all candidates when r_shared != 0; nu: [J][m], NULL allowed
+ * only when nis_out is NULL; nis_out [J], S_out [J][m][m] and flag_out [J] are each nullable, but not all three.
+ * 1 <= m <= min(N, EKF_DENSE64_MAX_M), J >= 1, J * m <= EKF_DENSE64_SCORE_MAX_ROWS.  A NULL handle / H / R, a bad J or m,
+ * nis_out without nu or no output at all return EKF_ERR_INVALID before the device is looked at.
+ * Read-only: Sigma, the state and every operand of propagate / correct are bit for bit what they were (the product
+ * buffer F * Sigma, dead between propagations, serves as workspace, as it does for correct).
+ * UNLIKE ekf_dense64_correct, where there is one S and nothing to go on with, a singular or non-finite S_j is not an
+ * error of the call: that candidate gets flag 1 and nis = NaN (S_out holds what was summed), the call returns EKF_OK and
+ * every other candidate's outputs are unaffected.
+ * A candidate's outputs do not depend on what else is in the call: alone or at any position of any batch with the same
+ * m, with R shared or replicated, they are the same bits; and the same from run to run (no floating-point atomics).
+ * The argmin and the gates are the caller's: INTEGRATION.md shows the reference's rule (:293-330) next to this call.
+ * Buffers for the candidates are allocated by the first call of a handle and grow with larger calls (the stacked
+ * Jacobians, 512 ld bytes per group of floor(64 / m) candidates; 2.1 MB of operands and results; partial blocks that do
+ * not fit the product buffer); a failure there returns EKF_ERR_NOMEM and leaves the handle as it was.
+ * Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the three launches only. */
+#define EKF_DENSE64_SCORE_MAX_ROWS 2048     /* J * m of one call */
+ekf_status ekf_dense64_score(ekf_dense64_handle h, int J, int m,
+                             const double* H,     /* [J][m][N], row-major, dense */
+                             const double* R,     /* [J][m][m], or [m][m] when r_shared != 0 */
+                             int r_shared,
+                             const double* nu,    /* [J][m] innovations; NULL allowed only when nis_out is NULL */
+                             double* nis_out,     /* [J]  nu_j^T S_j^-1 nu_j          (nullable) */
+                             double* S_out,       /* [J][m][m]  S_j = H_j Sigma H_j^T + R_j   (nullable) */
+                             int* flag_out,       /* [J]  0 = scored, 1 = S_j singular or not finite (nullable) */
+                             double* elapsed_ms); /* HIP-event time of the launches only (nullable) */
+
 /* ---- laser-scan front end: rigid2d::CircleFitting, batched ----------
  * std::vector<Vector2D> approxCirclePositions(std::vector<double> ranges)
  *                                          circle_fitting.hpp:27, circle_fitting.cpp:298-304
