@@ -43,7 +43,8 @@ SYMBOLS = [
     "ekf_dense_launch_info", "ekf_dense_tile_map",
     "ekf_dense64_create", "ekf_dense64_destroy", "ekf_dense64_set", "ekf_dense64_propagate", "ekf_dense64_get_sigma",
     "ekf_dense64_launch_info", "ekf_dense64_tile_map",
-    "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
+    "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
+    "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
     "ekf_phase_trace", "ekf_test_raise_device_error",
@@ -199,6 +200,7 @@ def load():
         "ekf_dense64_get_state": [h, _dp],
         "ekf_dense64_correct": [h, C.c_int, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_score": [h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
+        "ekf_dense64_propagate_block": [h, C.c_int, C.c_int, _dp, _dp, _dp, _dp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_set_known_counts": [h, _ip],
@@ -718,6 +720,7 @@ class DensePropagator64:
 
     MAX_M = 64   # EKF_DENSE64_MAX_M
     SCORE_MAX_ROWS = 2048   # EKF_DENSE64_SCORE_MAX_ROWS
+    MAX_R = 64   # EKF_DENSE64_MAX_R
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -824,6 +827,33 @@ class DensePropagator64:
                                            S.ctypes.data_as(_dp) if S is not None else None,
                                            flags.ctypes.data_as(_ip), C.byref(ms)))
         return nis, S, flags, ms.value
+
+    def propagate_block(self, first, Fr, Qr=None, dx=None):
+        """Block-structured prediction (ekf_slam.cpp:76-102 for a general model): Sigma <- F Sigma F^T + Q for F = identity
+        with Fr in [first, first + r)^2 and Q = zero with Qr in the same square; state[first:first + r] += dx.  Fr: r x r,
+        Qr: r x r or None (zero), dx: r or None (state untouched).  Only the block's rows and columns of Sigma are
+        written; the F and Q given to set() play no part.  Returns elapsed_ms."""
+        Fr = np.ascontiguousarray(Fr, dtype=np.float64)
+        if Fr.ndim != 2 or Fr.shape[0] != Fr.shape[1] or not 1 <= Fr.shape[0] <= min(self.N, self.MAX_R):
+            raise ValueError(f"Fr must be r x r with 1 <= r <= min(N, {self.MAX_R})")
+        r = Fr.shape[0]
+        first = int(first)
+        if not 0 <= first <= self.N - r:
+            raise ValueError("the block [first, first + r) must lie inside [0, N)")
+        pq, pdx = None, None
+        if Qr is not None:
+            Qr = np.ascontiguousarray(Qr, dtype=np.float64)
+            if Qr.shape != (r, r):
+                raise ValueError("Qr must be r x r")
+            pq = Qr.ctypes.data_as(_dp)
+        if dx is not None:
+            dx = np.ascontiguousarray(dx, dtype=np.float64)
+            if dx.shape != (r,):
+                raise ValueError("dx must have length r")
+            pdx = dx.ctypes.data_as(_dp)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_propagate_block(self._h, first, r, Fr.ctypes.data_as(_dp), pq, pdx, C.byref(ms)))
+        return ms.value
 
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""

@@ -1,7 +1,8 @@
 // ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: fp32 MFMA (configs[3],
 // ekf_dense.hip) and its fp64 twin (ekf_dense64.hip).  The host side of the two handles is one template over the element
 // type; the kernels stay separate.  The fp64 handle also owns a state vector, the dense measurement update for a
-// general Jacobian (ekf_dense64_correct.hip) and the read-only scoring of candidate measurements (ekf_dense64_score.hip).
+// general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip) and
+// the block-structured prediction (ekf_dense64_block.hip).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -28,6 +29,8 @@ struct ekf_dense64_s : DenseHandle<double> {
     double* sc_H = nullptr;      // the stacked Jacobians, [groups * 64][ld], columns N .. ld zero
     double* sc_ws = nullptr;     // the partial S blocks of a call that do not fit the product buffer T
     size_t sc_H_doubles = 0, sc_ws_doubles = 0;
+    // block-structured prediction (ekf_dense64_propagate_block)
+    double* blk_in = nullptr;    // Fr [64 * 64] | Qr [64 * 64] | dx [64]
 };
 
 namespace {
@@ -52,6 +55,8 @@ struct DenseOps64 {
 };
 
 constexpr int kMaxM = ekf::kDense64MaxM;
+constexpr int kMaxR = ekf::kDense64MaxR;
+constexpr size_t kBlkQ = (size_t)kMaxR * kMaxR, kBlkDx = 2 * kBlkQ, kBlkIn = kBlkDx + kMaxR;
 inline size_t corr_in_doubles(int ld) { return (size_t)2 * kMaxM * ld + kMaxM * kMaxM + kMaxM; }
 
 template <class H>
@@ -62,7 +67,7 @@ ekf_status dense_destroy(H* d) {
     for (auto* p : {d->F, d->S, d->T, d->Q})
         if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
-        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws})
+        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws, d->blk_in})
             if (p) (void)hipFree(p);
     for (hipEvent_t e : {d->e0, d->e1})
         if (e) (void)hipEventDestroy(e);
@@ -109,6 +114,8 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
             HIPC(hipMalloc((void**)&d->corr_out, 2 * sizeof(double)));
             const size_t ws = ekf::dense64_correct_plan(N, d->ld).ws_doubles;
             if (ws > (size_t)d->ld * d->ld) HIPC(hipMalloc((void**)&d->ws_own, sizeof(double) * ws));
+            HIPC(ekf::dense64_block_prepare());
+            HIPC(hipMalloc((void**)&d->blk_in, sizeof(double) * kBlkIn));
         }
         HIPC(hipEventCreate(&d->e0));
         HIPC(hipEventCreate(&d->e1));
@@ -316,6 +323,31 @@ ekf_status dense64_score(ekf_dense64_s* d, int J, int m, const double* H, const 
     return EKF_OK;
 }
 
+// The block-structured prediction: Fr, Qr and dx go up, one launch, timed by the handle's events.  The stored F and Q of
+// the handle are not involved.
+ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const double* Fr, const double* Qr,
+                                   const double* dx, double* elapsed_ms) {
+    if (!d || !Fr || r < 1 || r > kMaxR || first < 0 || r > d->N || first > d->N - r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_propagate_block: bad argument");
+    HIPC(hipSetDevice(d->device));
+    const size_t rr = sizeof(double) * r * r;
+    HIPC(hipMemcpyAsync(d->blk_in, Fr, rr, hipMemcpyHostToDevice, d->stream));
+    if (Qr) HIPC(hipMemcpyAsync(d->blk_in + kBlkQ, Qr, rr, hipMemcpyHostToDevice, d->stream));
+    if (dx) HIPC(hipMemcpyAsync(d->blk_in + kBlkDx, dx, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_block(d->S, d->x, d->blk_in, Qr ? d->blk_in + kBlkQ : nullptr, dx ? d->blk_in + kBlkDx : nullptr,
+                              d->N, d->ld, first, r, d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -372,6 +404,10 @@ ekf_status ekf_dense64_correct(ekf_dense64_handle d, int m, const double* H, con
 ekf_status ekf_dense64_score(ekf_dense64_handle d, int J, int m, const double* H, const double* R, int r_shared,
                              const double* nu, double* nis_out, double* S_out, int* flag_out, double* elapsed_ms) {
     return dense64_score(d, J, m, H, R, r_shared, nu, nis_out, S_out, flag_out, elapsed_ms);
+}
+ekf_status ekf_dense64_propagate_block(ekf_dense64_handle d, int first, int r, const double* Fr, const double* Qr,
+                                       const double* dx, double* elapsed_ms) {
+    return dense64_propagate_block(d, first, r, Fr, Qr, dx, elapsed_ms);
 }
 
 }  // extern "C"

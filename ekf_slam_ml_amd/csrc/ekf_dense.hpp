@@ -68,4 +68,15 @@ hipError_t dense64_score_prepare();   // raises the dynamic-LDS limits (panel pa
 void launch_dense64_score(const Dense64ScorePlan& sp, const double* Sigma, const double* Hs, double* Spart,
                           const double* R, int r_shared, const double* nu, int J, int m, double* nis, double* S_io,
                           int* flag, hipStream_t s);
+
+// ---- fp64 block-structured prediction (ekf_dense64_block.hip) on the same Sigma and state: F = identity with the r x r
+// Jacobian Fr in [first, first + r)^2, Q = zero with Qr in the same square.  One launch of 1 + 2 ceil(N / 64) workgroups
+// (the corner, the row panel and the column panel in strips of 64); touches nothing outside the block's rows and columns.
+constexpr int kDense64MaxR = 64;   // EKF_DENSE64_MAX_R
+size_t dense64_block_lds_bytes(int r);   // dynamic LDS of the launch: one r x 64 tile, 32.5 KiB at r = 64
+hipError_t dense64_block_prepare();      // nothing to raise at that size; kept so that every dense64 kernel file has one
+// Fr: r x r row-major, Qr: r x r or NULL, dx: r or NULL (state untouched), all on the device; 1 <= r <= 64,
+// 0 <= first, first + r <= N (the launcher does not check).
+void launch_dense64_block(double* Sigma, double* state, const double* Fr, const double* Qr, const double* dx, int N,
+                          int ld, int first, int r, hipStream_t s);
 }  // namespace ekf

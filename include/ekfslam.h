@@ -504,6 +504,37 @@ ekf_status ekf_dense64_score(ekf_dense64_handle h, int J, int m,
                              int* flag_out,       /* [J]  0 = scored, 1 = S_j singular or not finite (nullable) */
                              double* elapsed_ms); /* HIP-event time of the launches only (nullable) */
 
+/* Block-structured prediction: the motion model every SLAM caller has -- a dynamic block of r states anywhere in the
+ * vector with an arbitrary r x r Jacobian, everything else static.  The reference's prediction() (ekf_slam.cpp:76-102)
+ * builds At = eye + A with A non-zero in the pose rows only and Q non-zero in the pose block only; this call is that
+ * shape for a general model.  It gives what ekf_dense64_propagate(h, 1, ..) gives for `sigma = At*sigma*At.t() + Q`
+ * (:101-102) in its association (At*sigma)*At.t() + Q with
+ *   F = identity with Fr written into [first, first + r)^2        Q = zero with Qr written into the same square
+ * that is, with b = [first, first + r):
+ *   Sigma[b, j] <- Fr Sigma[b, j]   for every column j outside b   (rows of Sigma)
+ *   Sigma[i, b] <- Sigma[i, b] Fr^T for every row i outside b      (COLUMNS of Sigma: Sigma is never symmetrised)
+ *   Sigma[b, b] <- (Fr Sigma[b, b]) Fr^T + Qr                      (the inner product rounded to fp64 first)
+ *   state[first + k] += dx[k]       when dx is given               (state = state + update, :99)
+ * and no entry outside the block's rows and columns is written: 32 r N bytes move instead of the two N^3 products.
+ * Fr: r x r row-major; Qr: r x r row-major, NULL = zero; dx: r, NULL = state untouched.
+ * 1 <= r <= min(N, EKF_DENSE64_MAX_R), 0 <= first, first + r <= N.  A NULL handle or Fr, or a bad first or r, returns
+ * EKF_ERR_INVALID before the device is looked at.
+ * The F and Q stored by ekf_dense64_set are neither read nor changed, the padding of Sigma and of the state stays zero,
+ * so the two ways of predicting alternate freely with ekf_dense64_correct and ekf_dense64_score without Sigma leaving
+ * the device.  Memory: 66 KB of operands (Fr, Qr, dx) allocated with the handle; nothing of size ld^2, no workspace.
+ * One launch, no floating-point atomics.  Every dot product has exactly r terms, accumulated from +0 in ascending k
+ * with one fused multiply-add per term, an order that does not depend on N, ld, first or the launch geometry: the same
+ * block data gives the same bits wherever the block sits, whatever N is, on every run.
+ * The non-linear motion function that produces dx and any wrapping of an angle in the state stay with the caller: the
+ * entry point is model-free.  Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the
+ * launch only (no H2D of Fr / Qr / dx). */
+#define EKF_DENSE64_MAX_R 64
+ekf_status ekf_dense64_propagate_block(ekf_dense64_handle h, int first, int r,
+                                       const double* Fr,    /* r x r row-major */
+                                       const double* Qr,    /* r x r row-major, NULL = zero */
+                                       const double* dx,    /* r, NULL = state untouched */
+                                       double* elapsed_ms); /* HIP-event time of the launch only (nullable) */
+
 /* ---- laser-scan front end: rigid2d::CircleFitting, batched ----------
  * std::vector<Vector2D> approxCirclePositions(std::vector<double> ranges)
  *                                          circle_fitting.hpp:27, circle_fitting.cpp:298-304
