@@ -44,6 +44,7 @@ SYMBOLS = [
     "ekf_dense64_create", "ekf_dense64_destroy", "ekf_dense64_set", "ekf_dense64_propagate", "ekf_dense64_get_sigma",
     "ekf_dense64_launch_info", "ekf_dense64_tile_map",
     "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
+    "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
@@ -201,6 +202,8 @@ def load():
         "ekf_dense64_correct": [h, C.c_int, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_score": [h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
         "ekf_dense64_propagate_block": [h, C.c_int, C.c_int, _dp, _dp, _dp, _dp],
+        "ekf_dense64_correct_sparse": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
+        "ekf_dense64_score_sparse": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_set_known_counts": [h, _ip],
@@ -721,6 +724,8 @@ class DensePropagator64:
     MAX_M = 64   # EKF_DENSE64_MAX_M
     SCORE_MAX_ROWS = 2048   # EKF_DENSE64_SCORE_MAX_ROWS
     MAX_R = 64   # EKF_DENSE64_MAX_R
+    MAX_S = 64   # EKF_DENSE64_MAX_S
+    SCORE_SPARSE_MAX_ROWS = 65536   # EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -854,6 +859,81 @@ class DensePropagator64:
         ms = C.c_double()
         _check(self._lib.ekf_dense64_propagate_block(self._h, first, r, Fr.ctypes.data_as(_dp), pq, pdx, C.byref(ms)))
         return ms.value
+
+    def _index_lists(self, cols, ndim):
+        """cols as a contiguous int32 array of `ndim` dimensions whose rows hold distinct indices in [0, N)"""
+        a = np.asarray(cols)
+        if a.ndim != ndim or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"cols must be an integer array of {ndim} dimension(s), not empty")
+        if not 1 <= a.shape[-1] <= min(self.N, self.MAX_S):
+            raise ValueError(f"cols must list s columns with 1 <= s <= min(N, {self.MAX_S})")
+        if a.min() < 0 or a.max() >= self.N:
+            raise ValueError("every index in cols must lie in [0, N)")
+        srt = np.sort(a, axis=-1)
+        if (srt[..., 1:] == srt[..., :-1]).any():
+            raise ValueError("no index may appear twice in one row of cols")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def correct_sparse(self, cols, Hc, R, nu=None):
+        """correct() for the m x N Jacobian that is zero except H[:, cols[k]] = Hc[:, k] -- the reference's Hj has five
+        such columns (ekf_slam.cpp:140-178).  cols: s distinct indices in [0, N), Hc: m x s, R: m x m, nu: m or None
+        (state untouched).  The panels are gathered from s rows and s columns of Sigma instead of a pass over it; every
+        dot product has exactly s terms in ascending k.  Returns (nis or None, elapsed_ms); a singular or non-finite S
+        raises EkfError (EKF_ERR_STATE) and leaves state and Sigma as they were."""
+        cols = self._index_lists(cols, 1)
+        s = cols.shape[0]
+        Hc = np.ascontiguousarray(Hc, dtype=np.float64)
+        if Hc.ndim != 2 or Hc.shape[1] != s or not 1 <= Hc.shape[0] <= min(self.N, self.MAX_M):
+            raise ValueError(f"Hc must be m x s with 1 <= m <= min(N, {self.MAX_M})")
+        m = Hc.shape[0]
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.shape != (m, m):
+            raise ValueError("R must be m x m")
+        nis, pnu, pnis = None, None, None
+        if nu is not None:
+            nu = np.ascontiguousarray(nu, dtype=np.float64)
+            if nu.shape != (m,):
+                raise ValueError("nu must have length m")
+            nis = C.c_double()
+            pnu, pnis = nu.ctypes.data_as(_dp), C.byref(nis)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_correct_sparse(self._h, m, s, cols.ctypes.data_as(_ip), Hc.ctypes.data_as(_dp),
+                                                    R.ctypes.data_as(_dp), pnu, pnis, C.byref(ms)))
+        return (nis.value if nis is not None else None), ms.value
+
+    def score_sparse(self, cols, Hc, R, nu=None, want_S=False):
+        """score() for J Jacobians given by their non-zero columns: H_j is zero except H_j[:, cols[j, k]] = Hc[j, :, k].
+        cols: (J, s) with distinct indices in every row, Hc: (J, m, s); R: (m, m) shared or (J, m, m); nu: (J, m) or None.
+        Only the s x s blocks Sigma[cols_j, cols_j] are read, in one launch; J * m may reach SCORE_SPARSE_MAX_ROWS, so a
+        reading is scored against every landmark of a full map in one call.  Returns what score() returns."""
+        cols = self._index_lists(cols, 2)
+        J, s = cols.shape
+        Hc = np.ascontiguousarray(Hc, dtype=np.float64)
+        if Hc.ndim != 3 or Hc.shape[0] != J or Hc.shape[2] != s or not 1 <= Hc.shape[1] <= min(self.N, self.MAX_M):
+            raise ValueError(f"Hc must be J x m x s with 1 <= m <= min(N, {self.MAX_M})")
+        m = Hc.shape[1]
+        if J * m > self.SCORE_SPARSE_MAX_ROWS:
+            raise ValueError(f"J * m must not exceed {self.SCORE_SPARSE_MAX_ROWS}")
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.shape != (m, m) and R.shape != (J, m, m):
+            raise ValueError("R must be m x m or J x m x m")
+        nis, S, pnu = None, None, None
+        if nu is not None:
+            nu = np.ascontiguousarray(nu, dtype=np.float64)
+            if nu.shape != (J, m):
+                raise ValueError("nu must be J x m")
+            nis = np.empty(J, dtype=np.float64)
+            pnu = nu.ctypes.data_as(_dp)
+        if want_S:
+            S = np.empty((J, m, m), dtype=np.float64)
+        flags = np.empty(J, dtype=np.int32)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_score_sparse(self._h, J, m, s, cols.ctypes.data_as(_ip), Hc.ctypes.data_as(_dp),
+                                                  R.ctypes.data_as(_dp), 1 if R.ndim == 2 else 0, pnu,
+                                                  nis.ctypes.data_as(_dp) if nis is not None else None,
+                                                  S.ctypes.data_as(_dp) if S is not None else None,
+                                                  flags.ctypes.data_as(_ip), C.byref(ms)))
+        return nis, S, flags, ms.value
 
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""

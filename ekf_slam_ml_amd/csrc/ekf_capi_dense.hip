@@ -1,8 +1,9 @@
 // ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: fp32 MFMA (configs[3],
 // ekf_dense.hip) and its fp64 twin (ekf_dense64.hip).  The host side of the two handles is one template over the element
 // type; the kernels stay separate.  The fp64 handle also owns a state vector, the dense measurement update for a
-// general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip) and
-// the block-structured prediction (ekf_dense64_block.hip).
+// general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip),
+// the block-structured prediction (ekf_dense64_block.hip) and the update and scoring for a Jacobian given by its
+// non-zero columns (ekf_dense64_sparse.hip).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -31,6 +32,10 @@ struct ekf_dense64_s : DenseHandle<double> {
     size_t sc_H_doubles = 0, sc_ws_doubles = 0;
     // block-structured prediction (ekf_dense64_propagate_block)
     double* blk_in = nullptr;    // Fr [64 * 64] | Qr [64 * 64] | dx [64]
+    // column-sparse scoring (ekf_dense64_score_sparse): one buffer, nothing until the first call, grows with the calls
+    char* sps = nullptr;         // Hc | R | nu | nis | S | cols (ints) | flags (ints), cut per call
+    size_t sps_bytes = 0;
+    std::vector<int> host_stamp; // [N] the duplicate check of the index lists
 };
 
 namespace {
@@ -69,6 +74,8 @@ ekf_status dense_destroy(H* d) {
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
         for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws, d->blk_in})
             if (p) (void)hipFree(p);
+    if constexpr (std::is_same<H, ekf_dense64_s>::value)
+        if (d->sps) (void)hipFree(d->sps);
     for (hipEvent_t e : {d->e0, d->e1})
         if (e) (void)hipEventDestroy(e);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -116,6 +123,7 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
             if (ws > (size_t)d->ld * d->ld) HIPC(hipMalloc((void**)&d->ws_own, sizeof(double) * ws));
             HIPC(ekf::dense64_block_prepare());
             HIPC(hipMalloc((void**)&d->blk_in, sizeof(double) * kBlkIn));
+            HIPC(ekf::dense64_sparse_prepare());
         }
         HIPC(hipEventCreate(&d->e0));
         HIPC(hipEventCreate(&d->e1));
@@ -348,6 +356,120 @@ ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const dou
     return EKF_OK;
 }
 
+// ---- a Jacobian given by its s non-zero columns ---------------------------------------------------------------------------
+constexpr int kMaxS = ekf::kDense64MaxS;
+constexpr int kSparseRows = ekf::kDense64ScoreSparseMaxRows;
+
+// every row of cols [rows][s]: indices in [0, N), no index twice
+bool index_lists_ok(std::vector<int>& stamp, int N, int rows, int s, const int* cols) {
+    stamp.assign(N, 0);
+    for (int j = 0; j < rows; j++)
+        for (int k = 0; k < s; k++) {
+            const int c = cols[(size_t)j * s + k];
+            if (c < 0 || c >= N || stamp[c] == j + 1) return false;
+            stamp[c] = j + 1;
+        }
+    return true;
+}
+
+// One sparse correction: cols, Hc, R, nu go up into the (otherwise unused) operand buffer of the dense correction -- Hc and
+// the list where its H would sit, R and nu in their usual places -- four launches, the verdict and nis come back in one copy.
+ekf_status dense64_correct_sparse(ekf_dense64_s* d, int m, int s, const int* cols, const double* Hc, const double* R,
+                                  const double* nu, double* nis_out, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse: null handle");
+    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse: bad argument");
+    if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse: cols must hold distinct indices in [0, N)");
+    HIPC(hipSetDevice(d->device));
+    const int N = d->N, ld = d->ld;
+    const size_t oCols = (size_t)kMaxM * kMaxS, oR = (size_t)2 * kMaxM * ld, oNu = oR + kMaxM * kMaxM;   // (64 ld >= 8192)
+    HIPC(hipMemcpyAsync(d->corr_in, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(d->corr_in + oCols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(d->corr_in + oR, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(d->corr_in + oNu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
+    const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
+    double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_correct_sparse(pl, d->S, d->x, ws, reinterpret_cast<const int*>(d->corr_in + oCols), d->corr_in,
+                                       d->corr_in + oR, nu ? d->corr_in + oNu : nullptr, m, s, d->corr_out,
+                                       reinterpret_cast<int*>(d->corr_out + 1), d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    double out[2] = {0.0, 0.0};
+    HIPC(hipMemcpyAsync(out, d->corr_out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    int verdict = 0;
+    std::memcpy(&verdict, &out[1], sizeof(int));
+    if (verdict != 0)
+        return fail(EKF_ERR_STATE, "ekf_dense64_correct_sparse: H Sigma H^T + R is singular or not finite (zero or "
+                                   "non-finite pivot); state and Sigma are unchanged");
+    if (nis_out) *nis_out = out[0];
+    return EKF_OK;
+}
+
+// Sparse scoring of J candidates: the operands go up into one buffer (allocated into a local, the members change only when
+// that succeeded), one launch, the outputs come straight back into the caller's arrays.
+ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int* cols, const double* Hc, const double* R,
+                                int r_shared, const double* nu, double* nis_out, double* S_out, int* flag_out,
+                                double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: null handle");
+    if (!cols || !Hc || !R || J < 1 || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N ||
+        (long long)J * m > kSparseRows || (nis_out && !nu) || (!nis_out && !S_out && !flag_out))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: bad argument");
+    if (!index_lists_ok(d->host_stamp, d->N, J, s, cols))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: every row of cols must hold distinct indices in [0, N)");
+    HIPC(hipSetDevice(d->device));
+    const size_t mm = (size_t)m * m, al = 16;
+    auto up = [&](size_t b) { return (b + al - 1) / al * al; };
+    const size_t bHc = sizeof(double) * J * m * s, bR = sizeof(double) * (r_shared ? mm : J * mm);
+    const size_t oR = up(bHc), oNu = oR + up(bR), oNis = oNu + up(sizeof(double) * J * m), oS = oNis + up(sizeof(double) * J);
+    const size_t oCols = oS + (S_out ? up(sizeof(double) * J * mm) : 0), oFlag = oCols + up(sizeof(int) * J * s);
+    const size_t need = oFlag + up(sizeof(int) * J);
+    if (need > d->sps_bytes) {
+        char* fresh = nullptr;
+        const hipError_t e = hipMalloc((void**)&fresh, need);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                        std::string("ekf_dense64_score_sparse: ") + hipGetErrorString(e) +
+                            " while reserving the candidates' buffer");
+        }
+        if (d->sps) (void)hipFree(d->sps);   // (synchronises; no scoring call is in flight)
+        d->sps = fresh;
+        d->sps_bytes = need;
+    }
+    char* b = d->sps;
+    double *dHc = reinterpret_cast<double*>(b), *dR = reinterpret_cast<double*>(b + oR);
+    double *dNu = reinterpret_cast<double*>(b + oNu), *dNis = reinterpret_cast<double*>(b + oNis);
+    double* dS = S_out ? reinterpret_cast<double*>(b + oS) : nullptr;
+    int *dCols = reinterpret_cast<int*>(b + oCols), *dFlag = reinterpret_cast<int*>(b + oFlag);
+    HIPC(hipMemcpyAsync(dHc, Hc, bHc, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(dR, R, bR, hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(dNu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(dCols, cols, sizeof(int) * J * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_score_sparse(d->S, dCols, dHc, dR, r_shared ? 1 : 0, nu ? dNu : nullptr, J, m, s, d->ld,
+                                     nis_out ? dNis : nullptr, dS, dFlag, nullptr, d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    if (nis_out) HIPC(hipMemcpyAsync(nis_out, dNis, sizeof(double) * J, hipMemcpyDeviceToHost, d->stream));
+    if (S_out) HIPC(hipMemcpyAsync(S_out, dS, sizeof(double) * J * mm, hipMemcpyDeviceToHost, d->stream));
+    if (flag_out) HIPC(hipMemcpyAsync(flag_out, dFlag, sizeof(int) * J, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -408,6 +530,15 @@ ekf_status ekf_dense64_score(ekf_dense64_handle d, int J, int m, const double* H
 ekf_status ekf_dense64_propagate_block(ekf_dense64_handle d, int first, int r, const double* Fr, const double* Qr,
                                        const double* dx, double* elapsed_ms) {
     return dense64_propagate_block(d, first, r, Fr, Qr, dx, elapsed_ms);
+}
+ekf_status ekf_dense64_correct_sparse(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
+                                      const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    return dense64_correct_sparse(d, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+}
+ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, const int* cols, const double* Hc,
+                                    const double* R, int r_shared, const double* nu, double* nis_out, double* S_out,
+                                    int* flag_out, double* elapsed_ms) {
+    return dense64_score_sparse(d, J, m, s, cols, Hc, R, r_shared, nu, nis_out, S_out, flag_out, elapsed_ms);
 }
 
 }  // extern "C"

@@ -79,4 +79,25 @@ hipError_t dense64_block_prepare();      // nothing to raise at that size; kept 
 // 0 <= first, first + r <= N (the launcher does not check).
 void launch_dense64_block(double* Sigma, double* state, const double* Fr, const double* Qr, const double* dx, int N,
                           int ld, int first, int r, hipStream_t s);
+
+// ---- fp64 measurement update and scoring for a Jacobian with s listed non-zero columns (ekf_dense64_sparse.hip):
+// H[:, cols[k]] = Hc[:, k], every dot product exactly s fused multiply-adds in ascending k of the list.
+constexpr int kDense64MaxS = 64;                     // EKF_DENSE64_MAX_S
+constexpr int kDense64ScoreSparseMaxRows = 65536;    // EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
+hipError_t dense64_sparse_prepare();   // raises the dynamic-LDS limits (gather 64.8 KiB, scoring up to 98.8 KiB)
+// One launch: per candidate S_j = (Hc_j Sigma[cols_j, cols_j]) Hc_j^T + R_j, flag_j, nis_j.  All pointers on the device:
+// cols [J][s] (distinct, in [0, N): the launcher does not check), Hc [J][m][s], R [J][m][m] or [m][m] (r_shared),
+// nu [J][m] or NULL with nis NULL, nis [J] nullable, S_out [J][m][m] nullable, flag [J], Sinv [64][64] nullable (the
+// inverse of candidate 0 when its flag is 0).
+void launch_dense64_score_sparse(const double* Sigma, const int* cols, const double* Hc, const double* R, int r_shared,
+                                 const double* nu, int J, int m, int s, int ld, double* nis, double* S_out, int* flag,
+                                 double* Sinv, hipStream_t st);
+// Launches 5 and 6 of launch_dense64_correct (k_dc_gain, k_dc_update) on panels and an S^-1 already in ws.
+void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws, const double* nu,
+                                 int m, const int* verdict, hipStream_t s);
+// The four launches of one sparse correction: the panel gather into ws (off_T, off_Ut), the scoring kernel with J = 1
+// (S^-1 into off_Sinv, the verdict word, nis), then the gain and the update of the dense correction.
+void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
+                                   const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
+                                   double* nis, int* verdict, hipStream_t st);
 }  // namespace ekf

@@ -444,4 +444,17 @@ void launch_dense64_correct(const Dense64CorrectPlan& pl, double* Sigma, double*
                        pl.upd_blocks_per_chunk);
 }
 
+// Launches 5 and 6 alone, for a caller that has put T, U^T and S^-1 into ws itself (ekf_dense64_sparse.hip).
+void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws, const double* nu,
+                                 int m, const int* verdict, hipStream_t s) {
+    double* Tp = ws + pl.off_T;
+    double* Ut = ws + pl.off_Ut;
+    double* Kt = ws + pl.off_Kt;
+    double* Sinv = ws + pl.off_Sinv;
+    hipLaunchKernelGGL(k_dc_gain, dim3((pl.N + kGainRows - 1) / kGainRows), dim3(256), 0, s, Ut, Sinv, nu, Kt, state, verdict, pl.N, pl.ld, m);
+    hipLaunchKernelGGL(k_dc_update, dim3(pl.upd_strips, pl.upd_chunks), dim3(256),
+                       sizeof(double) * (size_t)((m + 3) & ~3) * kUpdCols, s, Sigma, Kt, Tp, verdict, pl.N, pl.ld, m,
+                       pl.upd_blocks_per_chunk);
+}
+
 }  // namespace ekf

@@ -1,0 +1,252 @@
+// ekf_dense64_sparse.hip -- the measurement update and the candidate scoring of the dense fp64 handle for a Jacobian that
+// is zero outside s listed columns (1 <= s <= 64): H[:, cols[k]] = Hc[:, k].  The reference's Hj has five such columns
+// (rigid2d/src/ekf_slam.cpp:140-178: the pose columns 0, 1, 2 and the landmark columns 3 + 2 i, 4 + 2 i), so
+//   T = H Sigma  is a combination of s ROWS of Sigma,     T[a][j] = sum_k Hc[a][k] Sigma[cols[k]][j]
+//   U = Sigma H^T  of s COLUMNS (Sigma is never symmetrised), U[i][a] = sum_k Sigma[i][cols[k]] Hc[a][k]
+//   S = T H^T + R  needs the s x s block Sigma[cols, cols] only, S[a][b] = (sum_k T[a][cols[k]] Hc[b][k]) + R[a][b]
+// and neither call has to stream Sigma to build them.
+//   k_dsp_gather   the two panels of a correction, written where k_dc_gain / k_dc_update (ekf_dense64_correct.hip) read
+//                  them: workgroups 0 .. n - 1 a strip of 64 columns of T each (s row segments of 512 contiguous bytes),
+//                  workgroups n .. 2 n - 1 a strip of 64 rows of U^T each (64 segments of s gathered doubles, loaded with
+//                  the lanes running ALONG the list so that neighbouring indices such as 0, 1, 2 share a cache line; the
+//                  transpose happens on the way through LDS, as in k_d64_block).  Both are then one product
+//                  out[a][c] = sum_k Hc[a][k] X[k][c] with Hc^T in LDS; the panels' padding (c >= N) is written as zero.
+//   k_dsp_score    per candidate: cols and Hc into LDS, the s x s block gathered, T' = Hc G (m x s, rounded to fp64), S,
+//                  the elimination of ekf_dense64_invert.hpp, flag, nis.  A wave per candidate (four to a workgroup)
+//                  where m <= 16 and four candidates fit 64 KiB of LDS, a workgroup per candidate otherwise; the same
+//                  operations in the same order either way.  ekf_dense64_score_sparse is ONE launch of it over J
+//                  candidates; ekf_dense64_correct_sparse launches it with J = 1 (and S^-1 written out), so a score and
+//                  the correction that follows it with the same operands see the same S, nis and verdict bit for bit.
+// The order of every dot product: acc = +0; acc = fma(x_k, y_k, acc) for k = 0, 1, .. s - 1 of the list -- exactly s
+// terms, one fused multiply-add per term (written as fma() because the library is built with -ffp-contract=off), a
+// function of nothing but s.  R enters by one plain addition.  No atomics.  So the same Sigma[cols, cols], Hc, R, nu give
+// the same bits wherever the columns sit, in any N, at any position of any batch, on every run.
+#include <hip/hip_runtime.h>
+
+#include "ekf_dense.hpp"
+#include "ekf_dense64_invert.hpp"
+
+namespace ekf {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int kMaxM = kDense64MaxM;
+constexpr int kMaxS = kDense64MaxS;
+constexpr int kStrip = 64;        // columns (rows) of a panel strip
+constexpr int kXS = kStrip + 1;   // LDS row stride of X: conflict-free both ways
+constexpr int kThreads = 256;
+constexpr int kBatch = kMaxS * kStrip / kThreads;   // elements of a tile per thread
+
+// ---- the panels --------------------------------------------------------------------------------------------------------
+// Tp, Ut: [m][ld] (row stride ld), the layout of Dense64CorrectPlan::off_T / off_Ut.
+__global__ __launch_bounds__(kThreads) void k_dsp_gather(const double* __restrict__ S, const int* __restrict__ cols,
+                                                         const double* __restrict__ Hc, double* __restrict__ Tp,
+                                                         double* __restrict__ Ut, int N, int ld, int m, int s,
+                                                         int n_strips) {
+    extern __shared__ __attribute__((aligned(32))) double sp_smem[];
+    const int m4 = (m + 3) & ~3;
+    double* Hct = sp_smem;          // [s][m4]: Hct[k][a] = Hc[a][k], zero for a >= m
+    double* X = Hct + s * m4;       // [s][kXS]
+    int* lc = reinterpret_cast<int*>(X + s * kXS);   // [s]
+    const int t = threadIdx.x, c = t & 63, w = t >> 6;
+    const int kind = (int)blockIdx.x >= n_strips ? 1 : 0;   // 0: columns of T, 1: rows of U^T
+    const int base = ((int)blockIdx.x - kind * n_strips) * kStrip;
+
+    // Every global load of a phase is issued before the first of its results is used (at most kBatch = 16 per thread).
+    double v[kBatch];
+#pragma unroll
+    for (int p = 0; p < kBatch; p++) {
+        if (p * kThreads >= s * m4) break;   // (uniform)
+        const int e = t + p * kThreads;
+        const int k = e / m4, a = e - k * m4;
+        v[p] = (e < s * m4 && a < m) ? Hc[a * s + k] : 0.0;
+    }
+    if (t < s) lc[t] = cols[t];
+#pragma unroll
+    for (int p = 0; p < kBatch; p++) {
+        if (p * kThreads >= s * m4) break;
+        const int e = t + p * kThreads;
+        if (e < s * m4) Hct[e] = v[p];
+    }
+    __syncthreads();
+    auto split = [&](int e, int& k, int& cc) {   // lanes run along what is contiguous (or nearly so) in memory
+        if (kind == 1) { cc = e / s; k = e - cc * s; }
+        else { k = e >> 6; cc = e & 63; }
+    };
+#pragma unroll
+    for (int p = 0; p < kBatch; p++) {
+        if (p * kThreads >= s * kStrip) break;
+        const int e = t + p * kThreads;
+        int k = 0, cc = 0;
+        split(e, k, cc);
+        double x = 0.0;
+        if (e < s * kStrip && base + cc < N)
+            x = kind == 0 ? S[(size_t)lc[k] * ld + base + cc] : S[(size_t)(base + cc) * ld + lc[k]];
+        v[p] = x;
+    }
+#pragma unroll
+    for (int p = 0; p < kBatch; p++) {
+        if (p * kThreads >= s * kStrip) break;
+        const int e = t + p * kThreads;
+        int k = 0, cc = 0;
+        split(e, k, cc);
+        if (e < s * kStrip) X[k * kXS + cc] = v[p];
+    }
+    __syncthreads();
+
+    // out[a][c] = sum_k Hc[a][k] X[k][c], k ascending; wave w owns a = 16 q + 4 w + (0..3)
+    double* out = (kind == 0 ? Tp : Ut) + base + c;
+    const bool real = base + c < N;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int a0 = 16 * q + 4 * w;
+        if (a0 >= m) break;   // (uniform in the wave)
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < s; k++) {
+            const double x = X[k * kXS + c];
+            const f64x4 f = *reinterpret_cast<const f64x4*>(Hct + k * m4 + a0);
+#pragma unroll
+            for (int u = 0; u < 4; u++) acc[u] = fma(f[u], x, acc[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (a0 + u < m) out[(size_t)(a0 + u) * ld] = real ? acc[u] : 0.0;   // the panels' padding is zero
+    }
+}
+
+// ---- S, its inverse, flag, nis of one candidate --------------------------------------------------------------------------
+// LDS of a candidate, in doubles: Hc [m][s] | G [s][s], T' [m][s] -- later [S | I] [m][2 m + 1] over both | 4 m + 1 of
+// scratch.  The index lists and the control words of all candidates of the workgroup follow as ints.
+__host__ __device__ constexpr int sparse_big(int m, int s) {
+    return s * s + m * s > m * (2 * m + 1) ? s * s + m * s : m * (2 * m + 1);
+}
+__host__ __device__ constexpr int sparse_cand_doubles(int m, int s) {
+    return (m * s + sparse_big(m, s) + 4 * m + 1 + 1) & ~1;
+}
+constexpr size_t sparse_score_lds(int per, int m, int s) {
+    return ((sizeof(double) * (size_t)per * sparse_cand_doubles(m, s) + sizeof(int) * (size_t)per * (s + 2)) + 15) &
+           ~(size_t)15;
+}
+constexpr int kWaveM = 16;                   // up to here a wave per candidate, LDS permitting
+constexpr size_t kWaveLds = 64 * 1024;       // what four candidates of a workgroup may take together
+
+// NT threads per candidate, 256 / NT candidates per workgroup; EPT = elements of S per thread (m * m <= NT * EPT).
+// cols [J][s], Hc [J][m][s], R [J][m][m] or [m][m], nu [J][m] or NULL with nis NULL, S_out [J][m][m] or NULL, flag [J],
+// Sinv [64][64] (stride 64) or NULL: written for candidate 0 when its S is regular.
+template <int NT, int EPT>
+__global__ __launch_bounds__(kThreads) void k_dsp_score(const double* __restrict__ Sigma, const int* __restrict__ cols,
+                                                        const double* __restrict__ Hc, const double* __restrict__ R,
+                                                        int r_shared, const double* __restrict__ nu,
+                                                        double* __restrict__ nis, double* __restrict__ S_out,
+                                                        int* __restrict__ flag, double* __restrict__ Sinv, int ld, int m,
+                                                        int s, int J) {
+    extern __shared__ __attribute__((aligned(32))) double sp_smem[];
+    constexpr int PER = kThreads / NT;
+    const int sub = threadIdx.x / NT, t = threadIdx.x % NT;
+    const int cand = blockIdx.x * PER + sub;
+    if (cand >= J) return;   // (uniform over the candidate's thread group; NT = 64 takes no workgroup barrier)
+    const int cd = sparse_cand_doubles(m, s), mm = m * m, ms = m * s, stride = 2 * m + 1;
+    double* hc = sp_smem + sub * cd;     // [m][s]
+    double* G = hc + ms;                 // [s][s] = Sigma[cols, cols]
+    double* Tl = G + s * s;              // [m][s] = Hc G
+    double* M = G;                       // [m][stride], once G and T' are spent
+    double* tail = G + sparse_big(m, s);
+    int* lc = reinterpret_cast<int*>(sp_smem + PER * cd) + sub * (s + 2);
+    const GjScratch sc{tail, tail + 2 * m, tail + 3 * m, tail + 4 * m, lc + s};
+
+    for (int e = t; e < s; e += NT) lc[e] = cols[(size_t)cand * s + e];
+    for (int e = t; e < ms; e += NT) hc[e] = Hc[(size_t)cand * ms + e];
+    gj_sync<NT>();
+    for (int e = t; e < s * s; e += NT) {   // lanes along the list: neighbouring indices share a cache line
+        const int a = e / s, b = e - a * s;
+        G[e] = Sigma[(size_t)lc[a] * ld + lc[b]];
+    }
+    gj_sync<NT>();
+    for (int e = t; e < ms; e += NT) {      // T'[a][b] = T[a][cols[b]] = sum_k Hc[a][k] Sigma[cols[k]][cols[b]]
+        const int a = e / s, b = e - a * s;
+        double acc = 0.0;
+        for (int k = 0; k < s; k++) acc = fma(hc[a * s + k], G[k * s + b], acc);
+        Tl[e] = acc;
+    }
+    gj_sync<NT>();
+    const double* Rc = R + (r_shared ? 0 : (size_t)cand * mm);
+    double sv[EPT];
+    int bad = 0;
+#pragma unroll
+    for (int q = 0; q < EPT; q++) {
+        const int e = t + NT * q;
+        sv[q] = 0.0;
+        if (e < mm) {
+            const int a = e / m, b = e - a * m;
+            double acc = 0.0;
+            for (int k = 0; k < s; k++) acc = fma(Tl[a * s + k], hc[b * s + k], acc);
+            const double val = acc + Rc[e];
+            if (!isfinite(val)) bad = 1;
+            if (S_out) S_out[(size_t)cand * mm + e] = val;
+            sv[q] = val;
+        }
+    }
+    gj_sync<NT>();   // every thread of the group is done with G and T'
+#pragma unroll
+    for (int q = 0; q < EPT; q++) {
+        const int e = t + NT * q;
+        if (e < mm) {
+            const int a = e / m, b = e - a * m;
+            M[a * stride + b] = sv[q];
+            M[a * stride + m + b] = a == b ? 1.0 : 0.0;
+        }
+    }
+    const int verdict = gj_invert<NT>(M, stride, sc, m, t, bad);   // (uniform over the group)
+    if (Sinv && cand == 0 && !verdict)
+        for (int e = t; e < mm; e += NT) Sinv[(e / m) * kMaxM + e % m] = M[(e / m) * stride + m + e % m];
+    double val = __builtin_nan("");
+    if (nis && !verdict) val = gj_quadratic<NT>(M, stride, sc, m, t, nu + (size_t)cand * m);
+    if (t == 0) {
+        if (nis) nis[cand] = val;
+        flag[cand] = verdict;
+    }
+}
+
+size_t gather_lds(int m, int s) {
+    return (sizeof(double) * ((size_t)s * ((m + 3) & ~3) + (size_t)s * kXS) + sizeof(int) * (size_t)s + 15) & ~(size_t)15;
+}
+
+}  // namespace
+
+hipError_t dense64_sparse_prepare() {
+    // gather: 64.8 KiB at m = s = 64; scoring: 64 KiB for four waves, 98.8 KiB for the workgroup at m = s = 64
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_dsp_gather),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)gather_lds(kMaxM, kMaxS));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dsp_score<64, 4>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWaveLds);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dsp_score<256, 16>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sparse_score_lds(1, kMaxM, kMaxS));
+}
+
+void launch_dense64_score_sparse(const double* Sigma, const int* cols, const double* Hc, const double* R, int r_shared,
+                                 const double* nu, int J, int m, int s, int ld, double* nis, double* S_out, int* flag,
+                                 double* Sinv, hipStream_t st) {
+    if (m <= kWaveM && sparse_score_lds(4, m, s) <= kWaveLds)
+        hipLaunchKernelGGL((k_dsp_score<64, 4>), dim3((J + 3) / 4), dim3(kThreads), sparse_score_lds(4, m, s), st, Sigma,
+                           cols, Hc, R, r_shared, nu, nis, S_out, flag, Sinv, ld, m, s, J);
+    else
+        hipLaunchKernelGGL((k_dsp_score<256, 16>), dim3(J), dim3(kThreads), sparse_score_lds(1, m, s), st, Sigma, cols,
+                           Hc, R, r_shared, nu, nis, S_out, flag, Sinv, ld, m, s, J);
+}
+
+void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
+                                   const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
+                                   double* nis, int* verdict, hipStream_t st) {
+    const int n_strips = pl.ld / kStrip;   // ld is a multiple of 128: the panels are written up to ld
+    hipLaunchKernelGGL(k_dsp_gather, dim3(2 * n_strips), dim3(kThreads), gather_lds(m, s), st, Sigma, cols, Hc,
+                       ws + pl.off_T, ws + pl.off_Ut, pl.N, pl.ld, m, s, n_strips);
+    launch_dense64_score_sparse(Sigma, cols, Hc, R, 1, nu, 1, m, s, pl.ld, nu ? nis : nullptr, nullptr, verdict,
+                                ws + pl.off_Sinv, st);
+    launch_dense64_correct_tail(pl, Sigma, state, ws, nu, m, verdict, st);
+}
+
+}  // namespace ekf

@@ -535,6 +535,56 @@ ekf_status ekf_dense64_propagate_block(ekf_dense64_handle h, int first, int r,
                                        const double* dx,    /* r, NULL = state untouched */
                                        double* elapsed_ms); /* HIP-event time of the launch only (nullable) */
 
+/* Measurement update and scoring for a Jacobian given by its non-zero columns: the Jacobian every landmark-SLAM caller
+ * has.  The reference's Hj (ekf_slam.cpp:140-178) is non-zero in five columns, the pose columns 0, 1, 2 and the landmark
+ * columns 3 + 2 i, 4 + 2 i.  H is the m x N matrix that is zero except H[:, cols[k]] = Hc[:, k], k = 0 .. s - 1;
+ * ekf_dense64_correct_sparse is ekf_dense64_correct for that H and ekf_dense64_score_sparse is ekf_dense64_score for
+ * those H_j, with the same operand order (T = H Sigma from rows of Sigma, U = Sigma H^T from columns, Sigma never
+ * symmetrised), the same elimination, the same verdict rule and the same nullability of nu / nis_out / S_out / flag_out
+ * and meaning of r_shared.  What changes is the cost: the panels of a correction are gathered from s rows and s columns
+ * of Sigma (O(s N) bytes instead of a pass over Sigma; four launches instead of six, the last two -- gain and rank-m
+ * update, 16 N^2 bytes -- being the dense call's own), and a score needs the s x s block Sigma[cols_j, cols_j] alone (one
+ * launch, no pass over Sigma, candidates as [J][m][s] instead of [J][m][N]).
+ * cols: distinct indices in [0, N) in any order (per candidate: [J][s], each row distinct); Hc: m x s row-major
+ * ([J][m][s]); 1 <= m <= min(N, EKF_DENSE64_MAX_M), 1 <= s <= min(N, EKF_DENSE64_MAX_S), m > s is allowed (R makes S
+ * regular), J >= 1, J * m <= EKF_DENSE64_SCORE_SPARSE_MAX_ROWS -- the reference's data_association() scores a reading
+ * against every known landmark (:300-314), 5000 candidates at N = 10003, in one call.
+ * A NULL handle (checked first), NULL cols / Hc / R, a bad m, s or J, a negative, out-of-range or repeated index in any
+ * row of cols (checked on the host), nis_out without nu or, for the scoring, no output at all return EKF_ERR_INVALID
+ * before the device is looked at.  A singular or non-finite S returns EKF_ERR_STATE from the correction and leaves state
+ * and Sigma bit for bit (the verdict word is read before the first store); in the scoring it is flag 1 and nis = NaN for
+ * that candidate only and the call returns EKF_OK.  The scoring is read-only.  The padding of Sigma and of the state
+ * stays zero, so propagate_block / score_sparse / correct_sparse make a whole SLAM cycle without Sigma leaving the device
+ * (INTEGRATION.md spells the reference's loop with them).
+ * ORDER OF ARITHMETIC (part of the contract): every entry of T, of U and of S - R is a dot product of exactly s terms,
+ * accumulated from +0 in ascending k of the list with one fused multiply-add per term:
+ *   T[a][j] = sum_k Hc[a][k] Sigma[cols[k]][j]     U[i][a] = sum_k Sigma[i][cols[k]] Hc[a][k]
+ *   S[a][b] = (sum_k T[a][cols[k]] Hc[b][k]) + R[a][b]      (the inner T rounded to fp64 first, R by one plain addition)
+ * S, its elimination, nis and the flag come from one device routine that both entry points launch, and there are no
+ * floating-point atomics.  So S, nis and flag of a candidate are the same bits alone or at any position of any batch,
+ * with R shared or replicated, in score_sparse and in the correct_sparse that follows with the same operands, wherever
+ * the listed columns sit in Sigma (in any N) given the same values of Sigma[cols, cols], and from run to run.  Permuting
+ * cols together with the columns of Hc changes the order of the sums: the result agrees to rounding, not bit for bit;
+ * nor is it bit-equal to the dense calls, which sum per-chunk partials.
+ * Memory: the correction uses the operand buffer and workspace of ekf_dense64_correct; the scoring allocates one buffer
+ * for its operands and results on first use (8 (J m s + J m m + ..) bytes, nothing of size ld^2), which grows with larger
+ * calls; a failure there returns EKF_ERR_NOMEM and leaves the handle as it was.
+ * Both are model-free (wrapping an angle is the caller's business) and synchronous, on the handle's stream.
+ * elapsed_ms (nullable) = HIP-event time of the launches only. */
+#define EKF_DENSE64_MAX_S 64                       /* listed columns of one Jacobian */
+#define EKF_DENSE64_SCORE_SPARSE_MAX_ROWS 65536    /* J * m of one ekf_dense64_score_sparse call */
+ekf_status ekf_dense64_correct_sparse(ekf_dense64_handle h, int m, int s,
+                                      const int* cols,      /* [s] distinct column indices in [0, N) */
+                                      const double* Hc,     /* m x s row-major: column k is H[:, cols[k]] */
+                                      const double* R,      /* m x m */
+                                      const double* nu,     /* m, NULL: state untouched, nis_out must be NULL */
+                                      double* nis_out, double* elapsed_ms);
+ekf_status ekf_dense64_score_sparse(ekf_dense64_handle h, int J, int m, int s,
+                                    const int* cols,        /* [J][s], each row distinct */
+                                    const double* Hc,       /* [J][m][s] */
+                                    const double* R, int r_shared, const double* nu,
+                                    double* nis_out, double* S_out, int* flag_out, double* elapsed_ms);
+
 /* ---- laser-scan front end: rigid2d::CircleFitting, batched ----------
  * std::vector<Vector2D> approxCirclePositions(std::vector<double> ranges)
  *                                          circle_fitting.hpp:27, circle_fitting.cpp:298-304
