@@ -45,6 +45,7 @@ SYMBOLS = [
     "ekf_dense64_launch_info", "ekf_dense64_tile_map",
     "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
+    "ekf_dense64_init_block", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
@@ -204,6 +205,10 @@ def load():
         "ekf_dense64_propagate_block": [h, C.c_int, C.c_int, _dp, _dp, _dp, _dp],
         "ekf_dense64_correct_sparse": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_score_sparse": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
+        "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
+        "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
+        "ekf_dense64_get_state_block": [h, C.c_int, C.c_int, _dp],
+        "ekf_dense64_set_state_block": [h, C.c_int, C.c_int, _dp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_set_known_counts": [h, _ip],
@@ -726,6 +731,7 @@ class DensePropagator64:
     MAX_R = 64   # EKF_DENSE64_MAX_R
     MAX_S = 64   # EKF_DENSE64_MAX_S
     SCORE_SPARSE_MAX_ROWS = 65536   # EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
+    READ_MAX = 65536   # EKF_DENSE64_READ_MAX
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -934,6 +940,102 @@ class DensePropagator64:
                                                   S.ctypes.data_as(_dp) if S is not None else None,
                                                   flags.ctypes.data_as(_ip), C.byref(ms)))
         return nis, S, flags, ms.value
+
+    def init_block(self, first, G=None, cols=None, W=None, xb=None, r=None):
+        """(Re)initialise the states b = [first, first + r) as a function of the s states in cols: Sigma <- F Sigma F^T + Q
+        for F = identity with F[b, b] = 0, F[b, cols] = G and Q = zero with Q[b, b] = W; state[b] = xb.  G: r x s with cols
+        (s distinct indices in [0, N), none inside b), or both None (s = 0: the block's rows and columns become +0, its
+        corner W, Sigma is not read -- with W = 100 I the prior of the reference's constructor, ekf_slam.cpp:27-36);
+        W: r x r or None (no addition); xb: r or None (state untouched); r: taken from G, W or xb when not given.  Only
+        the block's rows and columns of Sigma are written; the corner is bit for bit the S of
+        score_sparse(cols[None], G[None], W) taken before the call.  Returns elapsed_ms."""
+        if (G is None) != (cols is None):
+            raise ValueError("G and cols come together (both None: s = 0)")
+        if G is not None:
+            G = np.ascontiguousarray(G, dtype=np.float64)
+            if G.ndim != 2:
+                raise ValueError("G must be r x s")
+        if W is not None:
+            W = np.ascontiguousarray(W, dtype=np.float64)
+            if W.ndim != 2 or W.shape[0] != W.shape[1]:
+                raise ValueError("W must be r x r")
+        if xb is not None:
+            xb = np.ascontiguousarray(xb, dtype=np.float64)
+            if xb.ndim != 1:
+                raise ValueError("xb must have length r")
+        sizes = [int(r)] if r is not None else []
+        sizes += [a.shape[0] for a in (G, W, xb) if a is not None]
+        if not sizes or any(v != sizes[0] for v in sizes):
+            raise ValueError("r must be given by r, G, W or xb, and all of them must agree")
+        r = sizes[0]
+        if not 1 <= r <= min(self.N, self.MAX_R):
+            raise ValueError(f"1 <= r <= min(N, {self.MAX_R})")
+        first = int(first)
+        if not 0 <= first <= self.N - r:
+            raise ValueError("the block [first, first + r) must lie inside [0, N)")
+        s, pc, pg = 0, None, None
+        if cols is not None:
+            a = np.asarray(cols)
+            if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("cols must be a one-dimensional integer array, not empty (s = 0: cols = G = None)")
+            s = a.shape[0]
+            if s > min(self.N - r, self.MAX_S):
+                raise ValueError(f"cols must list s columns with s <= min(N - r, {self.MAX_S})")
+            if a.min() < 0 or a.max() >= self.N:
+                raise ValueError("every index in cols must lie in [0, N)")
+            if len(np.unique(a)) != s:
+                raise ValueError("no index may appear twice in cols")
+            if ((a >= first) & (a < first + r)).any():
+                raise ValueError("no index of cols may lie inside [first, first + r): that case is propagate_block")
+            if G.shape != (r, s):
+                raise ValueError("G must be r x s")
+            cols = np.ascontiguousarray(a, dtype=np.int32)
+            pc, pg = cols.ctypes.data_as(_ip), G.ctypes.data_as(_dp)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_init_block(self._h, first, r, s, pc, pg,
+                                                W.ctypes.data_as(_dp) if W is not None else None,
+                                                xb.ctypes.data_as(_dp) if xb is not None else None, C.byref(ms)))
+        return ms.value
+
+    def _read_list(self, idx, name):
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must be a one-dimensional integer array, not empty")
+        if a.min() < 0 or a.max() >= self.N:
+            raise ValueError(f"every index in {name} must lie in [0, N)")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def sigma_block(self, rows, cols):
+        """Sigma[np.ix_(rows, cols)] without reading Sigma back: one small gather on the device and one copy.  Indices
+        in [0, N), repeats and any order allowed, len(rows) * len(cols) <= READ_MAX."""
+        rows, cols = self._read_list(rows, "rows"), self._read_list(cols, "cols")
+        if len(rows) * len(cols) > self.READ_MAX:
+            raise ValueError(f"len(rows) * len(cols) must not exceed {self.READ_MAX}")
+        out = np.empty((len(rows), len(cols)), dtype=np.float64)
+        _check(self._lib.ekf_dense64_get_sigma_block(self._h, len(rows), rows.ctypes.data_as(_ip), len(cols),
+                                                     cols.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
+        return out
+
+    def _state_range(self, first, count):
+        first, count = int(first), int(count)
+        if count < 1 or first < 0 or first + count > self.N:
+            raise ValueError("the slice [first, first + count) must be non-empty and lie inside [0, N)")
+        return first, count
+
+    def state_block(self, first, count):
+        """state[first:first + count] without moving the whole vector"""
+        first, count = self._state_range(first, count)
+        out = np.empty(count, dtype=np.float64)
+        _check(self._lib.ekf_dense64_get_state_block(self._h, first, count, out.ctypes.data_as(_dp)))
+        return out
+
+    def set_state_block(self, first, x):
+        """state[first:first + len(x)] = x; the rest of the state is not touched"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 1:
+            raise ValueError("x must be one-dimensional")
+        first, count = self._state_range(first, x.shape[0])
+        _check(self._lib.ekf_dense64_set_state_block(self._h, first, count, x.ctypes.data_as(_dp)))
 
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""

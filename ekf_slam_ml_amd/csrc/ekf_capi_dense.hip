@@ -2,8 +2,9 @@
 // ekf_dense.hip) and its fp64 twin (ekf_dense64.hip).  The host side of the two handles is one template over the element
 // type; the kernels stay separate.  The fp64 handle also owns a state vector, the dense measurement update for a
 // general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip),
-// the block-structured prediction (ekf_dense64_block.hip) and the update and scoring for a Jacobian given by its
-// non-zero columns (ekf_dense64_sparse.hip).
+// the block-structured prediction (ekf_dense64_block.hip), the update and scoring for a Jacobian given by its non-zero
+// columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states and the block readout
+// (ekf_dense64_init.hip).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -36,6 +37,9 @@ struct ekf_dense64_s : DenseHandle<double> {
     char* sps = nullptr;         // Hc | R | nu | nis | S | cols (ints) | flags (ints), cut per call
     size_t sps_bytes = 0;
     std::vector<int> host_stamp; // [N] the duplicate check of the index lists
+    // (re)initialisation of a block (ekf_dense64_init_block) and the block readout (ekf_dense64_get_sigma_block)
+    double* ini_in = nullptr;    // G [64 * 64] | W [64 * 64] | xb [64] | cols (ints) [64]
+    double* rd_buf = nullptr;    // out [65536] | rows (ints) [65536] | cols (ints) [65536]
 };
 
 namespace {
@@ -62,6 +66,10 @@ struct DenseOps64 {
 constexpr int kMaxM = ekf::kDense64MaxM;
 constexpr int kMaxR = ekf::kDense64MaxR;
 constexpr size_t kBlkQ = (size_t)kMaxR * kMaxR, kBlkDx = 2 * kBlkQ, kBlkIn = kBlkDx + kMaxR;
+constexpr size_t kIniW = (size_t)kMaxR * ekf::kDense64MaxS, kIniXb = kIniW + (size_t)kMaxR * kMaxR, kIniCols = kIniXb + kMaxR,
+                 kIniIn = kIniCols + ekf::kDense64MaxS / 2;
+constexpr int kReadMax = ekf::kDense64ReadMax;
+constexpr size_t kRdRows = kReadMax, kRdCols = kRdRows + kReadMax / 2, kRdBuf = kRdCols + kReadMax / 2;
 inline size_t corr_in_doubles(int ld) { return (size_t)2 * kMaxM * ld + kMaxM * kMaxM + kMaxM; }
 
 template <class H>
@@ -72,7 +80,8 @@ ekf_status dense_destroy(H* d) {
     for (auto* p : {d->F, d->S, d->T, d->Q})
         if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
-        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws, d->blk_in})
+        for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws, d->blk_in, d->ini_in,
+                          d->rd_buf})
             if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
         if (d->sps) (void)hipFree(d->sps);
@@ -124,6 +133,9 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
             HIPC(ekf::dense64_block_prepare());
             HIPC(hipMalloc((void**)&d->blk_in, sizeof(double) * kBlkIn));
             HIPC(ekf::dense64_sparse_prepare());
+            HIPC(ekf::dense64_init_prepare());
+            HIPC(hipMalloc((void**)&d->ini_in, sizeof(double) * kIniIn));
+            HIPC(hipMalloc((void**)&d->rd_buf, sizeof(double) * kRdBuf));
         }
         HIPC(hipEventCreate(&d->e0));
         HIPC(hipEventCreate(&d->e1));
@@ -470,6 +482,79 @@ ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int
     return EKF_OK;
 }
 
+// ---- (re)initialisation of a block of states, block readouts, state slices ----------------------------------------------
+// G, W, xb and the list go up into the buffer allocated with the handle, one launch, timed by the handle's events.  The
+// stored F and Q of the handle are not involved.
+ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const int* cols, const double* G, const double* W,
+                              const double* xb, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: null handle");
+    if (r < 1 || r > kMaxR || r > d->N || first < 0 || first > d->N - r || s < 0 || s > kMaxS || s > d->N - r ||
+        (s > 0 && (!cols || !G)))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: bad argument");
+    if (s > 0) {
+        if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
+            return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: cols must hold distinct indices in [0, N)");
+        for (int k = 0; k < s; k++)
+            if (cols[k] >= first && cols[k] < first + r)
+                return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: no index of cols may lie inside [first, first + r) "
+                                             "(the in-place case is ekf_dense64_propagate_block)");
+    }
+    HIPC(hipSetDevice(d->device));
+    double* in = d->ini_in;
+    int* dcols = reinterpret_cast<int*>(in + kIniCols);
+    if (s > 0) {
+        HIPC(hipMemcpyAsync(in, G, sizeof(double) * r * s, hipMemcpyHostToDevice, d->stream));
+        HIPC(hipMemcpyAsync(dcols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    }
+    if (W) HIPC(hipMemcpyAsync(in + kIniW, W, sizeof(double) * r * r, hipMemcpyHostToDevice, d->stream));
+    if (xb) HIPC(hipMemcpyAsync(in + kIniXb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->N, d->ld,
+                             first, r, s, d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    return EKF_OK;
+}
+
+// out[a][c] = Sigma[rows[a]][cols[c]]: the two lists go up, one gather launch into the handle's buffer, one copy back.
+ekf_status dense64_get_sigma_block(ekf_dense64_s* d, int nr, const int* rows, int nc, const int* cols, double* out) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: null handle");
+    if (!rows || !cols || !out || nr < 1 || nc < 1 || (long long)nr * nc > kReadMax)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: bad argument");
+    for (int a = 0; a < nr; a++)
+        if (rows[a] < 0 || rows[a] >= d->N)
+            return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: every index of rows must lie in [0, N)");
+    for (int c = 0; c < nc; c++)
+        if (cols[c] < 0 || cols[c] >= d->N)
+            return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: every index of cols must lie in [0, N)");
+    HIPC(hipSetDevice(d->device));
+    int *drows = reinterpret_cast<int*>(d->rd_buf + kRdRows), *dcols = reinterpret_cast<int*>(d->rd_buf + kRdCols);
+    HIPC(hipMemcpyAsync(drows, rows, sizeof(int) * nr, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(dcols, cols, sizeof(int) * nc, hipMemcpyHostToDevice, d->stream));
+    ekf::launch_dense64_read_block(d->S, drows, dcols, d->rd_buf, nr, nc, d->ld, d->stream);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out, d->rd_buf, sizeof(double) * nr * nc, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+
+ekf_status dense64_state_block(const char* name, ekf_dense64_s* d, int first, int count, double* out, const double* x) {
+    if (!d) return fail(EKF_ERR_INVALID, std::string(name) + ": null handle");
+    if ((!out && !x) || count < 1 || first < 0 || count > d->N || first > d->N - count)
+        return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
+    HIPC(hipSetDevice(d->device));
+    if (out) HIPC(hipMemcpyAsync(out, d->x + first, sizeof(double) * count, hipMemcpyDeviceToHost, d->stream));
+    else HIPC(hipMemcpyAsync(d->x + first, x, sizeof(double) * count, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -539,6 +624,20 @@ ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, c
                                     const double* R, int r_shared, const double* nu, double* nis_out, double* S_out,
                                     int* flag_out, double* elapsed_ms) {
     return dense64_score_sparse(d, J, m, s, cols, Hc, R, r_shared, nu, nis_out, S_out, flag_out, elapsed_ms);
+}
+ekf_status ekf_dense64_init_block(ekf_dense64_handle d, int first, int r, int s, const int* cols, const double* G,
+                                  const double* W, const double* xb, double* elapsed_ms) {
+    return dense64_init_block(d, first, r, s, cols, G, W, xb, elapsed_ms);
+}
+ekf_status ekf_dense64_get_sigma_block(ekf_dense64_handle d, int nr, const int* rows, int nc, const int* cols,
+                                       double* out) {
+    return dense64_get_sigma_block(d, nr, rows, nc, cols, out);
+}
+ekf_status ekf_dense64_get_state_block(ekf_dense64_handle d, int first, int count, double* out) {
+    return dense64_state_block("ekf_dense64_get_state_block", d, first, count, out, nullptr);
+}
+ekf_status ekf_dense64_set_state_block(ekf_dense64_handle d, int first, int count, const double* x) {
+    return dense64_state_block("ekf_dense64_set_state_block", d, first, count, nullptr, x);
 }
 
 }  // extern "C"

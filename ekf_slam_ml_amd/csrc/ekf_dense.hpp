@@ -100,4 +100,20 @@ void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, do
 void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
                                    const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
                                    double* nis, int* verdict, hipStream_t st);
+
+// ---- fp64 (re)initialisation of a block of states (ekf_dense64_init.hip) on the same Sigma and state: the block
+// b = [first, first + r) becomes a function of the s listed states with Jacobian G (r x s): F = identity with F[b, b] = 0
+// and F[b, cols] = G, Q = zero with W in the block's square.  One launch of 1 + 2 ceil(N / 64) workgroups (the corner, the
+// row panel and the column panel in strips of 64); reads rows cols and columns cols outside b only (nothing at s = 0),
+// writes the block's rows and columns only.
+constexpr int kDense64ReadMax = 65536;   // EKF_DENSE64_READ_MAX: entries of one block readout
+size_t dense64_init_lds_bytes(int r, int s);   // dynamic LDS of the launch: 64.8 KiB at r = s = 64, none at s = 0
+hipError_t dense64_init_prepare();             // raises the dynamic-LDS limit to that
+// cols [s] (distinct, in [0, N), none in b: the launcher does not check), G: r x s row-major, both unused at s = 0;
+// W: r x r or NULL (no addition); xb: r or NULL (state untouched); all on the device.  1 <= r <= 64, 0 <= s <= 64.
+void launch_dense64_init(double* Sigma, double* state, const int* cols, const double* G, const double* W,
+                         const double* xb, int N, int ld, int first, int r, int s, hipStream_t st);
+// out[a][c] = Sigma[rows[a]][cols[c]], nr * nc <= kDense64ReadMax, every index in [0, N) (not checked here)
+void launch_dense64_read_block(const double* Sigma, const int* rows, const int* cols, double* out, int nr, int nc, int ld,
+                               hipStream_t st);
 }  // namespace ekf

@@ -585,6 +585,61 @@ ekf_status ekf_dense64_score_sparse(ekf_dense64_handle h, int J, int m, int s,
                                     const double* R, int r_shared, const double* nu,
                                     double* nis_out, double* S_out, int* flag_out, double* elapsed_ms);
 
+/* (Re)initialisation of a block of states: what a map that grows, or a fixed-capacity map that recycles a slot, does to
+ * Sigma.  The states b = [first, first + r) are replaced by a new variable y = g(x[cols], z) of s other states and a
+ * reading z: G (r x s) is the Jacobian of g with respect to x[cols], W the caller's Gz R Gz^T, xb the value g(..).  The
+ * call gives what ekf_dense64_propagate(h, 1, ..) gives with
+ *   F = identity except F[b, b] = 0 and F[b, cols] = G          Q = zero except Q[b, b] = W
+ * that is
+ *   Sigma[b, j] <- sum_k G[a][k] Sigma[cols[k]][j]   for every column j outside b   (s ROWS of Sigma are read)
+ *   Sigma[i, b] <- sum_k Sigma[i][cols[k]] G[a][k]   for every row i outside b      (s COLUMNS: Sigma is never symmetrised)
+ *   Sigma[b, b] <- (G Sigma[cols, cols]) G^T + W     (the inner r x s product rounded to fp64 first; W by one plain
+ *                                                     addition; W = NULL: no addition)
+ *   state[first + k] <- xb[k]                        when xb is given
+ * and nothing else is written: the old content of the block's rows and columns is not read and does not leak into the
+ * result, the padding of Sigma and of the state stays zero, the F and Q of ekf_dense64_set are neither read nor changed.
+ * s = 0 (cols = G = NULL) drops the block: its rows and columns become +0, its corner W, and Sigma is not read at all.
+ * With W = 100 I that is the prior the reference's constructor gives every landmark (ekf_slam.cpp:27-36), and with xb from
+ * initialize_landmark (:200-214) the whole of the reference's initialisation; s = 3, cols = {0, 1, 2} and G the derivative
+ * of the inverse sensor model with respect to the pose is the textbook correlated initialisation (INTEGRATION.md spells
+ * both).  32 (r + s) N bytes move instead of ekf_dense64_set's 8 N^2 or a dense propagation with an embedded F.
+ * 1 <= r <= min(N, EKF_DENSE64_MAX_R), 0 <= s <= min(N - r, EKF_DENSE64_MAX_S), 0 <= first, first + r <= N; cols: distinct
+ * indices in [0, N), none of them inside b.  Lists that overlap b are not supported: the in-place case cols = b is
+ * ekf_dense64_propagate_block.  A NULL handle (checked first), a bad first, r or s, NULL cols or G with s > 0, an index
+ * that is negative, out of range, repeated or inside b return EKF_ERR_INVALID before the device is looked at; Sigma and the
+ * state are then as they were.
+ * ORDER OF ARITHMETIC (part of the contract): every entry is a dot product of exactly s terms, accumulated from +0 in
+ * ascending k of the list with one fused multiply-add per term; the corner is
+ *   S[a][d] = (sum_k T'[a][k] G[d][k]) + W[a][d],   T'[a][k] = sum_j G[a][j] Sigma[cols[j]][cols[k]]  rounded to fp64
+ * the order ekf_dense64_score_sparse uses for S: the new corner is bit for bit the S_out of
+ * ekf_dense64_score_sparse(h, 1, r, s, cols, G, W, ..) taken before the call.  One launch, no floating-point atomics, an
+ * order that does not depend on N, ld, first or the launch geometry: the same source values give the same bits wherever
+ * they sit, whatever N is, on every run.
+ * Memory: 66 KB of operands (G, W, xb, cols) allocated with the handle; the call allocates nothing.  Model-free (g, its
+ * Jacobians and any wrapping of an angle stay with the caller), synchronous, on the handle's stream.  elapsed_ms
+ * (nullable) = HIP-event time of the launch only. */
+ekf_status ekf_dense64_init_block(ekf_dense64_handle h, int first, int r, int s,
+                                  const int* cols,     /* [s] distinct, in [0, N), none inside [first, first + r); NULL iff s == 0 */
+                                  const double* G,     /* r x s row-major; NULL iff s == 0 */
+                                  const double* W,     /* r x r row-major, NULL = no addition */
+                                  const double* xb,    /* r: state[first + k] = xb[k]; NULL = state untouched */
+                                  double* elapsed_ms); /* HIP-event time of the launch only (nullable) */
+
+/* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
+ * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
+ * ekf_dense64_get_sigma_block: out[a][c] = Sigma[rows[a]][cols[c]], nr x nc row-major; one gather launch into a buffer
+ * allocated with the handle and one copy.  nr, nc >= 1, nr * nc <= EKF_DENSE64_READ_MAX, indices in [0, N), repeats
+ * allowed, any order.  Read-only.
+ * ekf_dense64_get_state_block / ekf_dense64_set_state_block: copies of `count` doubles from / to state[first ..],
+ * 1 <= count, 0 <= first, first + count <= N; nothing else of the state is touched.
+ * A NULL handle (checked first), a NULL array, a bad count or range or an index outside [0, N) return EKF_ERR_INVALID
+ * before the device is looked at.  Synchronous, on the handle's stream. */
+#define EKF_DENSE64_READ_MAX 65536
+ekf_status ekf_dense64_get_sigma_block(ekf_dense64_handle h, int nr, const int* rows, int nc, const int* cols,
+                                       double* out /* nr x nc */);
+ekf_status ekf_dense64_get_state_block(ekf_dense64_handle h, int first, int count, double* out);
+ekf_status ekf_dense64_set_state_block(ekf_dense64_handle h, int first, int count, const double* x);
+
 /* ---- laser-scan front end: rigid2d::CircleFitting, batched ----------
  * std::vector<Vector2D> approxCirclePositions(std::vector<double> ranges)
  *                                          circle_fitting.hpp:27, circle_fitting.cpp:298-304
