@@ -380,7 +380,12 @@ class EKF_SLAM:
         return f.value
 
     def set_forms(self, forms=FORMS_DEFAULT):
-        """which launch structures may be taken (FORM_* bits; test / measurement hook, results do not depend on it)"""
+        """which launch structures may be taken (FORM_* bits; test / measurement hook).  Most forms are exact: the same
+        operations in the same order, bit-identical results.  Two things move results at ROUNDING level (1e-10-class, inside
+        the 1e-9 contract): FORM_CURRENT_COLUMNS (on by default: the kept rows / columns carry their rounding from launch
+        to launch instead of being rebuilt from all pending factors), and whatever moves a delayed flush -- the forms that
+        decide how many corrections a launch appends (FORM_DELAYED_PAIR), run boundaries, getters in mid-run -- because the
+        delayed mode's reconstruction and flush contract their multiply-adds over what is pending"""
         _check(self._lib.ekf_set_forms(self._h, int(forms)))
 
     def _form(self, bit, enable):
@@ -557,7 +562,12 @@ class BatchEKF:
         return f.value
 
     def set_forms(self, forms=FORMS_DEFAULT):
-        """which launch structures may be taken (FORM_* bits; test / measurement hook, results do not depend on it)"""
+        """which launch structures may be taken (FORM_* bits; test / measurement hook).  Most forms are exact: the same
+        operations in the same order, bit-identical results.  Two things move results at ROUNDING level (1e-10-class, inside
+        the 1e-9 contract): FORM_CURRENT_COLUMNS (on by default: the kept rows / columns carry their rounding from launch
+        to launch instead of being rebuilt from all pending factors), and whatever moves a delayed flush -- the forms that
+        decide how many corrections a launch appends (FORM_DELAYED_PAIR), run boundaries, getters in mid-run -- because the
+        delayed mode's reconstruction and flush contract their multiply-adds over what is pending"""
         _check(self._lib.ekf_batch_set_forms(self._h, int(forms)))
 
     def _form(self, bit, enable):
