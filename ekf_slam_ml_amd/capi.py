@@ -45,6 +45,7 @@ SYMBOLS = [
     "ekf_dense64_launch_info", "ekf_dense64_tile_map",
     "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
+    "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
     "ekf_dense64_init_block", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -205,6 +206,9 @@ def load():
         "ekf_dense64_propagate_block": [h, C.c_int, C.c_int, _dp, _dp, _dp, _dp],
         "ekf_dense64_correct_sparse": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_score_sparse": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
+        "ekf_dense64_correct_sparse_deferred": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
+        "ekf_dense64_flush": [h, _dp],
+        "ekf_dense64_pending": [h, _ip],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
         "ekf_dense64_get_state_block": [h, C.c_int, C.c_int, _dp],
@@ -742,6 +746,7 @@ class DensePropagator64:
     MAX_S = 64   # EKF_DENSE64_MAX_S
     SCORE_SPARSE_MAX_ROWS = 65536   # EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
     READ_MAX = 65536   # EKF_DENSE64_READ_MAX
+    PENDING_MAX_ROWS = 64   # EKF_DENSE64_PENDING_MAX_ROWS
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -896,6 +901,30 @@ class DensePropagator64:
         (state untouched).  The panels are gathered from s rows and s columns of Sigma instead of a pass over it; every
         dot product has exactly s terms in ascending k.  Returns (nis or None, elapsed_ms); a singular or non-finite S
         raises EkfError (EKF_ERR_STATE) and leaves state and Sigma as they were."""
+        return self._correct_sparse("ekf_dense64_correct_sparse", cols, Hc, R, nu)
+
+    def correct_sparse_deferred(self, cols, Hc, R, nu=None):
+        """correct_sparse() without the pass over Sigma: the same arguments, checks and results (state and nis at once,
+        against the current covariance), but K and T (m rows each) are appended to the handle's pending rows instead of
+        being applied.  score_sparse() and further deferred corrections read through the pending rows; flush(), or any
+        other call that touches Sigma, applies them all in one pass.  With pending + m > PENDING_MAX_ROWS it flushes
+        first.  A singular or non-finite S raises EkfError (EKF_ERR_STATE) and leaves state, Sigma and the pending rows."""
+        return self._correct_sparse("ekf_dense64_correct_sparse_deferred", cols, Hc, R, nu)
+
+    def flush(self):
+        """apply the pending rows to Sigma (one rank-`pending` update); a no-op with nothing pending.  Returns elapsed_ms"""
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_flush(self._h, C.byref(ms)))
+        return ms.value
+
+    @property
+    def pending(self):
+        """rows of K / T that deferred corrections have left for the flush, 0 .. PENDING_MAX_ROWS"""
+        rows = C.c_int()
+        _check(self._lib.ekf_dense64_pending(self._h, C.byref(rows)))
+        return rows.value
+
+    def _correct_sparse(self, entry, cols, Hc, R, nu):
         cols = self._index_lists(cols, 1)
         s = cols.shape[0]
         Hc = np.ascontiguousarray(Hc, dtype=np.float64)
@@ -913,8 +942,8 @@ class DensePropagator64:
             nis = C.c_double()
             pnu, pnis = nu.ctypes.data_as(_dp), C.byref(nis)
         ms = C.c_double()
-        _check(self._lib.ekf_dense64_correct_sparse(self._h, m, s, cols.ctypes.data_as(_ip), Hc.ctypes.data_as(_dp),
-                                                    R.ctypes.data_as(_dp), pnu, pnis, C.byref(ms)))
+        _check(getattr(self._lib, entry)(self._h, m, s, cols.ctypes.data_as(_ip), Hc.ctypes.data_as(_dp), R.ctypes.data_as(_dp), pnu, pnis,
+                    C.byref(ms)))
         return (nis.value if nis is not None else None), ms.value
 
     def score_sparse(self, cols, Hc, R, nu=None, want_S=False):

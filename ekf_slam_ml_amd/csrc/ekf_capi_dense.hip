@@ -4,7 +4,8 @@
 // general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip),
 // the block-structured prediction (ekf_dense64_block.hip), the update and scoring for a Jacobian given by its non-zero
 // columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states and the block readout
-// (ekf_dense64_init.hip).
+// (ekf_dense64_init.hip), and the deferred form of the sparse update (ekf_dense64_deferred.hip): pending rows of K and T
+// that the sparse calls read through and every other call that touches Sigma applies first (flush_pending).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -40,6 +41,9 @@ struct ekf_dense64_s : DenseHandle<double> {
     // (re)initialisation of a block (ekf_dense64_init_block) and the block readout (ekf_dense64_get_sigma_block)
     double* ini_in = nullptr;    // G [64 * 64] | W [64 * 64] | xb [64] | cols (ints) [64]
     double* rd_buf = nullptr;    // out [65536] | rows (ints) [65536] | cols (ints) [65536]
+    // deferred sparse corrections (ekf_dense64_correct_sparse_deferred): nothing until the first call
+    double* pend = nullptr;      // K^T [64][ld] | T [64][ld] | a word kept at zero (the flush's verdict argument)
+    int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
 };
 
 namespace {
@@ -71,6 +75,21 @@ constexpr size_t kIniW = (size_t)kMaxR * ekf::kDense64MaxS, kIniXb = kIniW + (si
 constexpr int kReadMax = ekf::kDense64ReadMax;
 constexpr size_t kRdRows = kReadMax, kRdCols = kRdRows + kReadMax / 2, kRdBuf = kRdCols + kReadMax / 2;
 inline size_t corr_in_doubles(int ld) { return (size_t)2 * kMaxM * ld + kMaxM * kMaxM + kMaxM; }
+constexpr int kMaxP = ekf::kDense64PendingMaxRows;
+inline size_t pend_T(int ld) { return (size_t)kMaxP * ld; }
+inline size_t pend_zero(int ld) { return 2 * pend_T(ld); }
+
+// Sigma <- Sigma_cur: one launch on the handle's stream when rows are pending, nothing otherwise.  Called by every entry
+// point that reads or writes Sigma in memory, after its argument checks and inside its timed region.
+template <class H>
+void flush_pending(H* d) {
+    if constexpr (std::is_same<H, ekf_dense64_s>::value) {
+        if (d->pend_rows == 0) return;
+        ekf::launch_dense64_flush(ekf::dense64_correct_plan(d->N, d->ld), d->S, d->pend, d->pend + pend_T(d->ld),
+                                  d->pend_rows, reinterpret_cast<const int*>(d->pend + pend_zero(d->ld)), d->stream);
+        d->pend_rows = 0;
+    }
+}
 
 template <class H>
 ekf_status dense_destroy(H* d) {
@@ -81,7 +100,7 @@ ekf_status dense_destroy(H* d) {
         if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
         for (double* p : {d->x, d->corr_in, d->corr_out, d->ws_own, d->sc_small, d->sc_H, d->sc_ws, d->blk_in, d->ini_in,
-                          d->rd_buf})
+                          d->rd_buf, d->pend})
             if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
         if (d->sps) (void)hipFree(d->sps);
@@ -133,6 +152,7 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
             HIPC(ekf::dense64_block_prepare());
             HIPC(hipMalloc((void**)&d->blk_in, sizeof(double) * kBlkIn));
             HIPC(ekf::dense64_sparse_prepare());
+            HIPC(ekf::dense64_deferred_prepare());
             HIPC(ekf::dense64_init_prepare());
             HIPC(hipMalloc((void**)&d->ini_in, sizeof(double) * kIniIn));
             HIPC(hipMalloc((void**)&d->rd_buf, sizeof(double) * kRdBuf));
@@ -161,6 +181,8 @@ ekf_status dense_set(H* d, const E* F, const E* Sigma, const E* Q) {
     for (int i = 0; i < 3; i++)
         if (src[i]) HIPC(hipMemcpy2DAsync(dst[i], pitch, src[i], w, w, d->N, hipMemcpyHostToDevice, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
+    if constexpr (std::is_same<H, ekf_dense64_s>::value)
+        if (Sigma) d->pend_rows = 0;   // the pending rows belonged to the covariance that was replaced
     return EKF_OK;
 }
 
@@ -169,6 +191,7 @@ ekf_status dense_propagate(const char* name, H* d, int iterations, double* elaps
     if (!d || iterations < 0) return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
     HIPC(hipSetDevice(d->device));
     HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
     for (int it = 0; it < iterations; it++) {
         Ops::gemm(d->F, d->S, d->T, nullptr, d->ld, false, d->stream, d->N);  // T = At*sigma (:102)
         Ops::gemm(d->T, d->F, d->S, d->Q, d->ld, true, d->stream, d->N);      // sigma = T*At.t() + Q
@@ -203,6 +226,7 @@ template <class H, class E>
 ekf_status dense_get_sigma(H* d, E* out) {
     if (!d || !out) return fail(EKF_ERR_INVALID, "null argument");
     HIPC(hipSetDevice(d->device));
+    flush_pending(d);
     const size_t w = sizeof(E) * d->N, pitch = sizeof(E) * d->ld;
     HIPC(hipMemcpy2DAsync(out, w, d->S, pitch, w, d->N, hipMemcpyDeviceToHost, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
@@ -235,6 +259,7 @@ ekf_status dense64_correct(ekf_dense64_s* d, int m, const double* H, const doubl
     const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
     double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
     HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
     ekf::launch_dense64_correct(pl, d->S, d->x, ws, d->corr_in, d->corr_in + oHt, d->corr_in + oR,
                                 nu ? d->corr_in + oNu : nullptr, m, d->corr_out, reinterpret_cast<int*>(d->corr_out + 1),
                                 d->stream);
@@ -327,6 +352,7 @@ ekf_status dense64_score(ekf_dense64_s* d, int J, int m, const double* H, const 
     double* ws = sp.spart_doubles > (size_t)ld * ld ? d->sc_ws : d->T;
     int* flags = reinterpret_cast<int*>(sm + kScFlag);
     HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
     ekf::launch_dense64_score(sp, d->S, d->sc_H, ws, sm + kScR, r_shared ? 1 : 0, nu ? sm + kScNu : nullptr, J, m,
                               nis_out ? sm + kScNis : nullptr, sm + kScS, flags, d->stream);
     HIPC(hipEventRecord(d->e1, d->stream));
@@ -355,6 +381,7 @@ ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const dou
     if (Qr) HIPC(hipMemcpyAsync(d->blk_in + kBlkQ, Qr, rr, hipMemcpyHostToDevice, d->stream));
     if (dx) HIPC(hipMemcpyAsync(d->blk_in + kBlkDx, dx, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
     ekf::launch_dense64_block(d->S, d->x, d->blk_in, Qr ? d->blk_in + kBlkQ : nullptr, dx ? d->blk_in + kBlkDx : nullptr,
                               d->N, d->ld, first, r, d->stream);
     HIPC(hipEventRecord(d->e1, d->stream));
@@ -403,6 +430,7 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, int m, int s, const int* col
     const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
     double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
     HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
     ekf::launch_dense64_correct_sparse(pl, d->S, d->x, ws, reinterpret_cast<const int*>(d->corr_in + oCols), d->corr_in,
                                        d->corr_in + oR, nu ? d->corr_in + oNu : nullptr, m, s, d->corr_out,
                                        reinterpret_cast<int*>(d->corr_out + 1), d->stream);
@@ -422,6 +450,84 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, int m, int s, const int* col
         return fail(EKF_ERR_STATE, "ekf_dense64_correct_sparse: H Sigma H^T + R is singular or not finite (zero or "
                                    "non-finite pivot); state and Sigma are unchanged");
     if (nis_out) *nis_out = out[0];
+    return EKF_OK;
+}
+
+// The deferred form of the sparse correction: the same uploads, three launches (no pass over Sigma), the same single
+// synchronisation; K and T stay in the pending panels, which the first call allocates (into a local: the members change only
+// when everything succeeded).
+ekf_status dense64_correct_sparse_deferred(ekf_dense64_s* d, int m, int s, const int* cols, const double* Hc,
+                                           const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse_deferred: null handle");
+    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse_deferred: bad argument");
+    if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse_deferred: cols must hold distinct indices in [0, N)");
+    HIPC(hipSetDevice(d->device));
+    const int N = d->N, ld = d->ld;
+    if (!d->pend) {
+        const size_t bytes = sizeof(double) * (pend_zero(ld) + 2);
+        double* fresh = nullptr;
+        hipError_t e = hipMalloc((void**)&fresh, bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(fresh, 0, bytes, d->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(d->stream);
+            if (fresh) (void)hipFree(fresh);
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                        std::string("ekf_dense64_correct_sparse_deferred: ") + hipGetErrorString(e) +
+                            " while reserving the pending panels");
+        }
+        d->pend = fresh;
+    }
+    const size_t oCols = (size_t)kMaxM * kMaxS, oR = (size_t)2 * kMaxM * ld, oNu = oR + kMaxM * kMaxM;   // (64 ld >= 8192)
+    HIPC(hipMemcpyAsync(d->corr_in, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(d->corr_in + oCols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(d->corr_in + oR, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(d->corr_in + oNu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
+    const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
+    double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
+    HIPC(hipEventRecord(d->e0, d->stream));
+    if (d->pend_rows + m > kMaxP) flush_pending(d);   // no room for m more rows
+    ekf::launch_dense64_correct_deferred(pl, d->S, d->x, ws, d->pend, d->pend + pend_T(ld), d->pend_rows,
+                                         reinterpret_cast<const int*>(d->corr_in + oCols), d->corr_in, d->corr_in + oR,
+                                         nu ? d->corr_in + oNu : nullptr, m, s, d->corr_out,
+                                         reinterpret_cast<int*>(d->corr_out + 1), d->stream);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    double out[2] = {0.0, 0.0};
+    HIPC(hipMemcpyAsync(out, d->corr_out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    int verdict = 0;
+    std::memcpy(&verdict, &out[1], sizeof(int));
+    if (verdict != 0)
+        return fail(EKF_ERR_STATE, "ekf_dense64_correct_sparse_deferred: H Sigma H^T + R is singular or not finite (zero "
+                                   "or non-finite pivot); state, Sigma and the pending rows are unchanged");
+    d->pend_rows += m;
+    if (nis_out) *nis_out = out[0];
+    return EKF_OK;
+}
+
+ekf_status dense64_flush(ekf_dense64_s* d, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_flush: null handle");
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (d->pend_rows == 0) return EKF_OK;
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
     return EKF_OK;
 }
 
@@ -466,8 +572,13 @@ ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int
     if (nu) HIPC(hipMemcpyAsync(dNu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
     HIPC(hipMemcpyAsync(dCols, cols, sizeof(int) * J * s, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    ekf::launch_dense64_score_sparse(d->S, dCols, dHc, dR, r_shared ? 1 : 0, nu ? dNu : nullptr, J, m, s, d->ld,
-                                     nis_out ? dNis : nullptr, dS, dFlag, nullptr, d->stream);
+    if (d->pend_rows == 0)
+        ekf::launch_dense64_score_sparse(d->S, dCols, dHc, dR, r_shared ? 1 : 0, nu ? dNu : nullptr, J, m, s, d->ld,
+                                         nis_out ? dNis : nullptr, dS, dFlag, nullptr, d->stream);
+    else   // against Sigma_cur: read through the pending rows
+        ekf::launch_dense64_score_deferred(d->S, d->pend, d->pend + pend_T(d->ld), d->pend_rows, dCols, dHc, dR,
+                                           r_shared ? 1 : 0, nu ? dNu : nullptr, J, m, s, d->ld, nis_out ? dNis : nullptr,
+                                           dS, dFlag, nullptr, d->stream);
     HIPC(hipEventRecord(d->e1, d->stream));
     HIPC(hipGetLastError());
     if (nis_out) HIPC(hipMemcpyAsync(nis_out, dNis, sizeof(double) * J, hipMemcpyDeviceToHost, d->stream));
@@ -509,6 +620,7 @@ ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const i
     if (W) HIPC(hipMemcpyAsync(in + kIniW, W, sizeof(double) * r * r, hipMemcpyHostToDevice, d->stream));
     if (xb) HIPC(hipMemcpyAsync(in + kIniXb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
     ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->N, d->ld,
                              first, r, s, d->stream);
     HIPC(hipEventRecord(d->e1, d->stream));
@@ -537,6 +649,7 @@ ekf_status dense64_get_sigma_block(ekf_dense64_s* d, int nr, const int* rows, in
     int *drows = reinterpret_cast<int*>(d->rd_buf + kRdRows), *dcols = reinterpret_cast<int*>(d->rd_buf + kRdCols);
     HIPC(hipMemcpyAsync(drows, rows, sizeof(int) * nr, hipMemcpyHostToDevice, d->stream));
     HIPC(hipMemcpyAsync(dcols, cols, sizeof(int) * nc, hipMemcpyHostToDevice, d->stream));
+    flush_pending(d);
     ekf::launch_dense64_read_block(d->S, drows, dcols, d->rd_buf, nr, nc, d->ld, d->stream);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out, d->rd_buf, sizeof(double) * nr * nc, hipMemcpyDeviceToHost, d->stream));
@@ -619,6 +732,16 @@ ekf_status ekf_dense64_propagate_block(ekf_dense64_handle d, int first, int r, c
 ekf_status ekf_dense64_correct_sparse(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
                                       const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
     return dense64_correct_sparse(d, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+}
+ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
+                                               const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    return dense64_correct_sparse_deferred(d, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+}
+ekf_status ekf_dense64_flush(ekf_dense64_handle d, double* elapsed_ms) { return dense64_flush(d, elapsed_ms); }
+ekf_status ekf_dense64_pending(ekf_dense64_handle d, int* rows) {
+    if (!d || !rows) return fail(EKF_ERR_INVALID, "ekf_dense64_pending: null argument");
+    *rows = d->pend_rows;
+    return EKF_OK;
 }
 ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, const int* cols, const double* Hc,
                                     const double* R, int r_shared, const double* nu, double* nis_out, double* S_out,

@@ -101,6 +101,29 @@ void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, 
                                    const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
                                    double* nis, int* verdict, hipStream_t st);
 
+// ---- fp64 deferred sparse corrections (ekf_dense64_deferred.hip): p <= 64 pending rows of two panels [64][ld],
+// Kp[q][i] = K[i][q] and Tq[q][j] = T[q][j], stand for Sigma_cur = Sigma - sum_{q < p} Kp[q]^T Tq[q]; the correction and the
+// scoring read through them, x = fma(-Kp[q][row], Tq[q][col], x) in ascending q before the dot products of the sparse
+// calls, and Sigma is rewritten once per flush.
+constexpr int kDense64PendingMaxRows = 64;   // EKF_DENSE64_PENDING_MAX_ROWS
+hipError_t dense64_deferred_prepare();   // raises the dynamic-LDS limits (gather 128.8 KiB, scoring up to 114.8 KiB)
+// launch_dense64_score_sparse against Sigma_cur: the same arguments plus the pending panels and their row count p >= 0.
+void launch_dense64_score_deferred(const double* Sigma, const double* Kp, const double* Tq, int p, const int* cols,
+                                   const double* Hc, const double* R, int r_shared, const double* nu, int J, int m, int s,
+                                   int ld, double* nis, double* S_out, int* flag, double* Sinv, hipStream_t st);
+// Launch 5 of launch_dense64_correct (k_dc_gain) on U^T and S^-1 in ws, K^T written to Kt [m][ld] instead of ws.
+void launch_dense64_gain(const Dense64CorrectPlan& pl, const double* ws, double* Kt, double* state, const double* nu, int m,
+                         const int* verdict, hipStream_t s);
+// The three launches of one deferred sparse correction, p + m <= 64: the gather through the pending rows (T into rows
+// p .. p + m - 1 of Tq, U^T into ws), the scoring kernel with J = 1 (S^-1 into ws, the verdict word, nis), the gain (K^T
+// into rows p .. p + m - 1 of Kp, state += K nu).  Sigma is not written; a set verdict leaves rows q < p and the state.
+void launch_dense64_correct_deferred(const Dense64CorrectPlan& pl, const double* Sigma, double* state, double* ws,
+                                     double* Kp, double* Tq, int p, const int* cols, const double* Hc, const double* R,
+                                     const double* nu, int m, int s, double* nis, int* verdict, hipStream_t st);
+// Launch 6 of launch_dense64_correct (k_dc_update) at rank p on the pending panels; zero: a device word that holds 0.
+void launch_dense64_flush(const Dense64CorrectPlan& pl, double* Sigma, const double* Kp, const double* Tq, int p,
+                          const int* zero, hipStream_t s);
+
 // ---- fp64 (re)initialisation of a block of states (ekf_dense64_init.hip) on the same Sigma and state: the block
 // b = [first, first + r) becomes a function of the s listed states with Jacobian G (r x s): F = identity with F[b, b] = 0
 // and F[b, cols] = G, Q = zero with W in the block's square.  One launch of 1 + 2 ceil(N / 64) workgroups (the corner, the

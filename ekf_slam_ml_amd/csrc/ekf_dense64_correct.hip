@@ -457,4 +457,20 @@ void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, do
                        pl.upd_blocks_per_chunk);
 }
 
+// Launch 5 alone, with K^T written to `Kt` instead of the workspace panel (ekf_dense64_deferred.hip: a pending row).
+void launch_dense64_gain(const Dense64CorrectPlan& pl, const double* ws, double* Kt, double* state, const double* nu, int m,
+                         const int* verdict, hipStream_t s) {
+    hipLaunchKernelGGL(k_dc_gain, dim3((pl.N + kGainRows - 1) / kGainRows), dim3(256), 0, s, ws + pl.off_Ut,
+                       ws + pl.off_Sinv, nu, Kt, state, verdict, pl.N, pl.ld, m);
+}
+
+// Launch 6 alone on the pending panels of p deferred rows: Sigma <- Sigma - sum_q Kp[q]^T Tq[q].  `zero`: a device word
+// that holds 0 (the kernel's verdict argument).
+void launch_dense64_flush(const Dense64CorrectPlan& pl, double* Sigma, const double* Kp, const double* Tq, int p,
+                          const int* zero, hipStream_t s) {
+    hipLaunchKernelGGL(k_dc_update, dim3(pl.upd_strips, pl.upd_chunks), dim3(256),
+                       sizeof(double) * (size_t)((p + 3) & ~3) * kUpdCols, s, Sigma, Kp, Tq, zero, pl.N, pl.ld, p,
+                       pl.upd_blocks_per_chunk);
+}
+
 }  // namespace ekf

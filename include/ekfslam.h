@@ -585,6 +585,44 @@ ekf_status ekf_dense64_score_sparse(ekf_dense64_handle h, int J, int m, int s,
                                     const double* R, int r_shared, const double* nu,
                                     double* nis_out, double* S_out, int* flag_out, double* elapsed_ms);
 
+/* Deferred sparse corrections: one pass over Sigma per tick instead of one per reading.  ekf_dense64_correct_sparse ends in
+ * the rank-m update Sigma <- Sigma - K T, which rewrites all of Sigma (16 N^2 bytes); a tick with V readings streams Sigma
+ * V times.  The deferred form keeps the factors instead: the handle holds p <= EKF_DENSE64_PENDING_MAX_ROWS pending rows of
+ * K and of T, the current covariance is
+ *   Sigma_cur = Sigma_base - sum_{q < p} K^T[q] T[q]        (Sigma_base: what is in memory; never symmetrised)
+ * and Sigma_base is rewritten once, by the flush (one launch of the rank-m update at rank p).  Nothing is approximated:
+ * the deferred sequence is the eager one up to the rounding of another order of summation.
+ * ekf_dense64_correct_sparse_deferred: the arguments, the argument checks (in the same order), the verdict rule and the
+ *   one synchronisation of ekf_dense64_correct_sparse, and its results for Sigma_cur: S, nis, K, state += K nu at once
+ *   (get_state* / set_state* are never stale and never flush).  Sigma in memory is not written; K (m rows) and
+ *   T = Hc Sigma_cur[cols, :] (m rows) are appended to the pending panels.  With p + m > 64 it flushes first.  A singular
+ *   or non-finite S returns EKF_ERR_STATE and leaves the state, Sigma and the pending rows bit for bit and their count as
+ *   it was (a flush the call had to make first stands: it changes the representation, not Sigma_cur).
+ * ekf_dense64_score_sparse with rows pending scores against Sigma_cur (with none it launches what it always did).
+ * Every other entry point that reads or writes Sigma -- propagate, propagate_block, correct, score, correct_sparse,
+ *   init_block, get_sigma, get_sigma_block -- flushes first when rows are pending, after its own argument checks (a
+ *   refused call changes nothing, the pending rows included) and inside its elapsed_ms; with nothing pending none of them
+ *   does anything new.  ekf_dense64_set with a Sigma drops the pending rows (they belonged to the covariance it replaces),
+ *   with F or Q alone it leaves them; destroy drops them.
+ * ekf_dense64_flush: Sigma_base <- Sigma_cur now; with nothing pending a no-op that reports 0 ms without looking at the
+ *   device.  ekf_dense64_pending: the rows waiting, 0 .. 64.
+ * ORDER OF ARITHMETIC (part of the contract): wherever the sparse calls read an entry of Sigma, the deferred ones read
+ *   x = Sigma_base[i][j];  x = fma(-K^T[q][i], T[q][j], x)  for q = 0, 1, .. p - 1
+ * one fused multiply-add per pending row in ascending q, and then run the sparse calls' own dot products on x.  No
+ * floating-point atomics.  So S, nis and flag of a candidate are the same bits alone or at any position of any batch, in
+ * score_sparse and in the deferred correction that follows with the same operands, and from run to run, with rows pending
+ * too.  The flush sums its p terms in the order of v_mfma_f64_16x16x4_f64, so a deferred sequence agrees with the eager one
+ * to rounding, not in bits -- except that with nothing pending ONE deferred correction followed by the flush runs the
+ * arithmetic of ekf_dense64_correct_sparse on the same operands and is bit-identical to it (state, Sigma, nis).
+ * Memory: the pending panels, 2 * 64 * ld doubles (10.4 MB at N = 10003), are allocated by the first deferred call; a
+ * failure there returns EKF_ERR_NOMEM and leaves the handle as it was.  elapsed_ms (nullable) = HIP-event time of the
+ * launches only. */
+#define EKF_DENSE64_PENDING_MAX_ROWS 64
+ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle h, int m, int s, const int* cols, const double* Hc,
+                                               const double* R, const double* nu, double* nis_out, double* elapsed_ms);
+ekf_status ekf_dense64_flush(ekf_dense64_handle h, double* elapsed_ms);    /* no-op, 0 ms, with nothing pending */
+ekf_status ekf_dense64_pending(ekf_dense64_handle h, int* rows);           /* rows of K / T waiting, 0 .. 64 */
+
 /* (Re)initialisation of a block of states: what a map that grows, or a fixed-capacity map that recycles a slot, does to
  * Sigma.  The states b = [first, first + r) are replaced by a new variable y = g(x[cols], z) of s other states and a
  * reading z: G (r x s) is the Jacobian of g with respect to x[cols], W the caller's Gz R Gz^T, xb the value g(..).  The
