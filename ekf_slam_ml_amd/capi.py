@@ -46,6 +46,7 @@ SYMBOLS = [
     "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
+    "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_init_block", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -209,6 +210,8 @@ def load():
         "ekf_dense64_correct_sparse_deferred": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_flush": [h, _dp],
         "ekf_dense64_pending": [h, _ip],
+        "ekf_dense64_set_carry": [h, C.c_int],
+        "ekf_dense64_get_carry": [h, _ip],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
         "ekf_dense64_get_state_block": [h, C.c_int, C.c_int, _dp],
@@ -923,6 +926,19 @@ class DensePropagator64:
         rows = C.c_int()
         _check(self._lib.ekf_dense64_pending(self._h, C.byref(rows)))
         return rows.value
+
+    @property
+    def carry(self):
+        """True: propagate_block(), init_block() and sigma_block() leave the pending rows pending (the two updates map
+        them, the readout reads through them) and the caller chooses when to flush(); False (the default): they flush
+        first.  Setting it touches nothing; it decides what the next calls do."""
+        on = C.c_int()
+        _check(self._lib.ekf_dense64_get_carry(self._h, C.byref(on)))
+        return bool(on.value)
+
+    @carry.setter
+    def carry(self, on):
+        _check(self._lib.ekf_dense64_set_carry(self._h, 1 if on else 0))
 
     def _correct_sparse(self, entry, cols, Hc, R, nu):
         cols = self._index_lists(cols, 1)

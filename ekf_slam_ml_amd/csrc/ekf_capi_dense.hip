@@ -5,7 +5,8 @@
 // the block-structured prediction (ekf_dense64_block.hip), the update and scoring for a Jacobian given by its non-zero
 // columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states and the block readout
 // (ekf_dense64_init.hip), and the deferred form of the sparse update (ekf_dense64_deferred.hip): pending rows of K and T
-// that the sparse calls read through and every other call that touches Sigma applies first (flush_pending).
+// that the sparse calls read through and every other call that touches Sigma applies first (flush_pending) -- unless the
+// caller lets propagate_block, init_block and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -44,6 +45,7 @@ struct ekf_dense64_s : DenseHandle<double> {
     // deferred sparse corrections (ekf_dense64_correct_sparse_deferred): nothing until the first call
     double* pend = nullptr;      // K^T [64][ld] | T [64][ld] | a word kept at zero (the flush's verdict argument)
     int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
+    int carry = 0;               // ekf_dense64_set_carry: propagate_block, init_block, get_sigma_block do not flush
 };
 
 namespace {
@@ -89,6 +91,16 @@ void flush_pending(H* d) {
                                   d->pend_rows, reinterpret_cast<const int*>(d->pend + pend_zero(d->ld)), d->stream);
         d->pend_rows = 0;
     }
+}
+
+// The pending rows through a congruence with A = identity except rows [first, first + r) (ekf_dense64_carry.hip): mapped
+// when the handle carries them, applied to Sigma otherwise.  M, src: the operands the entry point has already sent up.
+void carry_or_flush(ekf_dense64_s* d, const double* M, const int* src, int first, int r, int s) {
+    if (d->carry && d->pend_rows > 0)
+        ekf::launch_dense64_panel_map(d->pend, d->pend + pend_T(d->ld), d->pend_rows, M, src, d->ld, first, r, s,
+                                      d->stream);
+    else
+        flush_pending(d);
 }
 
 template <class H>
@@ -381,7 +393,7 @@ ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const dou
     if (Qr) HIPC(hipMemcpyAsync(d->blk_in + kBlkQ, Qr, rr, hipMemcpyHostToDevice, d->stream));
     if (dx) HIPC(hipMemcpyAsync(d->blk_in + kBlkDx, dx, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    flush_pending(d);
+    carry_or_flush(d, d->blk_in, nullptr, first, r, r);
     ekf::launch_dense64_block(d->S, d->x, d->blk_in, Qr ? d->blk_in + kBlkQ : nullptr, dx ? d->blk_in + kBlkDx : nullptr,
                               d->N, d->ld, first, r, d->stream);
     HIPC(hipEventRecord(d->e1, d->stream));
@@ -620,7 +632,7 @@ ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const i
     if (W) HIPC(hipMemcpyAsync(in + kIniW, W, sizeof(double) * r * r, hipMemcpyHostToDevice, d->stream));
     if (xb) HIPC(hipMemcpyAsync(in + kIniXb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    flush_pending(d);
+    carry_or_flush(d, in, s > 0 ? dcols : nullptr, first, r, s);
     ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->N, d->ld,
                              first, r, s, d->stream);
     HIPC(hipEventRecord(d->e1, d->stream));
@@ -649,8 +661,13 @@ ekf_status dense64_get_sigma_block(ekf_dense64_s* d, int nr, const int* rows, in
     int *drows = reinterpret_cast<int*>(d->rd_buf + kRdRows), *dcols = reinterpret_cast<int*>(d->rd_buf + kRdCols);
     HIPC(hipMemcpyAsync(drows, rows, sizeof(int) * nr, hipMemcpyHostToDevice, d->stream));
     HIPC(hipMemcpyAsync(dcols, cols, sizeof(int) * nc, hipMemcpyHostToDevice, d->stream));
-    flush_pending(d);
-    ekf::launch_dense64_read_block(d->S, drows, dcols, d->rd_buf, nr, nc, d->ld, d->stream);
+    if (d->carry && d->pend_rows > 0) {   // Sigma_cur through the pending rows; read-only
+        ekf::launch_dense64_read_block_deferred(d->S, d->pend, d->pend + pend_T(d->ld), d->pend_rows, drows, dcols,
+                                                d->rd_buf, nr, nc, d->ld, d->stream);
+    } else {
+        flush_pending(d);
+        ekf::launch_dense64_read_block(d->S, drows, dcols, d->rd_buf, nr, nc, d->ld, d->stream);
+    }
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out, d->rd_buf, sizeof(double) * nr * nc, hipMemcpyDeviceToHost, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
@@ -741,6 +758,16 @@ ekf_status ekf_dense64_flush(ekf_dense64_handle d, double* elapsed_ms) { return 
 ekf_status ekf_dense64_pending(ekf_dense64_handle d, int* rows) {
     if (!d || !rows) return fail(EKF_ERR_INVALID, "ekf_dense64_pending: null argument");
     *rows = d->pend_rows;
+    return EKF_OK;
+}
+ekf_status ekf_dense64_set_carry(ekf_dense64_handle d, int on) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_set_carry: null handle");
+    d->carry = on ? 1 : 0;
+    return EKF_OK;
+}
+ekf_status ekf_dense64_get_carry(ekf_dense64_handle d, int* on) {
+    if (!d || !on) return fail(EKF_ERR_INVALID, "ekf_dense64_get_carry: null argument");
+    *on = d->carry;
     return EKF_OK;
 }
 ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, const int* cols, const double* Hc,

@@ -139,4 +139,15 @@ void launch_dense64_init(double* Sigma, double* state, const int* cols, const do
 // out[a][c] = Sigma[rows[a]][cols[c]], nr * nc <= kDense64ReadMax, every index in [0, N) (not checked here)
 void launch_dense64_read_block(const double* Sigma, const int* rows, const int* cols, double* out, int nr, int nc, int ld,
                                hipStream_t st);
+
+// ---- the pending rows carried through propagate_block, init_block and the block readout (ekf_dense64_carry.hip): those
+// calls are congruences Sigma <- A Sigma A^T + Q with A = identity except rows [first, first + r), so they run on Sigma in
+// memory unchanged while every pending row v of both panels takes v[first + a] <- sum_k M[a][k] v[src[k]] (k ascending
+// from +0, one fma per term).  M: r x s row-major on the device; src: s indices on the device, or NULL for the block itself
+// (then s == r, in place); s = 0 writes +0.  One launch of ceil(2 p / 4) workgroups; nothing at p = 0.
+void launch_dense64_panel_map(double* Kp, double* Tq, int p, const double* M, const int* src, int ld, int first, int r,
+                              int s, hipStream_t st);
+// launch_dense64_read_block against Sigma_cur: x = fma(-Kp[q][rows[a]], Tq[q][cols[c]], x) for q = 0 .. p - 1, p >= 1
+void launch_dense64_read_block_deferred(const double* Sigma, const double* Kp, const double* Tq, int p, const int* rows,
+                                        const int* cols, double* out, int nr, int nc, int ld, hipStream_t st);
 }  // namespace ekf

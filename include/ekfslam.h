@@ -623,6 +623,39 @@ ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle h, int m, int 
 ekf_status ekf_dense64_flush(ekf_dense64_handle h, double* elapsed_ms);    /* no-op, 0 ms, with nothing pending */
 ekf_status ekf_dense64_pending(ekf_dense64_handle h, int* rows);           /* rows of K / T waiting, 0 .. 64 */
 
+/* Carrying the pending rows across ticks: the caller chooses the flush cadence.  With the policy off (the default) every
+ * entry point does exactly what is written above.  With it on and rows pending, the three calls a SLAM tick makes between
+ * its corrections no longer flush:
+ *   ekf_dense64_propagate_block  runs its one launch on Sigma_base with the same arithmetic and the same bits as on a
+ *     handle with nothing pending (Qr goes into Sigma_base alone, the state gets dx as before) and replaces, in every
+ *     pending row q < p of BOTH panels, the entries [first, first + r) by Fr times those entries;
+ *   ekf_dense64_init_block  runs its one launch on Sigma_base and sets, in every pending row of both panels, the entries
+ *     [first, first + r) to G v[cols] (to +0 with s = 0);
+ *   ekf_dense64_get_sigma_block  returns Sigma_cur[rows[a]][cols[c]] and stays read-only.
+ * This is exact algebra, not an approximation: both updates are Sigma <- A Sigma A^T + Q with A the identity except in the
+ * block's r rows, and A Sigma_cur A^T + Q = (A Sigma_base A^T + Q) - sum_q (A K^T[q]) (A T[q]^T)^T.  The extra work is at
+ * most 128 rows * r * s multiply-adds in one small launch; there is no pass over Sigma.
+ * ekf_dense64_correct_sparse_deferred, ekf_dense64_score_sparse, ekf_dense64_flush and ekf_dense64_pending are unchanged;
+ * propagate, correct, score, correct_sparse and get_sigma still flush first; ekf_dense64_set with a Sigma still drops the
+ * rows.  With the policy on and nothing pending the three calls launch exactly what they launch with it off.  A refused
+ * call (bad arguments, checked before the device is looked at, as above) changes nothing, the pending rows included.
+ * ekf_dense64_set_carry never touches Sigma, the state or the pending rows: it only decides what the next calls do, so it
+ * may be switched with rows pending.  on: 0 = off, anything else = on.  A NULL handle or NULL pointer returns
+ * EKF_ERR_INVALID.
+ * ORDER OF ARITHMETIC (part of the contract).  Panel map, for each pending row v of the K panel and of the T panel alike:
+ *   v'[first + a] = sum_k M[a][k] v[src[k]]      M = Fr, src = the block (r terms) / M = G, src = cols (s terms)
+ * accumulated from +0 in ascending k with one fused multiply-add per term, an order that does not depend on N, ld, first,
+ * p or the launch geometry; propagate_block's map is in place, all r source entries of a row being read before any is
+ * written.  Readout: x = Sigma_base[i][j]; x = fma(-K^T[q][i], T[q][j], x) for q = 0, 1, .. p - 1 -- the fold of the
+ * deferred calls above, so ekf_dense64_get_sigma_block(cols, cols) returns bit for bit the s x s block that
+ * ekf_dense64_score_sparse and the next deferred correction work on.  No floating-point atomics: the same bits from run to
+ * run.  The padding of the panels (columns >= N) stays zero.  A carried sequence agrees with the flush-first sequence to
+ * rounding, not in bits; in particular the corner written by ekf_dense64_init_block (computed from Sigma_base, the pending
+ * rows' share of it living in the mapped panels) is bit-equal to the S_out of ekf_dense64_score_sparse taken before the
+ * call only when nothing is pending. */
+ekf_status ekf_dense64_set_carry(ekf_dense64_handle h, int on);
+ekf_status ekf_dense64_get_carry(ekf_dense64_handle h, int* on);
+
 /* (Re)initialisation of a block of states: what a map that grows, or a fixed-capacity map that recycles a slot, does to
  * Sigma.  The states b = [first, first + r) are replaced by a new variable y = g(x[cols], z) of s other states and a
  * reading z: G (r x s) is the Jacobian of g with respect to x[cols], W the caller's Gz R Gz^T, xb the value g(..).  The
