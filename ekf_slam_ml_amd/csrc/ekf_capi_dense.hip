@@ -4,9 +4,10 @@
 // general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip),
 // the block-structured prediction (ekf_dense64_block.hip), the update and scoring for a Jacobian given by its non-zero
 // columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states and the block readout
-// (ekf_dense64_init.hip), and the deferred form of the sparse update (ekf_dense64_deferred.hip): pending rows of K and T
-// that the sparse calls read through and every other call that touches Sigma applies first (flush_pending) -- unless the
-// caller lets propagate_block, init_block and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
+// (ekf_dense64_init.hip), and the deferred form of the sparse update (the second instantiation of ekf_dense64_sparse.hip's
+// kernels): pending rows of K and T that the sparse calls read through and every other call that touches Sigma applies
+// first (flush_pending) -- unless the caller lets propagate_block, init_block and the block readout carry them
+// (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -103,6 +104,37 @@ void carry_or_flush(ekf_dense64_s* d, const double* M, const int* src, int first
         flush_pending(d);
 }
 
+// The end of a timed entry point: e1 behind the launches, the launch error, the copies back to the host (a null dst is
+// skipped), ONE synchronisation, the time between the handle's events.
+struct CopyBack {
+    void* dst;
+    const void* src;
+    size_t bytes;
+};
+template <class H>
+ekf_status finish_timed(H* d, double* elapsed_ms, std::initializer_list<CopyBack> back = {}) {
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    for (const CopyBack& c : back)
+        if (c.dst) HIPC(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    return EKF_OK;
+}
+
+// finish_timed of a correction: corr_out (nis | verdict) comes back in one copy; *verdict: 0 = applied, 1 = S singular.
+ekf_status finish_correction(ekf_dense64_s* d, double* elapsed_ms, double* nis, int* verdict) {
+    double out[2] = {0.0, 0.0};
+    EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
+    *nis = out[0];
+    std::memcpy(verdict, &out[1], sizeof(int));
+    return EKF_OK;
+}
+
 template <class H>
 ekf_status dense_destroy(H* d) {
     if (!d) return EKF_OK;
@@ -164,7 +196,6 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
             HIPC(ekf::dense64_block_prepare());
             HIPC(hipMalloc((void**)&d->blk_in, sizeof(double) * kBlkIn));
             HIPC(ekf::dense64_sparse_prepare());
-            HIPC(ekf::dense64_deferred_prepare());
             HIPC(ekf::dense64_init_prepare());
             HIPC(hipMalloc((void**)&d->ini_in, sizeof(double) * kIniIn));
             HIPC(hipMalloc((void**)&d->rd_buf, sizeof(double) * kRdBuf));
@@ -208,15 +239,7 @@ ekf_status dense_propagate(const char* name, H* d, int iterations, double* elaps
         Ops::gemm(d->F, d->S, d->T, nullptr, d->ld, false, d->stream, d->N);  // T = At*sigma (:102)
         Ops::gemm(d->T, d->F, d->S, d->Q, d->ld, true, d->stream, d->N);      // sigma = T*At.t() + Q
     }
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    return EKF_OK;
+    return finish_timed(d, elapsed_ms);
 }
 
 template <class Ops, class H>
@@ -275,22 +298,13 @@ ekf_status dense64_correct(ekf_dense64_s* d, int m, const double* H, const doubl
     ekf::launch_dense64_correct(pl, d->S, d->x, ws, d->corr_in, d->corr_in + oHt, d->corr_in + oR,
                                 nu ? d->corr_in + oNu : nullptr, m, d->corr_out, reinterpret_cast<int*>(d->corr_out + 1),
                                 d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    double out[2] = {0.0, 0.0};
-    HIPC(hipMemcpyAsync(out, d->corr_out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
+    double nis = 0.0;
     int verdict = 0;
-    std::memcpy(&verdict, &out[1], sizeof(int));
+    EKFC(finish_correction(d, elapsed_ms, &nis, &verdict));
     if (verdict != 0)
         return fail(EKF_ERR_STATE, "ekf_dense64_correct: H Sigma H^T + R is singular or not finite (zero or non-finite "
                                    "pivot); state and Sigma are unchanged");
-    if (nis_out) *nis_out = out[0];
+    if (nis_out) *nis_out = nis;
     return EKF_OK;
 }
 
@@ -367,18 +381,9 @@ ekf_status dense64_score(ekf_dense64_s* d, int J, int m, const double* H, const 
     flush_pending(d);
     ekf::launch_dense64_score(sp, d->S, d->sc_H, ws, sm + kScR, r_shared ? 1 : 0, nu ? sm + kScNu : nullptr, J, m,
                               nis_out ? sm + kScNis : nullptr, sm + kScS, flags, d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    if (nis_out) HIPC(hipMemcpyAsync(nis_out, sm + kScNis, sizeof(double) * J, hipMemcpyDeviceToHost, d->stream));
-    if (S_out) HIPC(hipMemcpyAsync(S_out, sm + kScS, sizeof(double) * J * mm, hipMemcpyDeviceToHost, d->stream));
-    if (flag_out) HIPC(hipMemcpyAsync(flag_out, flags, sizeof(int) * J, hipMemcpyDeviceToHost, d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    return EKF_OK;
+    return finish_timed(d, elapsed_ms, {{nis_out, sm + kScNis, sizeof(double) * J},
+                                        {S_out, sm + kScS, sizeof(double) * J * mm},
+                                        {flag_out, flags, sizeof(int) * J}});
 }
 
 // The block-structured prediction: Fr, Qr and dx go up, one launch, timed by the handle's events.  The stored F and Q of
@@ -396,15 +401,7 @@ ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const dou
     carry_or_flush(d, d->blk_in, nullptr, first, r, r);
     ekf::launch_dense64_block(d->S, d->x, d->blk_in, Qr ? d->blk_in + kBlkQ : nullptr, dx ? d->blk_in + kBlkDx : nullptr,
                               d->N, d->ld, first, r, d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    return EKF_OK;
+    return finish_timed(d, elapsed_ms);
 }
 
 // ---- a Jacobian given by its s non-zero columns ---------------------------------------------------------------------------
@@ -424,60 +421,21 @@ bool index_lists_ok(std::vector<int>& stamp, int N, int rows, int s, const int* 
 }
 
 // One sparse correction: cols, Hc, R, nu go up into the (otherwise unused) operand buffer of the dense correction -- Hc and
-// the list where its H would sit, R and nu in their usual places -- four launches, the verdict and nis come back in one copy.
-ekf_status dense64_correct_sparse(ekf_dense64_s* d, int m, int s, const int* cols, const double* Hc, const double* R,
-                                  const double* nu, double* nis_out, double* elapsed_ms) {
-    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse: null handle");
+// the list where its H would sit, R and nu in their usual places -- the verdict and nis come back in one copy.  Eager: the
+// pending rows are applied first, four launches.  Deferred: three launches (no pass over Sigma) unless the m new rows do not
+// fit; K and T stay in the pending panels, which the first call allocates (into a local: the member changes only when
+// everything succeeded).
+ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s, const int* cols, const double* Hc,
+                                  const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    const std::string fn = deferred ? "ekf_dense64_correct_sparse_deferred" : "ekf_dense64_correct_sparse";
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
     if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N || (nis_out && !nu))
-        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse: bad argument");
+        return fail(EKF_ERR_INVALID, fn + ": bad argument");
     if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
-        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse: cols must hold distinct indices in [0, N)");
+        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N)");
     HIPC(hipSetDevice(d->device));
     const int N = d->N, ld = d->ld;
-    const size_t oCols = (size_t)kMaxM * kMaxS, oR = (size_t)2 * kMaxM * ld, oNu = oR + kMaxM * kMaxM;   // (64 ld >= 8192)
-    HIPC(hipMemcpyAsync(d->corr_in, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipMemcpyAsync(d->corr_in + oCols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipMemcpyAsync(d->corr_in + oR, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
-    if (nu) HIPC(hipMemcpyAsync(d->corr_in + oNu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
-    const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
-    double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
-    HIPC(hipEventRecord(d->e0, d->stream));
-    flush_pending(d);
-    ekf::launch_dense64_correct_sparse(pl, d->S, d->x, ws, reinterpret_cast<const int*>(d->corr_in + oCols), d->corr_in,
-                                       d->corr_in + oR, nu ? d->corr_in + oNu : nullptr, m, s, d->corr_out,
-                                       reinterpret_cast<int*>(d->corr_out + 1), d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    double out[2] = {0.0, 0.0};
-    HIPC(hipMemcpyAsync(out, d->corr_out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    int verdict = 0;
-    std::memcpy(&verdict, &out[1], sizeof(int));
-    if (verdict != 0)
-        return fail(EKF_ERR_STATE, "ekf_dense64_correct_sparse: H Sigma H^T + R is singular or not finite (zero or "
-                                   "non-finite pivot); state and Sigma are unchanged");
-    if (nis_out) *nis_out = out[0];
-    return EKF_OK;
-}
-
-// The deferred form of the sparse correction: the same uploads, three launches (no pass over Sigma), the same single
-// synchronisation; K and T stay in the pending panels, which the first call allocates (into a local: the members change only
-// when everything succeeded).
-ekf_status dense64_correct_sparse_deferred(ekf_dense64_s* d, int m, int s, const int* cols, const double* Hc,
-                                           const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
-    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse_deferred: null handle");
-    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N || (nis_out && !nu))
-        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse_deferred: bad argument");
-    if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
-        return fail(EKF_ERR_INVALID, "ekf_dense64_correct_sparse_deferred: cols must hold distinct indices in [0, N)");
-    HIPC(hipSetDevice(d->device));
-    const int N = d->N, ld = d->ld;
-    if (!d->pend) {
+    if (deferred && !d->pend) {
         const size_t bytes = sizeof(double) * (pend_zero(ld) + 2);
         double* fresh = nullptr;
         hipError_t e = hipMalloc((void**)&fresh, bytes);
@@ -487,8 +445,7 @@ ekf_status dense64_correct_sparse_deferred(ekf_dense64_s* d, int m, int s, const
             if (fresh) (void)hipFree(fresh);
             (void)hipGetLastError();
             return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
-                        std::string("ekf_dense64_correct_sparse_deferred: ") + hipGetErrorString(e) +
-                            " while reserving the pending panels");
+                        fn + ": " + hipGetErrorString(e) + " while reserving the pending panels");
         }
         d->pend = fresh;
     }
@@ -499,29 +456,26 @@ ekf_status dense64_correct_sparse_deferred(ekf_dense64_s* d, int m, int s, const
     if (nu) HIPC(hipMemcpyAsync(d->corr_in + oNu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
     const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
     double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
+    const int* dcols = reinterpret_cast<const int*>(d->corr_in + oCols);
+    const double *dR = d->corr_in + oR, *dnu = nu ? d->corr_in + oNu : nullptr;
+    int* dverdict = reinterpret_cast<int*>(d->corr_out + 1);
     HIPC(hipEventRecord(d->e0, d->stream));
-    if (d->pend_rows + m > kMaxP) flush_pending(d);   // no room for m more rows
-    ekf::launch_dense64_correct_deferred(pl, d->S, d->x, ws, d->pend, d->pend + pend_T(ld), d->pend_rows,
-                                         reinterpret_cast<const int*>(d->corr_in + oCols), d->corr_in, d->corr_in + oR,
-                                         nu ? d->corr_in + oNu : nullptr, m, s, d->corr_out,
-                                         reinterpret_cast<int*>(d->corr_out + 1), d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    double out[2] = {0.0, 0.0};
-    HIPC(hipMemcpyAsync(out, d->corr_out, sizeof(out), hipMemcpyDeviceToHost, d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
+    if (!deferred || d->pend_rows + m > kMaxP) flush_pending(d);   // deferred: only when there is no room for m more rows
+    if (deferred)
+        ekf::launch_dense64_correct_deferred(pl, d->S, d->x, ws, d->pend, d->pend + pend_T(ld), d->pend_rows, dcols,
+                                             d->corr_in, dR, dnu, m, s, d->corr_out, dverdict, d->stream);
+    else
+        ekf::launch_dense64_correct_sparse(pl, d->S, d->x, ws, dcols, d->corr_in, dR, dnu, m, s, d->corr_out, dverdict,
+                                           d->stream);
+    double nis = 0.0;
     int verdict = 0;
-    std::memcpy(&verdict, &out[1], sizeof(int));
+    EKFC(finish_correction(d, elapsed_ms, &nis, &verdict));
     if (verdict != 0)
-        return fail(EKF_ERR_STATE, "ekf_dense64_correct_sparse_deferred: H Sigma H^T + R is singular or not finite (zero "
-                                   "or non-finite pivot); state, Sigma and the pending rows are unchanged");
-    d->pend_rows += m;
-    if (nis_out) *nis_out = out[0];
+        return fail(EKF_ERR_STATE, fn + ": H Sigma H^T + R is singular or not finite (zero or non-finite pivot); " +
+                                       (deferred ? "state, Sigma and the pending rows are unchanged"
+                                                 : "state and Sigma are unchanged"));
+    if (deferred) d->pend_rows += m;
+    if (nis_out) *nis_out = nis;
     return EKF_OK;
 }
 
@@ -532,15 +486,7 @@ ekf_status dense64_flush(ekf_dense64_s* d, double* elapsed_ms) {
     HIPC(hipSetDevice(d->device));
     HIPC(hipEventRecord(d->e0, d->stream));
     flush_pending(d);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    return EKF_OK;
+    return finish_timed(d, elapsed_ms);
 }
 
 // Sparse scoring of J candidates: the operands go up into one buffer (allocated into a local, the members change only when
@@ -584,25 +530,12 @@ ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int
     if (nu) HIPC(hipMemcpyAsync(dNu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
     HIPC(hipMemcpyAsync(dCols, cols, sizeof(int) * J * s, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    if (d->pend_rows == 0)
-        ekf::launch_dense64_score_sparse(d->S, dCols, dHc, dR, r_shared ? 1 : 0, nu ? dNu : nullptr, J, m, s, d->ld,
-                                         nis_out ? dNis : nullptr, dS, dFlag, nullptr, d->stream);
-    else   // against Sigma_cur: read through the pending rows
-        ekf::launch_dense64_score_deferred(d->S, d->pend, d->pend + pend_T(d->ld), d->pend_rows, dCols, dHc, dR,
-                                           r_shared ? 1 : 0, nu ? dNu : nullptr, J, m, s, d->ld, nis_out ? dNis : nullptr,
-                                           dS, dFlag, nullptr, d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    if (nis_out) HIPC(hipMemcpyAsync(nis_out, dNis, sizeof(double) * J, hipMemcpyDeviceToHost, d->stream));
-    if (S_out) HIPC(hipMemcpyAsync(S_out, dS, sizeof(double) * J * mm, hipMemcpyDeviceToHost, d->stream));
-    if (flag_out) HIPC(hipMemcpyAsync(flag_out, dFlag, sizeof(int) * J, hipMemcpyDeviceToHost, d->stream));
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    return EKF_OK;
+    const double* Tq = d->pend_rows ? d->pend + pend_T(d->ld) : nullptr;   // (no panels before the first deferred call)
+    ekf::launch_dense64_score_sparse(d->S, d->pend, Tq, d->pend_rows, dCols, dHc, dR, r_shared ? 1 : 0, nu ? dNu : nullptr,
+                                     J, m, s, d->ld, nis_out ? dNis : nullptr, dS, dFlag, nullptr, d->stream);
+    return finish_timed(d, elapsed_ms, {{nis_out, dNis, sizeof(double) * J},
+                                        {S_out, dS, sizeof(double) * J * mm},
+                                        {flag_out, dFlag, sizeof(int) * J}});
 }
 
 // ---- (re)initialisation of a block of states, block readouts, state slices ----------------------------------------------
@@ -635,15 +568,7 @@ ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const i
     carry_or_flush(d, in, s > 0 ? dcols : nullptr, first, r, s);
     ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->N, d->ld,
                              first, r, s, d->stream);
-    HIPC(hipEventRecord(d->e1, d->stream));
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(d->stream));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
-        *elapsed_ms = ms;
-    }
-    return EKF_OK;
+    return finish_timed(d, elapsed_ms);
 }
 
 // out[a][c] = Sigma[rows[a]][cols[c]]: the two lists go up, one gather launch into the handle's buffer, one copy back.
@@ -748,11 +673,11 @@ ekf_status ekf_dense64_propagate_block(ekf_dense64_handle d, int first, int r, c
 }
 ekf_status ekf_dense64_correct_sparse(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
                                       const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
-    return dense64_correct_sparse(d, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+    return dense64_correct_sparse(d, false, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
 }
 ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
                                                const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
-    return dense64_correct_sparse_deferred(d, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+    return dense64_correct_sparse(d, true, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
 }
 ekf_status ekf_dense64_flush(ekf_dense64_handle d, double* elapsed_ms) { return dense64_flush(d, elapsed_ms); }
 ekf_status ekf_dense64_pending(ekf_dense64_handle d, int* rows) {

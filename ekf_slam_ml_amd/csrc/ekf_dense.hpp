@@ -81,17 +81,23 @@ void launch_dense64_block(double* Sigma, double* state, const double* Fr, const 
                           int ld, int first, int r, hipStream_t s);
 
 // ---- fp64 measurement update and scoring for a Jacobian with s listed non-zero columns (ekf_dense64_sparse.hip):
-// H[:, cols[k]] = Hc[:, k], every dot product exactly s fused multiply-adds in ascending k of the list.
+// H[:, cols[k]] = Hc[:, k], every dot product exactly s fused multiply-adds in ascending k of the list.  Eager, or
+// deferred: p <= 64 pending rows of two panels [64][ld], Kp[q][i] = K[i][q] and Tq[q][j] = T[q][j], stand for
+// Sigma_cur = Sigma - sum_{q < p} Kp[q]^T Tq[q]; the correction and the scoring read through them,
+// x = fma(-Kp[q][row], Tq[q][col], x) in ascending q before the dot products, and Sigma is rewritten once per flush.
 constexpr int kDense64MaxS = 64;                     // EKF_DENSE64_MAX_S
 constexpr int kDense64ScoreSparseMaxRows = 65536;    // EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
-hipError_t dense64_sparse_prepare();   // raises the dynamic-LDS limits (gather 64.8 KiB, scoring up to 98.8 KiB)
-// One launch: per candidate S_j = (Hc_j Sigma[cols_j, cols_j]) Hc_j^T + R_j, flag_j, nis_j.  All pointers on the device:
-// cols [J][s] (distinct, in [0, N): the launcher does not check), Hc [J][m][s], R [J][m][m] or [m][m] (r_shared),
-// nu [J][m] or NULL with nis NULL, nis [J] nullable, S_out [J][m][m] nullable, flag [J], Sinv [64][64] nullable (the
-// inverse of candidate 0 when its flag is 0).
-void launch_dense64_score_sparse(const double* Sigma, const int* cols, const double* Hc, const double* R, int r_shared,
-                                 const double* nu, int J, int m, int s, int ld, double* nis, double* S_out, int* flag,
-                                 double* Sinv, hipStream_t st);
+constexpr int kDense64PendingMaxRows = 64;           // EKF_DENSE64_PENDING_MAX_ROWS
+// raises the dynamic-LDS limits of both forms (gather 64.8 / 128.8 KiB, scoring up to 98.8 / 114.8 KiB)
+hipError_t dense64_sparse_prepare();
+// One launch: per candidate S_j = (Hc_j Sigma_cur[cols_j, cols_j]) Hc_j^T + R_j, flag_j, nis_j.  All pointers on the device:
+// Kp, Tq and their row count p >= 0 (p = 0: the eager kernel on Sigma as it is, the panels not looked at), cols [J][s]
+// (distinct, in [0, N): the launcher does not check), Hc [J][m][s], R [J][m][m] or [m][m] (r_shared), nu [J][m] or NULL
+// with nis NULL, nis [J] nullable, S_out [J][m][m] nullable, flag [J], Sinv [64][64] nullable (the inverse of candidate 0
+// when its flag is 0).
+void launch_dense64_score_sparse(const double* Sigma, const double* Kp, const double* Tq, int p, const int* cols,
+                                 const double* Hc, const double* R, int r_shared, const double* nu, int J, int m, int s,
+                                 int ld, double* nis, double* S_out, int* flag, double* Sinv, hipStream_t st);
 // Launches 5 and 6 of launch_dense64_correct (k_dc_gain, k_dc_update) on panels and an S^-1 already in ws.
 void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws, const double* nu,
                                  int m, const int* verdict, hipStream_t s);
@@ -100,23 +106,13 @@ void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, do
 void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
                                    const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
                                    double* nis, int* verdict, hipStream_t st);
-
-// ---- fp64 deferred sparse corrections (ekf_dense64_deferred.hip): p <= 64 pending rows of two panels [64][ld],
-// Kp[q][i] = K[i][q] and Tq[q][j] = T[q][j], stand for Sigma_cur = Sigma - sum_{q < p} Kp[q]^T Tq[q]; the correction and the
-// scoring read through them, x = fma(-Kp[q][row], Tq[q][col], x) in ascending q before the dot products of the sparse
-// calls, and Sigma is rewritten once per flush.
-constexpr int kDense64PendingMaxRows = 64;   // EKF_DENSE64_PENDING_MAX_ROWS
-hipError_t dense64_deferred_prepare();   // raises the dynamic-LDS limits (gather 128.8 KiB, scoring up to 114.8 KiB)
-// launch_dense64_score_sparse against Sigma_cur: the same arguments plus the pending panels and their row count p >= 0.
-void launch_dense64_score_deferred(const double* Sigma, const double* Kp, const double* Tq, int p, const int* cols,
-                                   const double* Hc, const double* R, int r_shared, const double* nu, int J, int m, int s,
-                                   int ld, double* nis, double* S_out, int* flag, double* Sinv, hipStream_t st);
 // Launch 5 of launch_dense64_correct (k_dc_gain) on U^T and S^-1 in ws, K^T written to Kt [m][ld] instead of ws.
 void launch_dense64_gain(const Dense64CorrectPlan& pl, const double* ws, double* Kt, double* state, const double* nu, int m,
                          const int* verdict, hipStream_t s);
-// The three launches of one deferred sparse correction, p + m <= 64: the gather through the pending rows (T into rows
-// p .. p + m - 1 of Tq, U^T into ws), the scoring kernel with J = 1 (S^-1 into ws, the verdict word, nis), the gain (K^T
-// into rows p .. p + m - 1 of Kp, state += K nu).  Sigma is not written; a set verdict leaves rows q < p and the state.
+// The three launches of one deferred sparse correction, p + m <= 64, all on the deferred kernels (at p = 0 too): the gather
+// through the pending rows (T into rows p .. p + m - 1 of Tq, U^T into ws), the scoring kernel with J = 1 (S^-1 into ws,
+// the verdict word, nis), the gain (K^T into rows p .. p + m - 1 of Kp, state += K nu).  Sigma is not written; a set
+// verdict leaves rows q < p and the state.
 void launch_dense64_correct_deferred(const Dense64CorrectPlan& pl, const double* Sigma, double* state, double* ws,
                                      double* Kp, double* Tq, int p, const int* cols, const double* Hc, const double* R,
                                      const double* nu, int m, int s, double* nis, int* verdict, hipStream_t st);

@@ -1,5 +1,6 @@
-// ekf_dense64_carry.hip -- the pending rows of the dense fp64 handle (ekf_dense64_deferred.hip) CARRIED through the calls
-// that used to flush them: the block-structured prediction, the (re)initialisation of a block and the block readout.
+// ekf_dense64_carry.hip -- the pending rows of the dense fp64 handle (the deferred form of ekf_dense64_sparse.hip) CARRIED
+// through the calls that used to flush them: the block-structured prediction, the (re)initialisation of a block and the
+// block readout.
 // The current covariance is Sigma_cur = Sigma_base - sum_{q < p} Kp[q]^T Tq[q].  propagate_block and init_block are
 // congruences Sigma <- A Sigma A^T + Q with A the identity except in the r rows b = [first, first + r), and
 //   A Sigma_cur A^T + Q = (A Sigma_base A^T + Q) - sum_q (A Kp[q]^T) (A Tq[q]^T)^T
@@ -11,14 +12,14 @@
 //                     wave loads the <= 64 source entries of its row in one instruction (lane k: v[src[k]]), parks them in
 //                     LDS, and every lane a < r then walks them as broadcasts: all of a row's loads are issued before its
 //                     first store.  2 p * r * s <= 128 * 64 * 64 multiply-adds in <= 32 workgroups: launch-bound.
-//   k_dfp_read_block  k_d64_read_block (ekf_dense64_init.hip) plus the fold of ekf_dense64_deferred.hip: a workgroup owns
+//   k_dfp_read_block  k_d64_read_block (ekf_dense64_init.hip) plus the fold of ekf_dense64_sparse.hip: a workgroup owns
 //                     256 consecutive entries of out, which touch <= 256 listed rows and <= 256 listed columns; their
 //                     pending scalars Kp[q][rows[a]], Tq[q][cols[c]] go through LDS eight rows q at a time.
 // The order (part of the contract, include/ekfslam.h).  Map: acc = +0; acc = fma(M[a][k], v[src[k]], acc) for k = 0, 1, ..
 // -- exactly r (resp. s) terms, the same for both panels, a function of nothing but the block data.  Readout:
-// x = Sigma_base[i][j]; x = fma(-Kp[q][i], Tq[q][j], x) for q = 0, 1, .. p - 1: the fold k_dfp_score applies to the block it
-// reads.  fma() because the library is built with -ffp-contract=off.  No atomics.  Only columns [first, first + r) of rows
-// q < p are written: the panels' padding (columns >= N) and their rows >= p are not touched.
+// x = Sigma_base[i][j]; x = fma(-Kp[q][i], Tq[q][j], x) for q = 0, 1, .. p - 1: the fold the deferred k_dsp_score applies
+// to the block it reads.  fma() because the library is built with -ffp-contract=off.  No atomics.  Only columns
+// [first, first + r) of rows q < p are written: the panels' padding (columns >= N) and their rows >= p are not touched.
 #include <hip/hip_runtime.h>
 
 #include "ekf_dense.hpp"

@@ -457,7 +457,7 @@ void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, do
                        pl.upd_blocks_per_chunk);
 }
 
-// Launch 5 alone, with K^T written to `Kt` instead of the workspace panel (ekf_dense64_deferred.hip: a pending row).
+// Launch 5 alone, with K^T written to `Kt` instead of the workspace panel (the deferred form of ekf_dense64_sparse.hip: a pending row).
 void launch_dense64_gain(const Dense64CorrectPlan& pl, const double* ws, double* Kt, double* state, const double* nu, int m,
                          const int* verdict, hipStream_t s) {
     hipLaunchKernelGGL(k_dc_gain, dim3((pl.N + kGainRows - 1) / kGainRows), dim3(256), 0, s, ws + pl.off_Ut,

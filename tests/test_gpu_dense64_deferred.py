@@ -1,5 +1,5 @@
 """-m gpu: the deferred sparse correction of the fp64 dense handle (ekf_dense64_correct_sparse_deferred, ekf_dense64_flush,
-ekf_dense64_pending, ekf_dense64_deferred.hip): K and T of a correction wait in pending rows, score_sparse and further
+ekf_dense64_pending, ekf_dense64_sparse.hip): K and T of a correction wait in pending rows, score_sparse and further
 deferred corrections read through them, Sigma is rewritten once per flush.  Integer chains bit-exact against numpy's eager
 sequence (tests/test_dense64_deferred_host.py proves them exact in float64); the capacity of 64 rows; random operands
 against the eager sequence through correct_sparse on a twin handle within 1e-12 per block; the bit-level properties of the
