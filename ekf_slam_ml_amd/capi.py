@@ -47,6 +47,7 @@ SYMBOLS = [
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
+    "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
     "ekf_dense64_init_block", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -212,6 +213,9 @@ def load():
         "ekf_dense64_pending": [h, _ip],
         "ekf_dense64_set_carry": [h, C.c_int],
         "ekf_dense64_get_carry": [h, _ip],
+        "ekf_dense64_set_live": [h, C.c_int],
+        "ekf_dense64_get_live": [h, _ip],
+        "ekf_dense64_coupling": [h, C.c_int, C.POINTER(C.c_longlong), _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
         "ekf_dense64_get_state_block": [h, C.c_int, C.c_int, _dp],
@@ -939,6 +943,28 @@ class DensePropagator64:
     @carry.setter
     def carry(self, on):
         _check(self._lib.ekf_dense64_set_carry(self._h, 1 if on else 0))
+
+    @property
+    def live(self):
+        """the live dimension Na (N by default): propagate_block(), correct_sparse(), correct_sparse_deferred(),
+        score_sparse(), init_block() and flush() run the filter of dimension Na in Sigma[:Na, :Na] and state[:Na], cut
+        their launches for Na and neither read nor write anything at an index >= Na.  Exact when the tail is decoupled
+        (coupling(Na)[0] == 0), which the reference's prior and init_block(s = 0) give.  Growing keeps the pending rows,
+        shrinking flushes them first; the dense calls (propagate, correct, score, sigma, set) ignore the setting."""
+        na = C.c_int()
+        _check(self._lib.ekf_dense64_get_live(self._h, C.byref(na)))
+        return na.value
+
+    @live.setter
+    def live(self, Na):
+        _check(self._lib.ekf_dense64_set_live(self._h, int(Na)))
+
+    def coupling(self, Na):
+        """what ties Sigma[:Na, :Na] to the rest: over the entries with exactly one index >= Na, how many are != 0 and
+        the largest absolute value.  Flushes first, otherwise read-only.  Returns (nonzero, max_abs, elapsed_ms)"""
+        count, most, ms = C.c_longlong(), C.c_double(), C.c_double()
+        _check(self._lib.ekf_dense64_coupling(self._h, int(Na), C.byref(count), C.byref(most), C.byref(ms)))
+        return count.value, most.value, ms.value
 
     def _correct_sparse(self, entry, cols, Hc, R, nu):
         cols = self._index_lists(cols, 1)

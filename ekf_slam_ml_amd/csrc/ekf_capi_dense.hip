@@ -7,7 +7,9 @@
 // (ekf_dense64_init.hip), and the deferred form of the sparse update (the second instantiation of ekf_dense64_sparse.hip's
 // kernels): pending rows of K and T that the sparse calls read through and every other call that touches Sigma applies
 // first (flush_pending) -- unless the caller lets propagate_block, init_block and the block readout carry them
-// (ekf_dense64_set_carry, ekf_dense64_carry.hip).
+// (ekf_dense64_set_carry, ekf_dense64_carry.hip).  The structured calls run at the handle's LIVE dimension
+// (ekf_dense64_set_live, N by default): every launch of theirs is cut for it, and nothing at an index from it on is read
+// or written; ekf_dense64_coupling (ekf_dense64_live.hip) measures what ties the live corner to the rest.
 #include "ekf_runtime.hpp"
 
 #include <type_traits>
@@ -47,6 +49,10 @@ struct ekf_dense64_s : DenseHandle<double> {
     double* pend = nullptr;      // K^T [64][ld] | T [64][ld] | a word kept at zero (the flush's verdict argument)
     int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
     int carry = 0;               // ekf_dense64_set_carry: propagate_block, init_block, get_sigma_block do not flush
+    // the live dimension (ekf_dense64_set_live): what the structured calls take for N; the plans change with it, not per call
+    int live = 0;                          // 1 .. N, N unless set
+    ekf::Dense64CorrectPlan pl_full{};     // of (N, ld): the dense correction, and the layout of the workspace
+    ekf::Dense64CorrectPlan pl_live{};     // of (live, ld) on that layout: the sparse corrections and the flush
 };
 
 namespace {
@@ -88,8 +94,7 @@ template <class H>
 void flush_pending(H* d) {
     if constexpr (std::is_same<H, ekf_dense64_s>::value) {
         if (d->pend_rows == 0) return;
-        ekf::launch_dense64_flush(ekf::dense64_correct_plan(d->N, d->ld), d->S, d->pend, d->pend + pend_T(d->ld),
-                                  d->pend_rows, reinterpret_cast<const int*>(d->pend + pend_zero(d->ld)), d->stream);
+        ekf::launch_dense64_flush(d->pl_live, d->S, d->pend, d->pend + pend_T(d->ld), d->pend_rows, reinterpret_cast<const int*>(d->pend + pend_zero(d->ld)), d->stream);
         d->pend_rows = 0;
     }
 }
@@ -191,7 +196,9 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
             HIPC(hipMalloc((void**)&d->corr_in, in));
             HIPC(hipMemsetAsync(d->corr_in, 0, in, d->stream));
             HIPC(hipMalloc((void**)&d->corr_out, 2 * sizeof(double)));
-            const size_t ws = ekf::dense64_correct_plan(N, d->ld).ws_doubles;
+            d->live = N;
+            d->pl_full = d->pl_live = ekf::dense64_correct_plan(N, d->ld);
+            const size_t ws = d->pl_full.ws_doubles;
             if (ws > (size_t)d->ld * d->ld) HIPC(hipMalloc((void**)&d->ws_own, sizeof(double) * ws));
             HIPC(ekf::dense64_block_prepare());
             HIPC(hipMalloc((void**)&d->blk_in, sizeof(double) * kBlkIn));
@@ -291,7 +298,7 @@ ekf_status dense64_correct(ekf_dense64_s* d, int m, const double* H, const doubl
     const size_t piece[3][2] = {{0, (size_t)m * ld}, {oHt, (size_t)ld * mp}, {oR, (size_t)kMaxM * kMaxM + kMaxM}};
     for (const auto& pc : piece)
         HIPC(hipMemcpyAsync(d->corr_in + pc[0], in + pc[0], sizeof(double) * pc[1], hipMemcpyHostToDevice, d->stream));
-    const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
+    const ekf::Dense64CorrectPlan& pl = d->pl_full;
     double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
     HIPC(hipEventRecord(d->e0, d->stream));
     flush_pending(d);
@@ -390,8 +397,8 @@ ekf_status dense64_score(ekf_dense64_s* d, int J, int m, const double* H, const 
 // the handle are not involved.
 ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const double* Fr, const double* Qr,
                                    const double* dx, double* elapsed_ms) {
-    if (!d || !Fr || r < 1 || r > kMaxR || first < 0 || r > d->N || first > d->N - r)
-        return fail(EKF_ERR_INVALID, "ekf_dense64_propagate_block: bad argument");
+    if (!d || !Fr || r < 1 || r > kMaxR || first < 0 || r > d->live || first > d->live - r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_propagate_block: bad argument (the block must lie inside the live dimension)");
     HIPC(hipSetDevice(d->device));
     const size_t rr = sizeof(double) * r * r;
     HIPC(hipMemcpyAsync(d->blk_in, Fr, rr, hipMemcpyHostToDevice, d->stream));
@@ -400,7 +407,7 @@ ekf_status dense64_propagate_block(ekf_dense64_s* d, int first, int r, const dou
     HIPC(hipEventRecord(d->e0, d->stream));
     carry_or_flush(d, d->blk_in, nullptr, first, r, r);
     ekf::launch_dense64_block(d->S, d->x, d->blk_in, Qr ? d->blk_in + kBlkQ : nullptr, dx ? d->blk_in + kBlkDx : nullptr,
-                              d->N, d->ld, first, r, d->stream);
+                              d->live, d->ld, first, r, d->stream);
     return finish_timed(d, elapsed_ms);
 }
 
@@ -429,12 +436,12 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s,
                                   const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
     const std::string fn = deferred ? "ekf_dense64_correct_sparse_deferred" : "ekf_dense64_correct_sparse";
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N || (nis_out && !nu))
+    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live || (nis_out && !nu))
         return fail(EKF_ERR_INVALID, fn + ": bad argument");
-    if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
-        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N)");
+    if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
+        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N), below the live dimension");
     HIPC(hipSetDevice(d->device));
-    const int N = d->N, ld = d->ld;
+    const int ld = d->ld;
     if (deferred && !d->pend) {
         const size_t bytes = sizeof(double) * (pend_zero(ld) + 2);
         double* fresh = nullptr;
@@ -454,7 +461,7 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s,
     HIPC(hipMemcpyAsync(d->corr_in + oCols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
     HIPC(hipMemcpyAsync(d->corr_in + oR, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
     if (nu) HIPC(hipMemcpyAsync(d->corr_in + oNu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
-    const ekf::Dense64CorrectPlan pl = ekf::dense64_correct_plan(N, ld);
+    const ekf::Dense64CorrectPlan& pl = d->pl_live;
     double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
     const int* dcols = reinterpret_cast<const int*>(d->corr_in + oCols);
     const double *dR = d->corr_in + oR, *dnu = nu ? d->corr_in + oNu : nullptr;
@@ -495,11 +502,12 @@ ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int
                                 int r_shared, const double* nu, double* nis_out, double* S_out, int* flag_out,
                                 double* elapsed_ms) {
     if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: null handle");
-    if (!cols || !Hc || !R || J < 1 || m < 1 || m > kMaxM || m > d->N || s < 1 || s > kMaxS || s > d->N ||
+    if (!cols || !Hc || !R || J < 1 || m < 1 || m > kMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live ||
         (long long)J * m > kSparseRows || (nis_out && !nu) || (!nis_out && !S_out && !flag_out))
         return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: bad argument");
-    if (!index_lists_ok(d->host_stamp, d->N, J, s, cols))
-        return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: every row of cols must hold distinct indices in [0, N)");
+    if (!index_lists_ok(d->host_stamp, d->live, J, s, cols))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: every row of cols must hold distinct indices in [0, N), "
+                                     "below the live dimension");
     HIPC(hipSetDevice(d->device));
     const size_t mm = (size_t)m * m, al = 16;
     auto up = [&](size_t b) { return (b + al - 1) / al * al; };
@@ -544,12 +552,13 @@ ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int
 ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const int* cols, const double* G, const double* W,
                               const double* xb, double* elapsed_ms) {
     if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: null handle");
-    if (r < 1 || r > kMaxR || r > d->N || first < 0 || first > d->N - r || s < 0 || s > kMaxS || s > d->N - r ||
+    if (r < 1 || r > kMaxR || r > d->live || first < 0 || first > d->live - r || s < 0 || s > kMaxS || s > d->live - r ||
         (s > 0 && (!cols || !G)))
-        return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: bad argument");
+        return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: bad argument (the block must lie inside the live dimension)");
     if (s > 0) {
-        if (!index_lists_ok(d->host_stamp, d->N, 1, s, cols))
-            return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: cols must hold distinct indices in [0, N)");
+        if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
+            return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: cols must hold distinct indices in [0, N), below the live "
+                                         "dimension");
         for (int k = 0; k < s; k++)
             if (cols[k] >= first && cols[k] < first + r)
                 return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: no index of cols may lie inside [first, first + r) "
@@ -566,7 +575,7 @@ ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const i
     if (xb) HIPC(hipMemcpyAsync(in + kIniXb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
     carry_or_flush(d, in, s > 0 ? dcols : nullptr, first, r, s);
-    ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->N, d->ld,
+    ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->live, d->ld,
                              first, r, s, d->stream);
     return finish_timed(d, elapsed_ms);
 }
@@ -588,7 +597,7 @@ ekf_status dense64_get_sigma_block(ekf_dense64_s* d, int nr, const int* rows, in
     HIPC(hipMemcpyAsync(dcols, cols, sizeof(int) * nc, hipMemcpyHostToDevice, d->stream));
     if (d->carry && d->pend_rows > 0) {   // Sigma_cur through the pending rows; read-only
         ekf::launch_dense64_read_block_deferred(d->S, d->pend, d->pend + pend_T(d->ld), d->pend_rows, drows, dcols,
-                                                d->rd_buf, nr, nc, d->ld, d->stream);
+                                                d->rd_buf, nr, nc, d->ld, d->N, d->live, d->stream);
     } else {
         flush_pending(d);
         ekf::launch_dense64_read_block(d->S, drows, dcols, d->rd_buf, nr, nc, d->ld, d->stream);
@@ -607,6 +616,49 @@ ekf_status dense64_state_block(const char* name, ekf_dense64_s* d, int first, in
     if (out) HIPC(hipMemcpyAsync(out, d->x + first, sizeof(double) * count, hipMemcpyDeviceToHost, d->stream));
     else HIPC(hipMemcpyAsync(d->x + first, x, sizeof(double) * count, hipMemcpyHostToDevice, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+
+// The live dimension.  Growing: a pending row is zero on [old, ld) whatever the panels hold there from wider calls, so those
+// columns of the p waiting rows of both panels are set to zero -- up to the new width rounded up to 128, what the calls of
+// that width keep zero -- and nothing is flushed.  Shrinking: the rows have support up to the old width, so they are applied
+// first, at the old width.
+ekf_status dense64_set_live(ekf_dense64_s* d, int Na) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_set_live: null handle");
+    if (Na < 1 || Na > d->N) return fail(EKF_ERR_INVALID, "ekf_dense64_set_live: the live dimension must lie in [1, N]");
+    if (Na == d->live) return EKF_OK;
+    if (d->pend_rows > 0) {
+        HIPC(hipSetDevice(d->device));
+        if (Na < d->live) {
+            flush_pending(d);
+        } else {
+            const int upto = std::min(d->ld, round_up(Na, ekf::kDenseTile));
+            for (double* panel : {d->pend, d->pend + pend_T(d->ld)})
+                HIPC(hipMemset2DAsync(panel + d->live, sizeof(double) * d->ld, 0, sizeof(double) * (upto - d->live),
+                                      d->pend_rows, d->stream));
+        }
+        HIPC(hipGetLastError());
+        HIPC(hipStreamSynchronize(d->stream));
+    }
+    d->live = Na;
+    d->pl_live = ekf::dense64_live_plan(d->pl_full, Na);
+    return EKF_OK;
+}
+
+// One streaming launch over the two rectangles; the two result words sit where a correction's nis and verdict do.
+ekf_status dense64_coupling(ekf_dense64_s* d, int Na, long long* nonzero, double* max_abs, double* elapsed_ms) {
+    if (!d || !nonzero) return fail(EKF_ERR_INVALID, "ekf_dense64_coupling: null argument");
+    if (Na < 1 || Na > d->N) return fail(EKF_ERR_INVALID, "ekf_dense64_coupling: Na must lie in [1, N]");
+    HIPC(hipSetDevice(d->device));
+    static_assert(sizeof(unsigned long long) == sizeof(double), "two words in corr_out");
+    unsigned long long out[2] = {0, 0};
+    HIPC(hipMemsetAsync(d->corr_out, 0, sizeof(out), d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    flush_pending(d);
+    ekf::launch_dense64_coupling(d->S, d->N, d->ld, Na, reinterpret_cast<unsigned long long*>(d->corr_out), d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
+    *nonzero = (long long)out[0];
+    if (max_abs) std::memcpy(max_abs, &out[1], sizeof(double));
     return EKF_OK;
 }
 
@@ -694,6 +746,15 @@ ekf_status ekf_dense64_get_carry(ekf_dense64_handle d, int* on) {
     if (!d || !on) return fail(EKF_ERR_INVALID, "ekf_dense64_get_carry: null argument");
     *on = d->carry;
     return EKF_OK;
+}
+ekf_status ekf_dense64_set_live(ekf_dense64_handle d, int Na) { return dense64_set_live(d, Na); }
+ekf_status ekf_dense64_get_live(ekf_dense64_handle d, int* Na) {
+    if (!d || !Na) return fail(EKF_ERR_INVALID, "ekf_dense64_get_live: null argument");
+    *Na = d->live;
+    return EKF_OK;
+}
+ekf_status ekf_dense64_coupling(ekf_dense64_handle d, int Na, long long* nonzero, double* max_abs, double* elapsed_ms) {
+    return dense64_coupling(d, Na, nonzero, max_abs, elapsed_ms);
 }
 ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, const int* cols, const double* Hc,
                                     const double* R, int r_shared, const double* nu, double* nis_out, double* S_out,

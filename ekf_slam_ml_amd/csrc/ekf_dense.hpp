@@ -37,8 +37,12 @@ struct Dense64CorrectPlan {
     int n_sparts;                              // 128-column chunks of S = T H^T
     int upd_strips, upd_chunks, upd_blocks_per_chunk;   // update: strips of 128 columns x chunks of 16-row blocks
     size_t off_T, off_Ut, off_Kt, off_Tpart, off_Upart, off_Spart, off_Sinv, ws_doubles;
+    int live;   // 0: N spans the handle; 1: N is a live dimension below it (dense64_live_plan) and indices >= N are off limits
 };
 Dense64CorrectPlan dense64_correct_plan(int N, int ld);
+// The plan of the structured calls (the sparse corrections, the flush) at live dimension Na <= full.N on the same ld and
+// the same workspace layout; `full` itself at Na == full.N.
+Dense64CorrectPlan dense64_live_plan(const Dense64CorrectPlan& full, int Na);
 hipError_t dense64_correct_prepare();   // raises the dynamic-LDS limits (panel pass: up to 99 KiB per workgroup at m > 48)
 // The six launches of one correction on stream s.  Sigma: ld x ld with zero padding (kept); state: ld doubles;
 // ws: pl.ws_doubles doubles; Hd: H as [m][ld] and Ht: H^T as [ld][m rounded up to 16], both zero padded; R: m x m; nu: m or NULL (state
@@ -143,7 +147,14 @@ void launch_dense64_read_block(const double* Sigma, const int* rows, const int* 
 // (then s == r, in place); s = 0 writes +0.  One launch of ceil(2 p / 4) workgroups; nothing at p = 0.
 void launch_dense64_panel_map(double* Kp, double* Tq, int p, const double* M, const int* src, int ld, int first, int r,
                               int s, hipStream_t st);
-// launch_dense64_read_block against Sigma_cur: x = fma(-Kp[q][rows[a]], Tq[q][cols[c]], x) for q = 0 .. p - 1, p >= 1
+// launch_dense64_read_block against Sigma_cur: x = fma(-Kp[q][rows[a]], Tq[q][cols[c]], x) for q = 0 .. p - 1, p >= 1.
+// live < N (the handle's live dimension): an entry with a row or column >= live is returned as stored, the panels unread there.
 void launch_dense64_read_block_deferred(const double* Sigma, const double* Kp, const double* Tq, int p, const int* rows,
-                                        const int* cols, double* out, int nr, int nc, int ld, hipStream_t st);
+                                        const int* cols, double* out, int nr, int nc, int ld, int N, int live,
+                                        hipStream_t st);
+
+// ---- the coupling between the live corner and the tail (ekf_dense64_live.hip): over the two rectangles of an N x N Sigma
+// with exactly one index >= Na, the number of entries != 0 and the largest absolute value.  One streaming launch, integer
+// atomics only.  out: two 64-bit words on the device, zero before the launch: the count, and the bits of the maximum.
+void launch_dense64_coupling(const double* Sigma, int N, int ld, int Na, unsigned long long* out, hipStream_t st);
 }  // namespace ekf

@@ -73,11 +73,15 @@ __global__ __launch_bounds__(kThreads) void k_dfp_map(double* Kp, double* Tq, in
 }
 
 // out[a][c] = Sigma_cur[rows[a]][cols[c]]: the lanes along the column list
+// LIVE (a live dimension below the handle's N, ekf_dense64_set_live): the pending rows have no support at indices >= live --
+// what the panels hold there is left over from wider calls -- so an entry with such a row or column is returned as stored,
+// and the panels are not read at those indices.  LIVE = false is the kernel as it was (`live` unused).
 constexpr int kFoldRows = 8;
+template <bool LIVE>
 __global__ __launch_bounds__(kThreads) void k_dfp_read_block(const double* __restrict__ S, const double* __restrict__ Kp,
                                                              const double* __restrict__ Tq, int p,
                                                              const int* __restrict__ rows, const int* __restrict__ cols,
-                                                             double* __restrict__ out, int nr, int nc, int ld) {
+                                                             double* __restrict__ out, int nr, int nc, int ld, int live) {
     __shared__ double fk[kFoldRows][kThreads];   // Kp[q][rows[a0 + i]]
     __shared__ double ft[kFoldRows][kThreads];   // Tq[q][cols[..]]: index c when nc < 256, else the thread's own column
     const int t = threadIdx.x;
@@ -93,18 +97,22 @@ __global__ __launch_bounds__(kThreads) void k_dfp_read_block(const double* __res
     const int my_col = t < ncl ? cols[wide ? (e0 + t) % nc : t] : 0;          // the column likewise
     const int ia = a - a0, jc = wide ? t : c;
     double x = real ? S[(size_t)rows[a] * ld + cols[c]] : 0.0;
+    bool folds = real;
+    if constexpr (LIVE) folds = real && rows[a] < live && cols[c] < live;
     for (int q0 = 0; q0 < p; q0 += kFoldRows) {
         const int qs = min(kFoldRows, p - q0);
         double kv[kFoldRows], tv[kFoldRows];
 #pragma unroll
         for (int q = 0; q < kFoldRows; q++) {   // every load of the chunk is issued before the first is used
-            kv[q] = (q < qs && t < na) ? Kp[(size_t)(q0 + q) * ld + my_row] : 0.0;
-            tv[q] = (q < qs && t < ncl) ? Tq[(size_t)(q0 + q) * ld + my_col] : 0.0;
+            bool kin = q < qs && t < na, tin = q < qs && t < ncl;
+            if constexpr (LIVE) kin = kin && my_row < live, tin = tin && my_col < live;
+            kv[q] = kin ? Kp[(size_t)(q0 + q) * ld + my_row] : 0.0;
+            tv[q] = tin ? Tq[(size_t)(q0 + q) * ld + my_col] : 0.0;
         }
 #pragma unroll
         for (int q = 0; q < kFoldRows; q++) fk[q][t] = kv[q], ft[q][t] = tv[q];
         __syncthreads();
-        if (real)
+        if (folds)
             for (int q = 0; q < qs; q++) x = fma(-fk[q][ia], ft[q][jc], x);
         __syncthreads();
     }
@@ -123,9 +131,15 @@ void launch_dense64_panel_map(double* Kp, double* Tq, int p, const double* M, co
 }
 
 void launch_dense64_read_block_deferred(const double* Sigma, const double* Kp, const double* Tq, int p, const int* rows,
-                                        const int* cols, double* out, int nr, int nc, int ld, hipStream_t st) {
-    hipLaunchKernelGGL(k_dfp_read_block, dim3((nr * nc + kThreads - 1) / kThreads), dim3(kThreads), 0, st, Sigma, Kp, Tq,
-                       p, rows, cols, out, nr, nc, ld);
+                                        const int* cols, double* out, int nr, int nc, int ld, int N, int live,
+                                        hipStream_t st) {
+    const dim3 grid((nr * nc + kThreads - 1) / kThreads);
+    if (live < N)
+        hipLaunchKernelGGL(k_dfp_read_block<true>, grid, dim3(kThreads), 0, st, Sigma, Kp, Tq, p, rows, cols, out, nr, nc, ld,
+                           live);
+    else
+        hipLaunchKernelGGL(k_dfp_read_block<false>, grid, dim3(kThreads), 0, st, Sigma, Kp, Tq, p, rows, cols, out, nr, nc, ld,
+                           live);
 }
 
 }  // namespace ekf

@@ -287,6 +287,12 @@ __global__ __launch_bounds__(256) void k_dc_gain(const double* __restrict__ Ut, 
 // unit is 16 rows x 128 columns = 4 column groups of 32, each two accumulators: lane (lk, li) owns the ADJACENT columns
 // 32 g + 2 li, + 1 (one 16-byte access; a row of a group is 256 contiguous bytes), which the two MFMAs of the group see as
 // their column li -- the B operand is read from LDS with the same pairing, so the permutation never shows.
+// LIVE (the handle's live dimension N is smaller than its capacity, ekf_dense64_set_live): rows and columns >= N of Sigma are
+// not padding but entries of the tail that the call must neither read nor write, so every load and store of the tile is
+// masked by row < N and column < N (a pair that straddles N as its first element alone); a masked entry enters the MFMA as
+// +0 and its result is dropped.  Row i of the product depends on row i of K and column j on column j of T alone, so what K^T
+// and T hold at indices >= N (the leftovers of a wider call) reaches no stored entry.  LIVE = false is the kernel as it was.
+template <bool LIVE>
 __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const double* __restrict__ Kt,
                                                    const double* __restrict__ Tp, const int* __restrict__ verdict, int N,
                                                    int ld, int m, int blocks_per_chunk) {
@@ -300,6 +306,10 @@ __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const
         const int k = e / (kUpdCols / 2), c2 = (e % (kUpdCols / 2)) * 2;
         f64x2 v = {0.0, 0.0};
         if (k < m) v = *reinterpret_cast<const f64x2*>(Tp + (size_t)k * ld + c0 + c2);
+        if constexpr (LIVE) {   // (the panel is allocated up to ld; what it holds from N on is not this call's)
+            if (c0 + c2 >= N) v[0] = 0.0;
+            if (c0 + c2 + 1 >= N) v[1] = 0.0;
+        }
         *reinterpret_cast<f64x2*>(dc_smem + k * kUpdCols + c2) = v;
     }
     __syncthreads();
@@ -313,7 +323,18 @@ __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const
 #pragma unroll
         for (int g = 0; g < 4; g++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) v[g][r] = *reinterpret_cast<const f64x2*>(base + (size_t)(4 * r) * ld + 32 * g);
+            for (int r = 0; r < 4; r++) {
+                const double* src = base + (size_t)(4 * r) * ld + 32 * g;
+                if constexpr (LIVE) {
+                    const int left = b * 16 + lk + 4 * r < N ? N - (c0 + 2 * li + 32 * g) : 0;   // live entries from here on
+                    f64x2 x = {0.0, 0.0};
+                    if (left >= 2) x = *reinterpret_cast<const f64x2*>(src);
+                    else if (left == 1) x[0] = src[0];
+                    v[g][r] = x;
+                } else {
+                    v[g][r] = *reinterpret_cast<const f64x2*>(src);
+                }
+            }
     };
     int b = b0 + w;
     if (b < b1) gload(b, cur);
@@ -327,7 +348,9 @@ __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const
         const double* kg = Kt + b * 16 + li;
         for (int s = 0; s < kp; s += 4) {
             const int k = s + lk;
-            const double a = k < m ? -kg[(size_t)k * ld] : 0.0;
+            double a = k < m ? -kg[(size_t)k * ld] : 0.0;
+            if constexpr (LIVE)
+                if (b * 16 + li >= N) a = 0.0;
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const f64x2 tv = *reinterpret_cast<const f64x2*>(dc_smem + k * kUpdCols + 32 * g + 2 * li);
@@ -341,7 +364,14 @@ __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 f64x2 v = {ae[g][r], ao[g][r]};
-                *reinterpret_cast<f64x2*>(base + (size_t)(4 * r) * ld + 32 * g) = v;
+                double* dst = base + (size_t)(4 * r) * ld + 32 * g;
+                if constexpr (LIVE) {
+                    const int left = b * 16 + lk + 4 * r < N ? N - (c0 + 2 * li + 32 * g) : 0;
+                    if (left >= 2) *reinterpret_cast<f64x2*>(dst) = v;
+                    else if (left == 1) dst[0] = v[0];
+                } else {
+                    *reinterpret_cast<f64x2*>(dst) = v;
+                }
             }
 #pragma unroll
         for (int g = 0; g < 4; g++)
@@ -353,6 +383,18 @@ __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const
 size_t panels_lds(int mb) { return sizeof(double) * (size_t)(kTile * kTileS + 2 * kTile * (16 * mb + 2)); }
 constexpr size_t kInvertLds = sizeof(double) * (size_t)(kMaxM * kInvS + 4 * kMaxM);
 constexpr size_t kUpdateLds = sizeof(double) * (size_t)kMaxM * kUpdCols;
+
+// Launch 6 at rank k: the kernel as it always was when the plan spans the handle (pl.live == 0), the masked one otherwise.
+void launch_update(const Dense64CorrectPlan& pl, double* Sigma, const double* Kt, const double* Tp, const int* verdict, int k,
+                   hipStream_t s) {
+    const size_t lds = sizeof(double) * (size_t)((k + 3) & ~3) * kUpdCols;
+    if (pl.live)
+        hipLaunchKernelGGL(k_dc_update<true>, dim3(pl.upd_strips, pl.upd_chunks), dim3(256), lds, s, Sigma, Kt, Tp, verdict,
+                           pl.N, pl.ld, k, pl.upd_blocks_per_chunk);
+    else
+        hipLaunchKernelGGL(k_dc_update<false>, dim3(pl.upd_strips, pl.upd_chunks), dim3(256), lds, s, Sigma, Kt, Tp, verdict,
+                           pl.N, pl.ld, k, pl.upd_blocks_per_chunk);
+}
 
 template <int MB>
 void launch_panels(const Dense64CorrectPlan& pl, const double* S, const double* Ht, double* Tpart, double* Upart,
@@ -380,7 +422,10 @@ hipError_t dense64_correct_prepare() {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dc_invert), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)kInvertLds);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dc_update), hipFuncAttributeMaxDynamicSharedMemorySize,
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dc_update<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kUpdateLds);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dc_update<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)kUpdateLds);
 }
 
@@ -418,6 +463,17 @@ Dense64CorrectPlan dense64_correct_plan(int N, int ld) {
     return pl;
 }
 
+// The plan of the structured calls at live dimension Na <= N: every launch is cut for Na (strips, chunks, the rows of the gain)
+// on the handle's ld, and the panels stay where the handle's own plan put them, because the workspace was sized for that.
+Dense64CorrectPlan dense64_live_plan(const Dense64CorrectPlan& full, int Na) {
+    if (Na >= full.N) return full;
+    Dense64CorrectPlan pl = dense64_correct_plan(Na, full.ld);
+    pl.live = 1;
+    pl.off_T = full.off_T, pl.off_Ut = full.off_Ut, pl.off_Kt = full.off_Kt, pl.off_Tpart = full.off_Tpart;
+    pl.off_Upart = full.off_Upart, pl.off_Spart = full.off_Spart, pl.off_Sinv = full.off_Sinv, pl.ws_doubles = full.ws_doubles;
+    return pl;
+}
+
 void launch_dense64_correct(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws, const double* Hd,
                             const double* Ht, const double* R, const double* nu, int m, double* nis, int* verdict,
                             hipStream_t s) {
@@ -439,9 +495,7 @@ void launch_dense64_correct(const Dense64CorrectPlan& pl, double* Sigma, double*
     hipLaunchKernelGGL(k_dc_spart, dim3(pl.n_sparts), dim3(256), 0, s, Tp, Hd, Spart, pl.ld, m);
     hipLaunchKernelGGL(k_dc_invert, dim3(1), dim3(256), kInvertLds, s, Spart, pl.n_sparts, R, nu, Sinv, nis, verdict, m);
     hipLaunchKernelGGL(k_dc_gain, dim3((pl.N + kGainRows - 1) / kGainRows), dim3(256), 0, s, Ut, Sinv, nu, Kt, state, verdict, pl.N, pl.ld, m);
-    hipLaunchKernelGGL(k_dc_update, dim3(pl.upd_strips, pl.upd_chunks), dim3(256),
-                       sizeof(double) * (size_t)((m + 3) & ~3) * kUpdCols, s, Sigma, Kt, Tp, verdict, pl.N, pl.ld, m,
-                       pl.upd_blocks_per_chunk);
+    launch_update(pl, Sigma, Kt, Tp, verdict, m, s);
 }
 
 // Launches 5 and 6 alone, for a caller that has put T, U^T and S^-1 into ws itself (ekf_dense64_sparse.hip).
@@ -452,9 +506,7 @@ void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, do
     double* Kt = ws + pl.off_Kt;
     double* Sinv = ws + pl.off_Sinv;
     hipLaunchKernelGGL(k_dc_gain, dim3((pl.N + kGainRows - 1) / kGainRows), dim3(256), 0, s, Ut, Sinv, nu, Kt, state, verdict, pl.N, pl.ld, m);
-    hipLaunchKernelGGL(k_dc_update, dim3(pl.upd_strips, pl.upd_chunks), dim3(256),
-                       sizeof(double) * (size_t)((m + 3) & ~3) * kUpdCols, s, Sigma, Kt, Tp, verdict, pl.N, pl.ld, m,
-                       pl.upd_blocks_per_chunk);
+    launch_update(pl, Sigma, Kt, Tp, verdict, m, s);
 }
 
 // Launch 5 alone, with K^T written to `Kt` instead of the workspace panel (the deferred form of ekf_dense64_sparse.hip: a pending row).
@@ -468,9 +520,7 @@ void launch_dense64_gain(const Dense64CorrectPlan& pl, const double* ws, double*
 // that holds 0 (the kernel's verdict argument).
 void launch_dense64_flush(const Dense64CorrectPlan& pl, double* Sigma, const double* Kp, const double* Tq, int p,
                           const int* zero, hipStream_t s) {
-    hipLaunchKernelGGL(k_dc_update, dim3(pl.upd_strips, pl.upd_chunks), dim3(256),
-                       sizeof(double) * (size_t)((p + 3) & ~3) * kUpdCols, s, Sigma, Kp, Tq, zero, pl.N, pl.ld, p,
-                       pl.upd_blocks_per_chunk);
+    launch_update(pl, Sigma, Kp, Tq, zero, p, s);
 }
 
 }  // namespace ekf

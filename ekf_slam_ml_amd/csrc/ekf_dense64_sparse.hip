@@ -392,7 +392,9 @@ template <class PEND>
 void launch_panels(const Dense64CorrectPlan& pl, const double* Sigma, PEND pend, double* Tout, double* ws, const int* cols,
                    const double* Hc, const double* R, const double* nu, int m, int s, double* nis, int* verdict,
                    hipStream_t st) {
-    const int n_strips = pl.ld / kStrip;   // ld is a multiple of 128: the panels are written up to ld
+    // the panels are written up to N rounded up to 128 (zeros from N on): ld itself when N spans the handle, and with a live
+    // dimension below it every strip the gain and the update of that width read
+    const int n_strips = (pl.N + 127) / 128 * 2;
     hipLaunchKernelGGL(k_dsp_gather<PEND>, dim3(2 * n_strips), dim3(kThreads), gather_lds(m, s, pend.p), st, Sigma, cols,
                        Hc, Tout, ws + pl.off_Ut, pl.N, pl.ld, m, s, n_strips, pend);
     launch_score(Sigma, pend, cols, Hc, R, 1, nu, 1, m, s, pl.ld, nu ? nis : nullptr, nullptr, verdict, ws + pl.off_Sinv,

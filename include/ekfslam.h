@@ -656,6 +656,51 @@ ekf_status ekf_dense64_pending(ekf_dense64_handle h, int* rows);           /* ro
 ekf_status ekf_dense64_set_carry(ekf_dense64_handle h, int on);
 ekf_status ekf_dense64_get_carry(ekf_dense64_handle h, int* on);
 
+/* The live dimension: the cost of the structured calls follows the map, not the handle's capacity.  A handle is created
+ * once at the capacity N it will ever need; with live = Na < N the STRUCTURED calls -- ekf_dense64_propagate_block,
+ * ekf_dense64_correct_sparse, ekf_dense64_correct_sparse_deferred, ekf_dense64_score_sparse, ekf_dense64_init_block and
+ * ekf_dense64_flush, with the panel map and the read-through of ekf_dense64_set_carry -- treat it as the filter of dimension
+ * Na that lives in Sigma[0:Na, 0:Na] and state[0:Na]: every launch of theirs is cut for Na (a flush rewrites 16 Na^2 bytes,
+ * not 16 N^2), and
+ *   NOTHING OUTSIDE IS READ OR WRITTEN: no entry of Sigma with a row or column index >= Na and no state entry >= Na, neither
+ *   the padding nor the entries between Na and the next multiple of 16 / 64 / 128 that the kernels' tiles cover (there the
+ *   loads and stores are masked element by element; what the workspace and the pending panels hold at indices >= Na from
+ *   wider calls reaches no stored value).
+ * The order of arithmetic of every structured call is independent of N and ld (the contracts above), so the results in the
+ * live corner -- Sigma, state, S, nis, flags, the pending count -- are BIT FOR BIT those of a handle created with N = Na
+ * that holds the same corner.
+ * WHY THE POLICY IS EXACT FOR A GROWING MAP.  If the tail is decoupled, Sigma[i][j] = 0 whenever exactly one of i, j is
+ * >= Na, the full-width call computes T = H Sigma and K = Sigma H^T S^-1 as zero at every index >= Na (H has no column
+ * there), so it changes nothing outside the corner and the live call equals it by value everywhere.  The reference's prior
+ * and ekf_dense64_init_block with s = 0 both give exactly such a tail, and landmarks are appended in discovery order, so
+ * live = 3 + 2 * known is exact.  This is a property of the caller's Sigma, not a check made at run time:
+ * ekf_dense64_coupling is the check.
+ * Arguments: with live = Na an index >= Na in cols, or a block with first + r > Na (and m, r or s larger than Na allows),
+ * returns EKF_ERR_INVALID in the existing order of checks, before the device is looked at; nothing changes, the pending rows
+ * included.  ekf_dense64_get_sigma_block, ekf_dense64_get_state_block and ekf_dense64_set_state_block keep their range
+ * [0, N); with the carry policy on and rows pending, an entry with a row or column index >= Na is returned as stored (the
+ * pending rows have no support there).
+ * Pending rows: growing Na never flushes and is exact -- a pending row is zero on [Na_old, ld) whatever the panels held there
+ * before; the call sets those columns of the waiting rows to zero.  Shrinking Na flushes first, at the old width.
+ * ekf_dense64_set with a Sigma drops the rows as before and leaves the live setting alone, as it leaves the carry policy.
+ * The dense-operand calls -- propagate, correct, score, get_sigma, set -- are defined on all N states and stay full-width:
+ * they flush first as they always did (at the live width: that is where the rows have support) and ignore the setting.
+ * Default live = N: every entry point launches exactly what it launched before the setting existed.  A NULL handle or
+ * pointer, Na < 1 or Na > N return EKF_ERR_INVALID.
+ * ekf_dense64_coupling: over the entries Sigma[i][j], i, j < N, with exactly one index >= Na: *nonzero = how many are != 0
+ * (-0.0 is zero; a NaN counts), *max_abs (nullable) = the largest absolute value, 0 when there is none, NaN if any entry is
+ * a NaN.  The check to run before shrinking, or after building a Sigma by other means.  One streaming launch that reads
+ * 16 Na (N - Na) bytes, the rectangle under the diagonal as rows; integer counts and an integer maximum of bit patterns,
+ * no floating-point atomics: a run repeats bit for bit.  It needs Sigma in memory, so it flushes first like get_sigma;
+ * otherwise read-only.  1 <= Na <= N, Na = N gives 0; it does not look at the live setting.  elapsed_ms (nullable) =
+ * HIP-event time of the launches. */
+ekf_status ekf_dense64_set_live(ekf_dense64_handle h, int Na);      /* 1 <= Na <= N; default N */
+ekf_status ekf_dense64_get_live(ekf_dense64_handle h, int* Na);
+ekf_status ekf_dense64_coupling(ekf_dense64_handle h, int Na,
+                                long long* nonzero,  /* entries Sigma[i][j] != 0 with exactly one of i, j >= Na */
+                                double* max_abs,     /* largest |Sigma[i][j]| among them (0 when none); nullable */
+                                double* elapsed_ms);
+
 /* (Re)initialisation of a block of states: what a map that grows, or a fixed-capacity map that recycles a slot, does to
  * Sigma.  The states b = [first, first + r) are replaced by a new variable y = g(x[cols], z) of s other states and a
  * reading z: G (r x s) is the Jacobian of g with respect to x[cols], W the caller's Gz R Gz^T, xb the value g(..).  The
