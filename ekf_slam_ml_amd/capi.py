@@ -48,7 +48,7 @@ SYMBOLS = [
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
-    "ekf_dense64_init_block", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
+    "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
@@ -217,6 +217,7 @@ def load():
         "ekf_dense64_get_live": [h, _ip],
         "ekf_dense64_coupling": [h, C.c_int, C.POINTER(C.c_longlong), _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
+        "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
         "ekf_dense64_get_state_block": [h, C.c_int, C.c_int, _dp],
         "ekf_dense64_set_state_block": [h, C.c_int, C.c_int, _dp],
@@ -933,8 +934,8 @@ class DensePropagator64:
 
     @property
     def carry(self):
-        """True: propagate_block(), init_block() and sigma_block() leave the pending rows pending (the two updates map
-        them, the readout reads through them) and the caller chooses when to flush(); False (the default): they flush
+        """True: propagate_block(), init_block(), swap_blocks() and sigma_block() leave the pending rows pending (the
+        updates map them, the readout reads through them) and the caller chooses when to flush(); False (the default): they flush
         first.  Setting it touches nothing; it decides what the next calls do."""
         on = C.c_int()
         _check(self._lib.ekf_dense64_get_carry(self._h, C.byref(on)))
@@ -947,7 +948,7 @@ class DensePropagator64:
     @property
     def live(self):
         """the live dimension Na (N by default): propagate_block(), correct_sparse(), correct_sparse_deferred(),
-        score_sparse(), init_block() and flush() run the filter of dimension Na in Sigma[:Na, :Na] and state[:Na], cut
+        score_sparse(), init_block(), swap_blocks() and flush() run the filter of dimension Na in Sigma[:Na, :Na] and state[:Na], cut
         their launches for Na and neither read nor write anything at an index >= Na.  Exact when the tail is decoupled
         (coupling(Na)[0] == 0), which the reference's prior and init_block(s = 0) give.  Growing keeps the pending rows,
         shrinking flushes them first; the dense calls (propagate, correct, score, sigma, set) ignore the setting."""
@@ -1076,6 +1077,23 @@ class DensePropagator64:
         _check(self._lib.ekf_dense64_init_block(self._h, first, r, s, pc, pg,
                                                 W.ctypes.data_as(_dp) if W is not None else None,
                                                 xb.ctypes.data_as(_dp) if xb is not None else None, C.byref(ms)))
+        return ms.value
+
+    def swap_blocks(self, first_a, first_b, r):
+        """Exchange the states [first_a, first_a + r) and [first_b, first_b + r): Sigma <- P Sigma P^T, state <- P state,
+        a pure copy of 2 r rows and 2 r columns in which every entry keeps its bits.  The blocks are disjoint (adjacent is
+        allowed) and lie inside the live dimension; either order gives the same result.  With carry on and rows pending
+        the pending rows take the same permutation and nothing is flushed; otherwise it flushes first.  Removing a landmark
+        in mid-map: swap_blocks(first, last, 2); init_block(last, W=prior); live -= 2.  Returns elapsed_ms."""
+        first_a, first_b, r = int(first_a), int(first_b), int(r)
+        if not 1 <= r <= min(self.N, self.MAX_R):
+            raise ValueError(f"1 <= r <= min(N, {self.MAX_R})")
+        if not (0 <= first_a <= self.N - r and 0 <= first_b <= self.N - r):
+            raise ValueError("both blocks must lie inside [0, N)")
+        if abs(first_a - first_b) < r:
+            raise ValueError("the blocks must be disjoint: |first_a - first_b| >= r")
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_swap_blocks(self._h, first_a, first_b, r, C.byref(ms)))
         return ms.value
 
     def _read_list(self, idx, name):

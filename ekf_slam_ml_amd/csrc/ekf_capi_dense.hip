@@ -4,9 +4,9 @@
 // general Jacobian (ekf_dense64_correct.hip), the read-only scoring of candidate measurements (ekf_dense64_score.hip),
 // the block-structured prediction (ekf_dense64_block.hip), the update and scoring for a Jacobian given by its non-zero
 // columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states and the block readout
-// (ekf_dense64_init.hip), and the deferred form of the sparse update (the second instantiation of ekf_dense64_sparse.hip's
-// kernels): pending rows of K and T that the sparse calls read through and every other call that touches Sigma applies
-// first (flush_pending) -- unless the caller lets propagate_block, init_block and the block readout carry them
+// (ekf_dense64_init.hip), the exchange of two blocks of states (ekf_dense64_swap.hip), and the deferred form of the sparse
+// update (the second instantiation of ekf_dense64_sparse.hip's kernels): pending rows of K and T that the sparse calls read through and every other call that touches Sigma applies
+// first (flush_pending) -- unless the caller lets propagate_block, init_block, swap_blocks and the block readout carry them
 // (ekf_dense64_set_carry, ekf_dense64_carry.hip).  The structured calls run at the handle's LIVE dimension
 // (ekf_dense64_set_live, N by default): every launch of theirs is cut for it, and nothing at an index from it on is read
 // or written; ekf_dense64_coupling (ekf_dense64_live.hip) measures what ties the live corner to the rest.
@@ -580,6 +580,24 @@ ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const i
     return finish_timed(d, elapsed_ms);
 }
 
+// The exchange of two blocks: nothing goes up.  The pending rows take the same permutation (a congruence with A = P, the
+// algebra of carry_or_flush) when the handle carries them, and are applied first otherwise.
+ekf_status dense64_swap_blocks(ekf_dense64_s* d, int first_a, int first_b, int r, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: null handle");
+    if (r < 1 || r > kMaxR || r > d->live || first_a < 0 || first_b < 0 || first_a > d->live - r || first_b > d->live - r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: bad argument (both blocks must lie inside the live dimension)");
+    if (std::abs(first_a - first_b) < r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: the blocks must be disjoint, |first_a - first_b| >= r");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    if (d->carry && d->pend_rows > 0)
+        ekf::launch_dense64_panel_swap(d->pend, d->pend + pend_T(d->ld), d->pend_rows, d->ld, first_a, first_b, r, d->stream);
+    else
+        flush_pending(d);
+    ekf::launch_dense64_swap(d->S, d->x, d->live, d->ld, first_a, first_b, r, d->stream);
+    return finish_timed(d, elapsed_ms);
+}
+
 // out[a][c] = Sigma[rows[a]][cols[c]]: the two lists go up, one gather launch into the handle's buffer, one copy back.
 ekf_status dense64_get_sigma_block(ekf_dense64_s* d, int nr, const int* rows, int nc, const int* cols, double* out) {
     if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: null handle");
@@ -764,6 +782,9 @@ ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, c
 ekf_status ekf_dense64_init_block(ekf_dense64_handle d, int first, int r, int s, const int* cols, const double* G,
                                   const double* W, const double* xb, double* elapsed_ms) {
     return dense64_init_block(d, first, r, s, cols, G, W, xb, elapsed_ms);
+}
+ekf_status ekf_dense64_swap_blocks(ekf_dense64_handle d, int first_a, int first_b, int r, double* elapsed_ms) {
+    return dense64_swap_blocks(d, first_a, first_b, r, elapsed_ms);
 }
 ekf_status ekf_dense64_get_sigma_block(ekf_dense64_handle d, int nr, const int* rows, int nc, const int* cols,
                                        double* out) {

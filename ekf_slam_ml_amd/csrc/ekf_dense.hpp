@@ -153,6 +153,16 @@ void launch_dense64_read_block_deferred(const double* Sigma, const double* Kp, c
                                         const int* cols, double* out, int nr, int nc, int ld, int N, int live,
                                         hipStream_t st);
 
+// ---- the exchange of two blocks of states (ekf_dense64_swap.hip) on the same Sigma and state: Sigma <- P Sigma P^T,
+// state <- P state for the P that swaps [first_a, first_a + r) with [first_b, first_b + r).  A pure copy, one launch of
+// 1 + 2 ceil(N / 64) workgroups (the 2 r x 2 r intersection with the state, the row panel and the column panel in strips of
+// 64); touches nothing outside the two blocks' rows and columns, and nothing at an index >= N.  No LDS.
+// 1 <= r <= 64, both blocks inside [0, N), |first_a - first_b| >= r (the launcher does not check); either order.
+void launch_dense64_swap(double* Sigma, double* state, int N, int ld, int first_a, int first_b, int r, hipStream_t st);
+// The same exchange on the pending rows carried through it: entries [first_a, +r) and [first_b, +r) of every row q < p of
+// both panels.  One launch of ceil(2 p / 4) workgroups; nothing at p = 0.
+void launch_dense64_panel_swap(double* Kp, double* Tq, int p, int ld, int first_a, int first_b, int r, hipStream_t st);
+
 // ---- the coupling between the live corner and the tail (ekf_dense64_live.hip): over the two rectangles of an N x N Sigma
 // with exactly one index >= Na, the number of entries != 0 and the largest absolute value.  One streaming launch, integer
 // atomics only.  out: two 64-bit words on the device, zero before the launch: the count, and the bits of the maximum.

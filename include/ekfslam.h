@@ -639,6 +639,7 @@ ekf_status ekf_dense64_pending(ekf_dense64_handle h, int* rows);           /* ro
  * propagate, correct, score, correct_sparse and get_sigma still flush first; ekf_dense64_set with a Sigma still drops the
  * rows.  With the policy on and nothing pending the three calls launch exactly what they launch with it off.  A refused
  * call (bad arguments, checked before the device is looked at, as above) changes nothing, the pending rows included.
+ * ekf_dense64_swap_blocks (below) is carried in the same way: the pending rows take its permutation.
  * ekf_dense64_set_carry never touches Sigma, the state or the pending rows: it only decides what the next calls do, so it
  * may be switched with rows pending.  on: 0 = off, anything else = on.  A NULL handle or NULL pointer returns
  * EKF_ERR_INVALID.
@@ -658,8 +659,8 @@ ekf_status ekf_dense64_get_carry(ekf_dense64_handle h, int* on);
 
 /* The live dimension: the cost of the structured calls follows the map, not the handle's capacity.  A handle is created
  * once at the capacity N it will ever need; with live = Na < N the STRUCTURED calls -- ekf_dense64_propagate_block,
- * ekf_dense64_correct_sparse, ekf_dense64_correct_sparse_deferred, ekf_dense64_score_sparse, ekf_dense64_init_block and
- * ekf_dense64_flush, with the panel map and the read-through of ekf_dense64_set_carry -- treat it as the filter of dimension
+ * ekf_dense64_correct_sparse, ekf_dense64_correct_sparse_deferred, ekf_dense64_score_sparse, ekf_dense64_init_block,
+ * ekf_dense64_swap_blocks and ekf_dense64_flush, with the panel map and the read-through of ekf_dense64_set_carry -- treat it as the filter of dimension
  * Na that lives in Sigma[0:Na, 0:Na] and state[0:Na]: every launch of theirs is cut for Na (a flush rewrites 16 Na^2 bytes,
  * not 16 N^2), and
  *   NOTHING OUTSIDE IS READ OR WRITTEN: no entry of Sigma with a row or column index >= Na and no state entry >= Na, neither
@@ -689,7 +690,8 @@ ekf_status ekf_dense64_get_carry(ekf_dense64_handle h, int* on);
  * pointer, Na < 1 or Na > N return EKF_ERR_INVALID.
  * ekf_dense64_coupling: over the entries Sigma[i][j], i, j < N, with exactly one index >= Na: *nonzero = how many are != 0
  * (-0.0 is zero; a NaN counts), *max_abs (nullable) = the largest absolute value, 0 when there is none, NaN if any entry is
- * a NaN.  The check to run before shrinking, or after building a Sigma by other means.  One streaming launch that reads
+ * a NaN.  The check to run before shrinking (ekf_dense64_swap_blocks below says how a block in mid-map gets to the end of
+ * the live corner and out of it), or after building a Sigma by other means.  One streaming launch that reads
  * 16 Na (N - Na) bytes, the rectangle under the diagonal as rows; integer counts and an integer maximum of bit patterns,
  * no floating-point atomics: a run repeats bit for bit.  It needs Sigma in memory, so it flushes first like get_sigma;
  * otherwise read-only.  1 <= Na <= N, Na = N gives 0; it does not look at the live setting.  elapsed_ms (nullable) =
@@ -740,6 +742,45 @@ ekf_status ekf_dense64_init_block(ekf_dense64_handle h, int first, int r, int s,
                                   const double* W,     /* r x r row-major, NULL = no addition */
                                   const double* xb,    /* r: state[first + k] = xb[k]; NULL = state untouched */
                                   double* elapsed_ms); /* HIP-event time of the launch only (nullable) */
+
+/* Exchange of two blocks of states: what a map that REMOVES a landmark in its middle does to Sigma.  The call is the
+ * symmetric permutation Sigma <- P Sigma P^T, state <- P state for the P that swaps A = [first_a, first_a + r) with
+ * B = [first_b, first_b + r) and is the identity elsewhere; with k, l in [0, r):
+ *   Sigma[first_a + k][j] <-> Sigma[first_b + k][j]   for every column j outside A u B
+ *   Sigma[i][first_a + k] <-> Sigma[i][first_b + k]   for every row i outside A u B
+ *   new Sigma[A, A] = old Sigma[B, B] and vice versa; new Sigma[first_a + k][first_b + l] = old Sigma[first_b + k][first_a + l]
+ *   and vice versa (the off-diagonal blocks are exchanged, NOT transposed: Sigma is never symmetrised)
+ *   state[first_a + k] <-> state[first_b + k]
+ * and nothing else is read or written.  It is a pure copy: every entry keeps its bits, NaN payloads and -0.0 included; the
+ * padding of Sigma and of the state stays zero; the F and Q of ekf_dense64_set are neither read nor changed.  The argument
+ * order (a, b) or (b, a) gives the same result, and the call is its own inverse.  64 r N bytes move, instead of the 16 N^2
+ * of ekf_dense64_get_sigma and ekf_dense64_set or a dense propagation with a permutation for F.
+ * REMOVING LANDMARK i of a map whose live corner ends with block `last` (INTEGRATION.md spells it):
+ *   ekf_dense64_swap_blocks(h, first_i, first_last, r, ..)      unless i is the last block itself
+ *   ekf_dense64_init_block(h, first_last, r, 0, NULL, NULL, W, NULL, ..)   the block is dropped: decoupled, its corner W
+ *   ekf_dense64_set_live(h, Na - r)
+ * with the same exchange in the caller's own bookkeeping (its copy of the state, its landmark ids); ekf_dense64_coupling is
+ * the check.  Nothing of size N^2 moves except the flush that shrinking already performs.
+ * 1 <= r <= EKF_DENSE64_MAX_R; both blocks inside the live dimension, 0 <= first, first + r <= Na; the blocks disjoint,
+ * |first_a - first_b| >= r (adjacent blocks are allowed; first_a == first_b is not a swap and is refused).  A NULL handle
+ * (checked first) or any bad value returns EKF_ERR_INVALID before the device is looked at; Sigma, the state and the pending
+ * rows are then as they were.
+ * PENDING ROWS.  With the carry policy off, or nothing pending, the call flushes first, as ekf_dense64_init_block does.  With
+ * it on and rows pending nothing is flushed: P is a congruence with A = P, the identity outside the two blocks, so
+ * P Sigma_cur P^T = P Sigma_base P^T - sum_q (P K^T[q]) (P T[q]^T)^T -- the launch runs on Sigma_base, and one small launch
+ * exchanges the entries [first_a, +r) and [first_b, +r) of every pending row q < p of BOTH panels (a pure copy, all of a
+ * row's loads before its stores; the panels' padding and their rows >= p are not touched).  The read-through fold is one
+ * fma per pending row per entry and does not depend on position, so after a carried swap ekf_dense64_get_sigma_block and
+ * ekf_dense64_score_sparse on index lists permuted by P return bit for bit what they returned on the original lists before
+ * it, and the flush gives bit for bit the swap of what it would have given.
+ * LIVE DIMENSION.  The launch is cut for live = Na: nothing at an index >= Na is read or written, and the result is the bits
+ * of a handle created with N = Na.
+ * One launch of 1 + 2 ceil(Na / 64) workgroups (the 2 r x 2 r intersection with the state, the row panel and the column
+ * panel in strips of 64); every entry has exactly one partner and one thread owns the pair, so there is no staging, no
+ * atomics and no dependence on the launch geometry.  The call allocates nothing and sends nothing up.  Synchronous, on the
+ * handle's stream.  elapsed_ms (nullable) = HIP-event time of the launches only. */
+ekf_status ekf_dense64_swap_blocks(ekf_dense64_handle h, int first_a, int first_b, int r,
+                                   double* elapsed_ms); /* HIP-event time of the launches only (nullable) */
 
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
