@@ -46,6 +46,7 @@ SYMBOLS = [
     "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
+    "ekf_dense64_score_landmarks", "ekf_dense64_associate_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
@@ -211,6 +212,9 @@ def load():
         "ekf_dense64_correct_sparse_deferred": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_flush": [h, _dp],
         "ekf_dense64_pending": [h, _ip],
+        "ekf_dense64_score_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip, _ip,
+                                        _dp, _dp, _dp],
+        "ekf_dense64_associate_landmarks": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, _ip, C.c_uint, _ip, _dp, _dp],
         "ekf_dense64_set_carry": [h, C.c_int],
         "ekf_dense64_get_carry": [h, _ip],
         "ekf_dense64_set_live": [h, C.c_int],
@@ -755,6 +759,7 @@ class DensePropagator64:
     SCORE_SPARSE_MAX_ROWS = 65536   # EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
     READ_MAX = 65536   # EKF_DENSE64_READ_MAX
     PENDING_MAX_ROWS = 64   # EKF_DENSE64_PENDING_MAX_ROWS
+    LM_DEFERRED, LM_GROW_LIVE = 1, 2   # EKF_DENSE64_LM_DEFERRED, EKF_DENSE64_LM_GROW_LIVE
 
     def __init__(self, N, device=-1):
         self._lib = load()
@@ -1022,6 +1027,58 @@ class DensePropagator64:
                                                   S.ctypes.data_as(_dp) if S is not None else None,
                                                   flags.ctypes.data_as(_ip), C.byref(ms)))
         return nis, S, flags, ms.value
+
+    def score_landmarks(self, sx, sy, first_lm=0, count=None, want_S=False, want_terms=False, params=None):
+        """calculate_maha_dis (ekf_slam.cpp:217-276) of the reading (sx, sy) against landmarks [first_lm, first_lm + count)
+        of the handle's own state [theta, x, y, m1x, m1y, ...]: the operands are built on the device and scored by
+        score_sparse()'s kernel, read-only.  count None: every landmark from first_lm that lies inside the live dimension.
+        params: a Params or None (the reference's constants).  Returns (nis, S or None, flags, elapsed_ms), and with
+        want_terms also (cols (count, 5), Hc (count, 2, 5), nu (count, 2) raw) -- handed back to score_sparse() they give
+        the same bits."""
+        first_lm = int(first_lm)
+        if count is None:
+            count = (self.live - 3) // 2 - first_lm
+        count = int(count)
+        if first_lm < 0 or not 1 <= count <= self.SCORE_SPARSE_MAX_ROWS // 2:
+            raise ValueError(f"first_lm >= 0 and 1 <= count <= {self.SCORE_SPARSE_MAX_ROWS // 2}")
+        nis, flags = np.empty(count, dtype=np.float64), np.empty(count, dtype=np.int32)
+        S = np.empty((count, 2, 2), dtype=np.float64) if want_S else None
+        cols = np.empty((count, 5), dtype=np.int32) if want_terms else None
+        Hc = np.empty((count, 2, 5), dtype=np.float64) if want_terms else None
+        nu = np.empty((count, 2), dtype=np.float64) if want_terms else None
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_score_landmarks(
+            self._h, C.byref(params) if params is not None else None, float(sx), float(sy), first_lm, count,
+            nis.ctypes.data_as(_dp), S.ctypes.data_as(_dp) if want_S else None, flags.ctypes.data_as(_ip),
+            cols.ctypes.data_as(_ip) if want_terms else None, Hc.ctypes.data_as(_dp) if want_terms else None,
+            nu.ctypes.data_as(_dp) if want_terms else None, C.byref(ms)))
+        if want_terms:
+            return nis, S, flags, ms.value, (cols, Hc, nu)
+        return nis, S, flags, ms.value
+
+    def associate_landmarks(self, readings, known, n_max, deferred=False, grow_live=False, params=None):
+        """data_association (ekf_slam.cpp:278-402) for the readings (J, 2) in order, on the handle's own state: per reading
+        the known landmarks are scored, the reference's rule is applied on the device, a new landmark is initialised
+        (init_block's path, s = 0, W = sigma0 I), the winner is corrected (correct_sparse, or correct_sparse_deferred with
+        deferred=True) and the heading wrapped.  grow_live: a new landmark first grows the live dimension when it has to.
+        Returns (known, assoc (J,) int32: landmark corrected / -1 dropped, best (J,), elapsed_ms).  A refused call or a
+        singular S raises EkfError; the exception carries .known, .assoc and .best as they stood."""
+        z = np.ascontiguousarray(readings, dtype=np.float64)
+        if z.ndim != 2 or z.shape[1] != 2 or z.shape[0] < 1:
+            raise ValueError("readings must be J x 2 with J >= 1")
+        J = z.shape[0]
+        k = C.c_int(int(known))
+        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
+        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        ms = C.c_double()
+        try:
+            _check(self._lib.ekf_dense64_associate_landmarks(
+                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
+                flags, assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), C.byref(ms)))
+        except EkfError as e:
+            e.known, e.assoc, e.best = k.value, assoc, best
+            raise
+        return k.value, assoc, best, ms.value
 
     def init_block(self, first, G=None, cols=None, W=None, xb=None, r=None):
         """(Re)initialise the states b = [first, first + r) as a function of the s states in cols: Sigma <- F Sigma F^T + Q

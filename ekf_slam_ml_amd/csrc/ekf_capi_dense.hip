@@ -53,6 +53,8 @@ struct ekf_dense64_s : DenseHandle<double> {
     int live = 0;                          // 1 .. N, N unless set
     ekf::Dense64CorrectPlan pl_full{};     // of (N, ld): the dense correction, and the layout of the workspace
     ekf::Dense64CorrectPlan pl_live{};     // of (live, ld) on that layout: the sparse corrections and the flush
+    // the landmark front end (ekf_dense64_associate_landmarks): nothing until the first call
+    ekf::Dense64LmRecord* lm_rec = nullptr;   // the decision record of one reading
 };
 
 namespace {
@@ -153,6 +155,8 @@ ekf_status dense_destroy(H* d) {
             if (p) (void)hipFree(p);
     if constexpr (std::is_same<H, ekf_dense64_s>::value)
         if (d->sps) (void)hipFree(d->sps);
+    if constexpr (std::is_same<H, ekf_dense64_s>::value)
+        if (d->lm_rec) (void)hipFree(d->lm_rec);
     for (hipEvent_t e : {d->e0, d->e1})
         if (e) (void)hipEventDestroy(e);
     if (d->stream) (void)hipStreamDestroy(d->stream);
@@ -432,41 +436,37 @@ bool index_lists_ok(std::vector<int>& stamp, int N, int rows, int s, const int* 
 // pending rows are applied first, four launches.  Deferred: three launches (no pass over Sigma) unless the m new rows do not
 // fit; K and T stay in the pending panels, which the first call allocates (into a local: the member changes only when
 // everything succeeded).
-ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s, const int* cols, const double* Hc,
-                                  const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
-    const std::string fn = deferred ? "ekf_dense64_correct_sparse_deferred" : "ekf_dense64_correct_sparse";
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live || (nis_out && !nu))
-        return fail(EKF_ERR_INVALID, fn + ": bad argument");
-    if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
-        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N), below the live dimension");
-    HIPC(hipSetDevice(d->device));
-    const int ld = d->ld;
-    if (deferred && !d->pend) {
-        const size_t bytes = sizeof(double) * (pend_zero(ld) + 2);
-        double* fresh = nullptr;
-        hipError_t e = hipMalloc((void**)&fresh, bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(fresh, 0, bytes, d->stream);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(d->stream);
-            if (fresh) (void)hipFree(fresh);
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
-                        fn + ": " + hipGetErrorString(e) + " while reserving the pending panels");
-        }
-        d->pend = fresh;
+// The public entry point is checks | pend_reserve | uploads | e0 | correct_sparse_launch | correct_sparse_finish; a caller
+// whose operands are already in the operand buffer (the landmark front end) runs the last two alone.
+constexpr size_t kCsCols = (size_t)kMaxM * ekf::kDense64MaxS;   // the list behind Hc (64 ld >= 8192)
+inline size_t cs_R(int ld) { return (size_t)2 * kMaxM * ld; }
+inline size_t cs_nu(int ld) { return cs_R(ld) + kMaxM * kMaxM; }
+
+ekf_status pend_reserve(ekf_dense64_s* d, const std::string& fn) {
+    if (d->pend) return EKF_OK;
+    const size_t bytes = sizeof(double) * (pend_zero(d->ld) + 2);
+    double* fresh = nullptr;
+    hipError_t e = hipMalloc((void**)&fresh, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(fresh, 0, bytes, d->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(d->stream);
+        if (fresh) (void)hipFree(fresh);
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                    fn + ": " + hipGetErrorString(e) + " while reserving the pending panels");
     }
-    const size_t oCols = (size_t)kMaxM * kMaxS, oR = (size_t)2 * kMaxM * ld, oNu = oR + kMaxM * kMaxM;   // (64 ld >= 8192)
-    HIPC(hipMemcpyAsync(d->corr_in, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipMemcpyAsync(d->corr_in + oCols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipMemcpyAsync(d->corr_in + oR, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
-    if (nu) HIPC(hipMemcpyAsync(d->corr_in + oNu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
+    d->pend = fresh;
+    return EKF_OK;
+}
+
+// the launches of one correction on operands that sit in the operand buffer; behind e0
+void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool have_nu) {
+    const int ld = d->ld;
     const ekf::Dense64CorrectPlan& pl = d->pl_live;
     double* ws = d->ws_own ? d->ws_own : d->T;   // (the product buffer is dead between propagations)
-    const int* dcols = reinterpret_cast<const int*>(d->corr_in + oCols);
-    const double *dR = d->corr_in + oR, *dnu = nu ? d->corr_in + oNu : nullptr;
+    const int* dcols = reinterpret_cast<const int*>(d->corr_in + kCsCols);
+    const double *dR = d->corr_in + cs_R(ld), *dnu = have_nu ? d->corr_in + cs_nu(ld) : nullptr;
     int* dverdict = reinterpret_cast<int*>(d->corr_out + 1);
-    HIPC(hipEventRecord(d->e0, d->stream));
     if (!deferred || d->pend_rows + m > kMaxP) flush_pending(d);   // deferred: only when there is no room for m more rows
     if (deferred)
         ekf::launch_dense64_correct_deferred(pl, d->S, d->x, ws, d->pend, d->pend + pend_T(ld), d->pend_rows, dcols,
@@ -474,6 +474,11 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s,
     else
         ekf::launch_dense64_correct_sparse(pl, d->S, d->x, ws, dcols, d->corr_in, dR, dnu, m, s, d->corr_out, dverdict,
                                            d->stream);
+}
+
+// the one synchronisation of a correction, its verdict, the count of the pending rows
+ekf_status correct_sparse_finish(ekf_dense64_s* d, const std::string& fn, bool deferred, int m, double* nis_out,
+                                 double* elapsed_ms) {
     double nis = 0.0;
     int verdict = 0;
     EKFC(finish_correction(d, elapsed_ms, &nis, &verdict));
@@ -484,6 +489,26 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s,
     if (deferred) d->pend_rows += m;
     if (nis_out) *nis_out = nis;
     return EKF_OK;
+}
+
+ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s, const int* cols, const double* Hc,
+                                  const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    const std::string fn = deferred ? "ekf_dense64_correct_sparse_deferred" : "ekf_dense64_correct_sparse";
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, fn + ": bad argument");
+    if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
+        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N), below the live dimension");
+    HIPC(hipSetDevice(d->device));
+    const int ld = d->ld;
+    if (deferred) EKFC(pend_reserve(d, fn));
+    HIPC(hipMemcpyAsync(d->corr_in, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(d->corr_in + kCsCols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(d->corr_in + cs_R(ld), R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(d->corr_in + cs_nu(ld), nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    correct_sparse_launch(d, deferred, m, s, nu != nullptr);
+    return correct_sparse_finish(d, fn, deferred, m, nis_out, elapsed_ms);
 }
 
 ekf_status dense64_flush(ekf_dense64_s* d, double* elapsed_ms) {
@@ -498,6 +523,58 @@ ekf_status dense64_flush(ekf_dense64_s* d, double* elapsed_ms) {
 
 // Sparse scoring of J candidates: the operands go up into one buffer (allocated into a local, the members change only when
 // that succeeded), one launch, the outputs come straight back into the caller's arrays.
+// The public entry point is checks | sps_layout | sps_reserve | uploads | e0 | score_sparse_launch | copies back; a caller
+// that builds the operands on the device (the landmark front end) writes them at the same offsets and launches the same.
+struct SpsLayout {
+    size_t oR, oNu, oNis, oS, oCols, oFlag, need;   // bytes from the buffer's start; Hc at 0
+};
+SpsLayout sps_layout(int J, int m, int s, bool r_shared, bool want_S) {
+    const size_t mm = (size_t)m * m, al = 16;
+    auto up = [&](size_t b) { return (b + al - 1) / al * al; };
+    const size_t bHc = sizeof(double) * J * m * s, bR = sizeof(double) * (r_shared ? mm : J * mm);
+    SpsLayout l;
+    l.oR = up(bHc);
+    l.oNu = l.oR + up(bR);
+    l.oNis = l.oNu + up(sizeof(double) * J * m);
+    l.oS = l.oNis + up(sizeof(double) * J);
+    l.oCols = l.oS + (want_S ? up(sizeof(double) * J * mm) : 0);
+    l.oFlag = l.oCols + up(sizeof(int) * J * s);
+    l.need = l.oFlag + up(sizeof(int) * J);
+    return l;
+}
+struct SpsView {
+    double *Hc, *R, *nu, *nis, *S;
+    int *cols, *flag;
+};
+SpsView sps_view(ekf_dense64_s* d, const SpsLayout& l, bool want_S) {
+    char* b = d->sps;
+    return {reinterpret_cast<double*>(b), reinterpret_cast<double*>(b + l.oR), reinterpret_cast<double*>(b + l.oNu),
+            reinterpret_cast<double*>(b + l.oNis), want_S ? reinterpret_cast<double*>(b + l.oS) : nullptr,
+            reinterpret_cast<int*>(b + l.oCols), reinterpret_cast<int*>(b + l.oFlag)};
+}
+ekf_status sps_reserve(ekf_dense64_s* d, size_t need, const char* fn) {
+    if (need <= d->sps_bytes) return EKF_OK;
+    char* fresh = nullptr;
+    const hipError_t e = hipMalloc((void**)&fresh, need);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                    std::string(fn) + ": " + hipGetErrorString(e) + " while reserving the candidates' buffer");
+    }
+    if (d->sps) (void)hipFree(d->sps);   // (synchronises; no scoring call is in flight)
+    d->sps = fresh;
+    d->sps_bytes = need;
+    return EKF_OK;
+}
+// the one launch on operands that sit in the buffer: eager, or read-through as rows are pending
+void score_sparse_launch(ekf_dense64_s* d, const SpsView& v, int J, int m, int s, bool r_shared, bool have_nu,
+                         bool want_nis) {
+    const double* Tq = d->pend_rows ? d->pend + pend_T(d->ld) : nullptr;   // (no panels before the first deferred call)
+    ekf::launch_dense64_score_sparse(d->S, d->pend, Tq, d->pend_rows, v.cols, v.Hc, v.R, r_shared ? 1 : 0,
+                                     have_nu ? v.nu : nullptr, J, m, s, d->ld, want_nis ? v.nis : nullptr, v.S, v.flag,
+                                     nullptr, d->stream);
+}
+
 ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int* cols, const double* Hc, const double* R,
                                 int r_shared, const double* nu, double* nis_out, double* S_out, int* flag_out,
                                 double* elapsed_ms) {
@@ -509,46 +586,34 @@ ekf_status dense64_score_sparse(ekf_dense64_s* d, int J, int m, int s, const int
         return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: every row of cols must hold distinct indices in [0, N), "
                                      "below the live dimension");
     HIPC(hipSetDevice(d->device));
-    const size_t mm = (size_t)m * m, al = 16;
-    auto up = [&](size_t b) { return (b + al - 1) / al * al; };
-    const size_t bHc = sizeof(double) * J * m * s, bR = sizeof(double) * (r_shared ? mm : J * mm);
-    const size_t oR = up(bHc), oNu = oR + up(bR), oNis = oNu + up(sizeof(double) * J * m), oS = oNis + up(sizeof(double) * J);
-    const size_t oCols = oS + (S_out ? up(sizeof(double) * J * mm) : 0), oFlag = oCols + up(sizeof(int) * J * s);
-    const size_t need = oFlag + up(sizeof(int) * J);
-    if (need > d->sps_bytes) {
-        char* fresh = nullptr;
-        const hipError_t e = hipMalloc((void**)&fresh, need);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
-                        std::string("ekf_dense64_score_sparse: ") + hipGetErrorString(e) +
-                            " while reserving the candidates' buffer");
-        }
-        if (d->sps) (void)hipFree(d->sps);   // (synchronises; no scoring call is in flight)
-        d->sps = fresh;
-        d->sps_bytes = need;
-    }
-    char* b = d->sps;
-    double *dHc = reinterpret_cast<double*>(b), *dR = reinterpret_cast<double*>(b + oR);
-    double *dNu = reinterpret_cast<double*>(b + oNu), *dNis = reinterpret_cast<double*>(b + oNis);
-    double* dS = S_out ? reinterpret_cast<double*>(b + oS) : nullptr;
-    int *dCols = reinterpret_cast<int*>(b + oCols), *dFlag = reinterpret_cast<int*>(b + oFlag);
-    HIPC(hipMemcpyAsync(dHc, Hc, bHc, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipMemcpyAsync(dR, R, bR, hipMemcpyHostToDevice, d->stream));
-    if (nu) HIPC(hipMemcpyAsync(dNu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipMemcpyAsync(dCols, cols, sizeof(int) * J * s, hipMemcpyHostToDevice, d->stream));
+    const size_t mm = (size_t)m * m;
+    const SpsLayout l = sps_layout(J, m, s, r_shared != 0, S_out != nullptr);
+    EKFC(sps_reserve(d, l.need, "ekf_dense64_score_sparse"));
+    const SpsView v = sps_view(d, l, S_out != nullptr);
+    HIPC(hipMemcpyAsync(v.Hc, Hc, sizeof(double) * J * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(v.R, R, sizeof(double) * (r_shared ? mm : J * mm), hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(v.nu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(v.cols, cols, sizeof(int) * J * s, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    const double* Tq = d->pend_rows ? d->pend + pend_T(d->ld) : nullptr;   // (no panels before the first deferred call)
-    ekf::launch_dense64_score_sparse(d->S, d->pend, Tq, d->pend_rows, dCols, dHc, dR, r_shared ? 1 : 0, nu ? dNu : nullptr,
-                                     J, m, s, d->ld, nis_out ? dNis : nullptr, dS, dFlag, nullptr, d->stream);
-    return finish_timed(d, elapsed_ms, {{nis_out, dNis, sizeof(double) * J},
-                                        {S_out, dS, sizeof(double) * J * mm},
-                                        {flag_out, dFlag, sizeof(int) * J}});
+    score_sparse_launch(d, v, J, m, s, r_shared != 0, nu != nullptr, nis_out != nullptr);
+    return finish_timed(d, elapsed_ms, {{nis_out, v.nis, sizeof(double) * J},
+                                        {S_out, v.S, sizeof(double) * J * mm},
+                                        {flag_out, v.flag, sizeof(int) * J}});
 }
 
 // ---- (re)initialisation of a block of states, block readouts, state slices ----------------------------------------------
 // G, W, xb and the list go up into the buffer allocated with the handle, one launch, timed by the handle's events.  The
 // stored F and Q of the handle are not involved.
+// the launches on operands that sit in the buffer (the public call after its uploads, the landmark front end after
+// k_dlm_decide): the pending rows carried or applied, then the one launch; behind e0
+void init_block_launch(ekf_dense64_s* d, int first, int r, int s, bool have_W, bool have_xb) {
+    double* in = d->ini_in;
+    int* dcols = reinterpret_cast<int*>(in + kIniCols);
+    carry_or_flush(d, in, s > 0 ? dcols : nullptr, first, r, s);
+    ekf::launch_dense64_init(d->S, d->x, dcols, in, have_W ? in + kIniW : nullptr, have_xb ? in + kIniXb : nullptr, d->live,
+                             d->ld, first, r, s, d->stream);
+}
+
 ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const int* cols, const double* G, const double* W,
                               const double* xb, double* elapsed_ms) {
     if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: null handle");
@@ -574,9 +639,7 @@ ekf_status dense64_init_block(ekf_dense64_s* d, int first, int r, int s, const i
     if (W) HIPC(hipMemcpyAsync(in + kIniW, W, sizeof(double) * r * r, hipMemcpyHostToDevice, d->stream));
     if (xb) HIPC(hipMemcpyAsync(in + kIniXb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    carry_or_flush(d, in, s > 0 ? dcols : nullptr, first, r, s);
-    ekf::launch_dense64_init(d->S, d->x, dcols, in, W ? in + kIniW : nullptr, xb ? in + kIniXb : nullptr, d->live, d->ld,
-                             first, r, s, d->stream);
+    init_block_launch(d, first, r, s, W != nullptr, xb != nullptr);
     return finish_timed(d, elapsed_ms);
 }
 
@@ -680,6 +743,135 @@ ekf_status dense64_coupling(ekf_dense64_s* d, int Na, long long* nonzero, double
     return EKF_OK;
 }
 
+// ---- the landmark front end: the reference's model and decision rule on the handle's own state -------------------------
+ekf::Params landmark_params(const ekf_params* params) {
+    ekf_params p;
+    ekf_default_params(&p);
+    if (params) p = *params;
+    return ekf::Params{p.sigma0_landmark, p.q_pose, p.r_meas, p.gate_new, p.gate_update, p.straight_eps};
+}
+
+// calculate_maha_dis (:217-276) of one reading: k_dlm_terms writes the operands where the uploads of score_sparse would
+// put them, then that call's one launch; everything asked for comes back behind the one synchronisation.
+ekf_status dense64_score_landmarks(ekf_dense64_s* d, const ekf_params* params, double sx, double sy, int first_lm, int count,
+                                   double* nis_out, double* S_out, int* flag_out, int* cols_out, double* Hc_out,
+                                   double* nu_out, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_score_landmarks: null handle");
+    if (count < 1 || count > kSparseRows / 2 || first_lm < 0 || 3 + 2 * ((long long)first_lm + count) > d->live ||
+        (!nis_out && !S_out && !flag_out))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_landmarks: bad argument (the landmarks must lie inside the live "
+                                     "dimension)");
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    const SpsLayout l = sps_layout(count, 2, 5, true, S_out != nullptr);
+    EKFC(sps_reserve(d, l.need, "ekf_dense64_score_landmarks"));
+    const SpsView v = sps_view(d, l, S_out != nullptr);
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_lm_terms(d->x, sx, sy, first_lm, count, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+    score_sparse_launch(d, v, count, 2, 5, true, true, nis_out != nullptr);
+    return finish_timed(d, elapsed_ms, {{nis_out, v.nis, sizeof(double) * count},
+                                        {S_out, v.S, sizeof(double) * count * 4},
+                                        {flag_out, v.flag, sizeof(int) * count},
+                                        {cols_out, v.cols, sizeof(int) * count * 5},
+                                        {Hc_out, v.Hc, sizeof(double) * count * 10},
+                                        {nu_out, v.nu, sizeof(double) * count * 2}});
+}
+
+// data_association (:278-402) for J readings.  Per reading: [terms | score | decide] and the 32-byte record back (the first
+// synchronisation); then, as the record says, [init_block] [terms of the winner, wrapped | correction | heading wrap] and
+// the correction's own synchronisation.  Nothing of the state comes down and no candidate array goes up.
+ekf_status dense64_associate_landmarks(ekf_dense64_s* d, const ekf_params* params, int J, const double* meas_xy, int n_max,
+                                       int* known, unsigned flags, int* assoc_out, double* best_out, double* elapsed_ms) {
+    const std::string fn = "ekf_dense64_associate_landmarks";
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (J < 1) return fail(EKF_ERR_INVALID, fn + ": J must be at least 1");
+    if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
+        return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
+    if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
+    if (3 + 2 * *known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
+    if (flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
+        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    for (int j = 0; j < J; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+    }
+    HIPC(hipSetDevice(d->device));
+    if (!d->lm_rec) {
+        ekf::Dense64LmRecord* fresh = nullptr;
+        const hipError_t e = hipMalloc((void**)&fresh, sizeof(*fresh));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                        fn + ": " + hipGetErrorString(e) + " while reserving the decision record");
+        }
+        d->lm_rec = fresh;
+    }
+    if (deferred) EKFC(pend_reserve(d, fn));
+    // the scoring buffer once, for the full map: a map that is being discovered must not pay a hipMalloc and a hipFree
+    // (a device synchronisation) per new landmark
+    if (n_max > 0) EKFC(sps_reserve(d, sps_layout(n_max, 2, 5, true, false).need, fn.c_str()));
+    double total = 0.0, ms = 0.0;
+    double* pms = elapsed_ms ? &ms : nullptr;
+    for (int j = 0; j < J; j++) {
+        const double sx = meas_xy[2 * j], sy = meas_xy[2 * j + 1];
+        const int k = *known;
+        SpsView v{};
+        if (k > 0) v = sps_view(d, sps_layout(k, 2, 5, true, false), false);   // (k <= n_max: inside the buffer)
+        HIPC(hipEventRecord(d->e0, d->stream));
+        if (k > 0) {
+            ekf::launch_dense64_lm_terms(d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+            score_sparse_launch(d, v, k, 2, 5, true, true, true);
+        }
+        ekf::launch_dense64_lm_decide(v.nis, k, k, n_max, p.gate_new, p.gate_update, p.sigma0_landmark, d->x, sx, sy,
+                                      d->lm_rec, d->ini_in + kIniW, d->ini_in + kIniXb, d->stream);
+        ekf::Dense64LmRecord rec{};
+        EKFC(finish_timed(d, pms, {{&rec, d->lm_rec, sizeof(rec)}}));
+        total += ms;
+        if (elapsed_ms) *elapsed_ms = total;
+        if (best_out) best_out[j] = rec.best;
+        if (rec.kind == 0) {   // dropped: nothing at all is written
+            if (assoc_out) assoc_out[j] = -1;
+            continue;
+        }
+        const bool fresh_lm = (rec.kind & ekf::kDense64LmNew) != 0, corrects = (rec.kind & ekf::kDense64LmCorrect) != 0;
+        if (fresh_lm && 3 + 2 * (k + 1) > d->live) {
+            if (!(flags & EKF_DENSE64_LM_GROW_LIVE))
+                return fail(EKF_ERR_INVALID, fn + ": a new landmark does not fit the live dimension (grow it with "
+                                                  "ekf_dense64_set_live, or pass EKF_DENSE64_LM_GROW_LIVE)");
+            EKFC(dense64_set_live(d, 3 + 2 * (k + 1)));
+        }
+        HIPC(hipEventRecord(d->e0, d->stream));
+        if (fresh_lm) init_block_launch(d, 3 + 2 * k, 2, 0, true, true);   // s = 0, W = sigma0 I, xb
+        if (!corrects) {   // (a gate_update <= 0: the landmark is initialised and not corrected)
+            EKFC(finish_timed(d, pms));
+            total += ms;
+            if (elapsed_ms) *elapsed_ms = total;
+            *known = k + 1;
+            if (assoc_out) assoc_out[j] = -1;
+            continue;
+        }
+        // the winner's operands from the current state, that is after an initialisation; the innovation wrapped (:183)
+        ekf::launch_dense64_lm_terms(d->x, sx, sy, rec.win, 1, 1, p.r_meas, reinterpret_cast<int*>(d->corr_in + kCsCols),
+                                     d->corr_in, d->corr_in + cs_R(d->ld), d->corr_in + cs_nu(d->ld), d->stream);
+        correct_sparse_launch(d, deferred, 2, 5, true);
+        ekf::launch_dense64_lm_wrap(d->x, reinterpret_cast<const int*>(d->corr_out + 1), d->stream);   // :187 / :385
+        if (assoc_out) assoc_out[j] = -1;
+        ms = 0.0;
+        const ekf_status st = correct_sparse_finish(d, fn, deferred, 2, nullptr, pms);
+        if (fresh_lm && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + 1;   // the initialisation stands
+        total += ms;   // (a refused correction's launches ran and were timed)
+        if (elapsed_ms) *elapsed_ms = total;
+        if (st != EKF_OK) return st;
+        if (assoc_out) assoc_out[j] = rec.win;
+    }
+    return EKF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -778,6 +970,17 @@ ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, c
                                     const double* R, int r_shared, const double* nu, double* nis_out, double* S_out,
                                     int* flag_out, double* elapsed_ms) {
     return dense64_score_sparse(d, J, m, s, cols, Hc, R, r_shared, nu, nis_out, S_out, flag_out, elapsed_ms);
+}
+ekf_status ekf_dense64_score_landmarks(ekf_dense64_handle d, const ekf_params* params, double sx, double sy, int first_lm,
+                                       int count, double* nis_out, double* S_out, int* flag_out, int* cols_out,
+                                       double* Hc_out, double* nu_out, double* elapsed_ms) {
+    return dense64_score_landmarks(d, params, sx, sy, first_lm, count, nis_out, S_out, flag_out, cols_out, Hc_out, nu_out,
+                                   elapsed_ms);
+}
+ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy,
+                                           int n_max, int* known, unsigned flags, int* assoc_out, double* best_out,
+                                           double* elapsed_ms) {
+    return dense64_associate_landmarks(d, params, J, meas_xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
 }
 ekf_status ekf_dense64_init_block(ekf_dense64_handle d, int first, int r, int s, const int* cols, const double* G,
                                   const double* W, const double* xb, double* elapsed_ms) {

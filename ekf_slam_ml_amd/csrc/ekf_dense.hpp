@@ -163,6 +163,32 @@ void launch_dense64_swap(double* Sigma, double* state, int N, int ld, int first_
 // both panels.  One launch of ceil(2 p / 4) workgroups; nothing at p = 0.
 void launch_dense64_panel_swap(double* Kp, double* Tq, int p, int ld, int first_a, int first_b, int r, hipStream_t st);
 
+// ---- the reference's landmark model and decision rule on the handle's state (ekf_dense64_landmarks.hip): state is
+// [theta, x, y, m1x, m1y, ...], candidate j of a call is landmark first_lm + j.
+// One thread per candidate: cols [count][5] = {0, 1, 2, 3 + 2 i, 4 + 2 i}, Hc [count][2][5] (predicted_terms), nu [count][2]
+// = z - zhat with the bearing raw (wrap = 0, the score's) or wrapped (wrap = 1, the correction's), R [2][2] = r_meas I;
+// Hc and nu on 16-byte boundaries.  3 + 2 (first_lm + count) <= the state's length (the launcher does not check).
+void launch_dense64_lm_terms(const double* state, double sx, double sy, int first_lm, int count, int wrap, double r_meas,
+                             int* cols, double* Hc, double* R, double* nu, hipStream_t st);
+// what k_dlm_decide leaves for the host: 32 bytes
+enum : int { kDense64LmCorrect = 1, kDense64LmNew = 2 };
+struct Dense64LmRecord {
+    int win;          // the landmark to correct (== known for a new one), -1: the reading is dropped
+    int kind;         // kDense64LmCorrect | kDense64LmNew
+    double best;      // the winning score, gate_new when no candidate won
+    double runner;    // the second-smallest score of the call and its candidate (+inf, INT_MAX with fewer than two)
+    int runner_idx, pad;
+};
+static_assert(sizeof(Dense64LmRecord) == 32, "the decision record is one 32-byte copy");
+// One workgroup: best = gate_new, win = known, the scores nis [count] (count = 0: none, nis unread) in ascending index
+// with a strict <, NaNs skipped; win == known < n_max: a new landmark, xb [2] = initialize_landmark, W [2][2] = sigma0 I,
+// the gate sees 0; gate < gate_update: corrected.  Independent of the launch geometry (ties resolve to the lower index).
+void launch_dense64_lm_decide(const double* nis, int count, int known, int n_max, double gate_new, double gate_update,
+                              double sigma0, const double* state, double sx, double sy, Dense64LmRecord* rec, double* W,
+                              double* xb, hipStream_t st);
+// state[0] = normalize_angle(state[0]) unless *verdict != 0 (the correction before it refused and wrote nothing)
+void launch_dense64_lm_wrap(double* state, const int* verdict, hipStream_t st);
+
 // ---- the coupling between the live corner and the tail (ekf_dense64_live.hip): over the two rectangles of an N x N Sigma
 // with exactly one index >= Na, the number of entries != 0 and the largest absolute value.  One streaming launch, integer
 // atomics only.  out: two 64-bit words on the device, zero before the launch: the count, and the bits of the maximum.

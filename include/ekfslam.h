@@ -623,6 +623,84 @@ ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle h, int m, int 
 ekf_status ekf_dense64_flush(ekf_dense64_handle h, double* elapsed_ms);    /* no-op, 0 ms, with nothing pending */
 ekf_status ekf_dense64_pending(ekf_dense64_handle h, int* rows);           /* rows of K / T waiting, 0 .. 64 */
 
+/* The landmark front end: the reference's data_association() (ekf_slam.cpp:278-402) on the handle's own state.  The sparse
+ * calls above are model-free, so a caller that spells the reference's loop with them reads the state back,
+ * builds one Jacobian per known landmark on the host, sends them up, takes the scores down, decides, and builds the
+ * winner's operands again -- five or six synchronous calls around one scoring launch.  Everything in between is a function
+ * of values that already sit in device memory; these two calls keep it there.  They are a layer over the calls above and
+ * below (score_sparse, correct_sparse[_deferred], init_block, set_live), which stay exactly as they are.
+ * State layout: [theta, x, y, m1x, m1y, ...], landmark i at 3 + 2 i, 4 + 2 i.  params: sigma0_landmark, r_meas, gate_new,
+ * gate_update are used; NULL = the reference's constants (ekf_default_params).
+ * OPERANDS, built on the device by one thread per candidate from the device helpers of the single-filter path (the same
+ * source, compiled with the library's -ffp-contract=off): candidate i has cols = {0, 1, 2, 3 + 2 i, 4 + 2 i}; Hc is the
+ * reference's Hj at those columns (:158-166: four divisions and one sqrt); R = r_meas I, shared; nu = z - zhat with
+ * z = (sqrt(sx^2 + sy^2), atan2(sy, sx)) and the predicted bearing wrapped (:152-155).  The innovation itself is RAW for
+ * scoring -- the reference's own quirk (:269) -- and WRAPPED in its bearing for the correction (:183).
+ * ekf_dense64_score_landmarks: calculate_maha_dis (:217-276) of one reading against landmarks [first_lm, first_lm + count).
+ *   It is ekf_dense64_score_sparse(J = count, m = 2, s = 5, r_shared = 1) on those operands: the same kernel (eager, or
+ *   read-through as rows are pending), the same flags (flag 1 and nis = NaN for a singular or non-finite S), the same
+ *   nullability (nis_out, S_out, flag_out not all NULL).  nis, S and flag are bit for bit what ekf_dense64_score_sparse
+ *   returns when it is handed cols_out, Hc_out, nu_out back.  1 <= count <= EKF_DENSE64_SCORE_SPARSE_MAX_ROWS / 2,
+ *   first_lm >= 0, 3 + 2 (first_lm + count) <= live; otherwise EKF_ERR_INVALID before the device is looked at, a NULL
+ *   handle first.  Read-only: Sigma, the state and the pending rows are untouched.  One synchronisation; nothing goes up.
+ * ekf_dense64_associate_landmarks: data_association for J readings in order.  *known (IN/OUT) counts the initialised
+ *   landmarks, which are landmarks 0 .. *known - 1; n_max is the map's capacity.  Per reading, THE RULE (:293-330):
+ *     best = gate_new, win = known; the known landmarks are scored (as above) and visited in ascending index with a strict
+ *     <, so the first of equal scores wins; a NaN score -- a flagged candidate -- never wins and disturbs nobody else.
+ *     win == known and known < n_max: a new landmark.  Its state becomes initialize_landmark's position (:200-214), its
+ *       covariance goes through ekf_dense64_init_block's path with s = 0 and W = sigma0_landmark I, *known is incremented,
+ *       and the gate below sees best = 0.
+ *     best < gate_update: the winner's operands are rebuilt from the current state (after an initialisation) and the
+ *       correction runs -- ekf_dense64_correct_sparse, or ekf_dense64_correct_sparse_deferred with
+ *       EKF_DENSE64_LM_DEFERRED -- and then state[0] = normalize_angle(state[0]) is stored unconditionally, as :187 / :385
+ *       do (a heading of -0.0 becomes +0.0, as in the reference).
+ *     otherwise the reading is dropped and nothing at all is written; known == n_max with nothing under gate_new drops it.
+ *   assoc_out[j] (nullable): the landmark corrected, -1 for a reading that was dropped (or whose correction was refused, or
+ *   that initialised a landmark without correcting it, which only a gate_update <= 0 does), -2 for a reading the call did
+ *   not reach.  best_out[j] (nullable): the winning score, gate_new when no known landmark won (a new landmark included).
+ *   COMPOSITION: the call goes through the internal paths of the calls it names, so every rule of theirs holds unchanged:
+ *   scores read through the pending rows, a deferred correction flushes first when its two rows do not fit, the eager one
+ *   and init_block flush first -- or, with the carry policy on, init_block maps the pending rows.  For one reading the
+ *   state and Sigma afterwards are bit for bit those of a twin handle on which the host makes the same decision and calls
+ *   init_block (W, xb) / correct_sparse[_deferred] with the operands the device built, and sets the heading.
+ *   EKF_DENSE64_LM_GROW_LIVE: a new landmark first grows the live dimension to 3 + 2 (known + 1) when it is smaller, by
+ *   ekf_dense64_set_live (exact, keeps the pending rows).  Without it a new landmark beyond the live dimension returns
+ *   EKF_ERR_INVALID before that reading changes anything; earlier readings stand.
+ *   FAILURES: checked before the device is looked at, in this order: NULL handle; NULL known or meas_xy; J < 1; n_max < 0
+ *   or 3 + 2 n_max > N; *known outside [0, n_max]; 3 + 2 *known > live; unknown flag bits -> EKF_ERR_INVALID, nothing
+ *   changes.  A singular or non-finite S of the winner returns EKF_ERR_STATE from that reading's correction, with that
+ *   reading's effects as the sparse calls define them (state, Sigma and pending rows as before the correction; an
+ *   initialisation that preceded it stands and is counted in *known; the heading is not rewritten).  Earlier readings
+ *   stand, later assoc_out entries are -2, *known is what it was after the last completed step.
+ *   SYNCHRONISATION: two points per reading -- the 32-byte decision record {win, kind, best, runner-up}, and the
+ *   correction's own (a dropped reading has the first only).  One case has a third: a new landmark that grows the live
+ *   dimension (EKF_DENSE64_LM_GROW_LIVE) while rows are pending goes through ekf_dense64_set_live, which clears the new
+ *   columns of the pending panels and synchronises; with nothing pending the growth costs nothing.  A reading goes up as sixteen bytes of kernel arguments; no
+ *   candidate array goes up and no state comes down.  No floating-point atomics; the decision does not depend on the launch
+ *   geometry (ties resolve to the lower index at every level of the reduction): the same inputs give the same bits on every
+ *   run.  Memory: the scoring buffer of ekf_dense64_score_sparse, reserved once per call for n_max candidates (so a map
+ *   that is being discovered never reallocates it), the pending panels with EKF_DENSE64_LM_DEFERRED, 32 bytes
+ *   for the record; a failure to reserve returns EKF_ERR_NOMEM / EKF_ERR_HIP and leaves the handle as it was.
+ * elapsed_ms (nullable) = HIP-event time of the launches only, summed over the readings, those of a reading that ends in
+ * EKF_ERR_STATE or in the live refusal included. */
+ekf_status ekf_dense64_score_landmarks(ekf_dense64_handle h, const ekf_params* params,
+                                       double sx, double sy, int first_lm, int count,
+                                       double* nis_out,   /* [count]            nullable */
+                                       double* S_out,     /* [count][2][2]      nullable */
+                                       int* flag_out,     /* [count]            nullable */
+                                       int* cols_out,     /* [count][5]         nullable: the operands the device built */
+                                       double* Hc_out,    /* [count][2][5]      nullable */
+                                       double* nu_out,    /* [count][2] raw (un-wrapped) innovation, nullable */
+                                       double* elapsed_ms);
+#define EKF_DENSE64_LM_DEFERRED  1u  /* corrections through the deferred path (pending rows), else correct_sparse */
+#define EKF_DENSE64_LM_GROW_LIVE 2u  /* a new landmark first grows the live dimension to 3 + 2 (known + 1) if it is smaller */
+ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle h, const ekf_params* params, int J,
+                                           const double* meas_xy /* [J][2] */, int n_max, int* known /* IN/OUT */,
+                                           unsigned flags,
+                                           int* assoc_out,    /* [J] landmark corrected, -1 dropped, -2 not reached; nullable */
+                                           double* best_out,  /* [J] winning score (gate_new when nothing won); nullable */
+                                           double* elapsed_ms);
+
 /* Carrying the pending rows across ticks: the caller chooses the flush cadence.  With the policy off (the default) every
  * entry point does exactly what is written above.  With it on and rows pending, the three calls a SLAM tick makes between
  * its corrections no longer flush:
