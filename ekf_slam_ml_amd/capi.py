@@ -691,20 +691,23 @@ class BatchEKF:
         _check(self._lib.ekf_batch_set_update_mode(self._h, int(max_pending_corrections), int(symmetric_gather)))
 
 
-class DensePropagator:
-    """Sigma <- F Sigma F^T + Q for an arbitrary dense F, fp32 on the matrix cores (configs[3]):
-    the reference's `sigma = At*sigma*At.t() + Q` (ekf_slam.cpp:101-102) as two dense products."""
+class _DensePropagatorBase:
+    """What the two dense handles share; a subclass names its entry points (_PREFIX), its element type (_DTYPE) and the
+    ctypes pointer to it (_PTR)."""
 
     def __init__(self, N, device=-1):
         self._lib = load()
         self.N = int(N)
         h = C.c_void_p()
-        _check(self._lib.ekf_dense_create(self.N, device, C.byref(h)))
+        _check(self._entry("create")(self.N, device, C.byref(h)))
         self._h = h
+
+    def _entry(self, name):
+        return getattr(self._lib, self._PREFIX + name)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.ekf_dense_destroy(self._h)
+            self._entry("destroy")(self._h)
             self._h = None
 
     __del__ = close
@@ -712,42 +715,52 @@ class DensePropagator:
     def _f(self, a):
         if a is None:
             return None, None
-        a = np.ascontiguousarray(a, dtype=np.float32)
+        a = np.ascontiguousarray(a, dtype=self._DTYPE)
         if a.shape != (self.N, self.N):
             raise ValueError("matrices must be N x N")
-        return a, a.ctypes.data_as(_fp)
+        return a, a.ctypes.data_as(self._PTR)
 
     def set(self, F=None, Sigma=None, Q=None):
         keep = [self._f(x) for x in (F, Sigma, Q)]
-        _check(self._lib.ekf_dense_set(self._h, keep[0][1], keep[1][1], keep[2][1]))
+        _check(self._entry("set")(self._h, keep[0][1], keep[1][1], keep[2][1]))
 
     def propagate(self, iterations=1):
         ms = C.c_double()
-        _check(self._lib.ekf_dense_propagate(self._h, int(iterations), C.byref(ms)))
+        _check(self._entry("propagate")(self._h, int(iterations), C.byref(ms)))
         return ms.value
 
     @property
     def sigma(self):
-        out = np.empty((self.N, self.N), dtype=np.float32)
-        _check(self._lib.ekf_dense_get_sigma(self._h, out.ctypes.data_as(_fp)))
+        out = np.empty((self.N, self.N), dtype=self._DTYPE)
+        _check(self._entry("get_sigma")(self._h, out.ctypes.data_as(self._PTR)))
         return out
 
-    def launch_info(self):
-        """{ld, tiles, n_big, n_tail}: how one product is cut into 256 x 128 tiles and a quarter-tile tail (test hook)"""
+    def _launch_info(self):
         v = [C.c_int() for _ in range(4)]
-        _check(self._lib.ekf_dense_launch_info(self._h, *[C.byref(x) for x in v]))
+        _check(self._entry("launch_info")(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("ld", "tiles", "n_big", "n_tail"), (x.value for x in v)))
 
     def tile_map(self):
         """bool [tiles][tiles] over the 128 x 128 blocks of the result: True = computed by the tail kernel"""
         t = self.launch_info()["tiles"]
         m = np.zeros(t * t, dtype=np.uint8)
-        _check(self._lib.ekf_dense_tile_map(self._h, m.ctypes.data_as(_bp)))
+        _check(self._entry("tile_map")(self._h, m.ctypes.data_as(_bp)))
         assert set(np.unique(m)) <= {0, 1}, "a block of the result is computed by no kernel"
         return m.reshape(t, t).astype(bool)
 
 
-class DensePropagator64:
+class DensePropagator(_DensePropagatorBase):
+    """Sigma <- F Sigma F^T + Q for an arbitrary dense F, fp32 on the matrix cores (configs[3]):
+    the reference's `sigma = At*sigma*At.t() + Q` (ekf_slam.cpp:101-102) as two dense products."""
+
+    _PREFIX, _DTYPE, _PTR = "ekf_dense_", np.float32, _fp
+
+    def launch_info(self):
+        """{ld, tiles, n_big, n_tail}: how one product is cut into 256 x 128 tiles and a quarter-tile tail (test hook)"""
+        return self._launch_info()
+
+
+class DensePropagator64(_DensePropagatorBase):
     """The fp64 twin of DensePropagator: Sigma <- F Sigma F^T + Q with fp64 operands and fp64 accumulation on the matrix
     cores, within the library's 1e-9 contract.  Takes and returns np.float64.  The handle also owns a state vector and
     the other half of a Kalman step, correct(): the measurement update for an arbitrary dense Jacobian."""
@@ -761,42 +774,7 @@ class DensePropagator64:
     PENDING_MAX_ROWS = 64   # EKF_DENSE64_PENDING_MAX_ROWS
     LM_DEFERRED, LM_GROW_LIVE = 1, 2   # EKF_DENSE64_LM_DEFERRED, EKF_DENSE64_LM_GROW_LIVE
 
-    def __init__(self, N, device=-1):
-        self._lib = load()
-        self.N = int(N)
-        h = C.c_void_p()
-        _check(self._lib.ekf_dense64_create(self.N, device, C.byref(h)))
-        self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ekf_dense64_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _f(self, a):
-        if a is None:
-            return None, None
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if a.shape != (self.N, self.N):
-            raise ValueError("matrices must be N x N")
-        return a, a.ctypes.data_as(_dp)
-
-    def set(self, F=None, Sigma=None, Q=None):
-        keep = [self._f(x) for x in (F, Sigma, Q)]
-        _check(self._lib.ekf_dense64_set(self._h, keep[0][1], keep[1][1], keep[2][1]))
-
-    def propagate(self, iterations=1):
-        ms = C.c_double()
-        _check(self._lib.ekf_dense64_propagate(self._h, int(iterations), C.byref(ms)))
-        return ms.value
-
-    @property
-    def sigma(self):
-        out = np.empty((self.N, self.N), dtype=np.float64)
-        _check(self._lib.ekf_dense64_get_sigma(self._h, out.ctypes.data_as(_dp)))
-        return out
+    _PREFIX, _DTYPE, _PTR = "ekf_dense64_", np.float64, _dp
 
     @property
     def state(self):
@@ -1195,17 +1173,7 @@ class DensePropagator64:
 
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""
-        v = [C.c_int() for _ in range(4)]
-        _check(self._lib.ekf_dense64_launch_info(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("ld", "tiles", "n_big", "n_tail"), (x.value for x in v)))
-
-    def tile_map(self):
-        """bool [tiles][tiles] over the 128 x 128 blocks of the result: True = computed by the tail kernel"""
-        t = self.launch_info()["tiles"]
-        m = np.zeros(t * t, dtype=np.uint8)
-        _check(self._lib.ekf_dense64_tile_map(self._h, m.ctypes.data_as(_bp)))
-        assert set(np.unique(m)) <= {0, 1}, "a block of the result is computed by no kernel"
-        return m.reshape(t, t).astype(bool)
+        return self._launch_info()
 
 
 MAX_CLUSTERS = 128

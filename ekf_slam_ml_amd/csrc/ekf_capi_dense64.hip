@@ -1,0 +1,604 @@
+// ekf_capi_dense64.hip -- C ABI of include/ekfslam.h, what the fp64 dense handle has beyond the propagation it shares with
+// the fp32 one (ekf_capi_dense.hip): a state vector, the dense measurement update (ekf_dense64_correct.hip), the read-only
+// scoring of candidates (ekf_dense64_score.hip), the block-structured prediction (ekf_dense64_block.hip), the update and
+// scoring for a Jacobian given by its non-zero columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states
+// and the block readout (ekf_dense64_init.hip), the exchange of two blocks (ekf_dense64_swap.hip), the landmark front end
+// (ekf_dense64_landmarks.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
+// read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
+// propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
+// The structured calls run at the handle's LIVE dimension (ekf_dense64_set_live, N by default): every launch of theirs is
+// cut for it, and nothing at an index from it on is read or written; ekf_dense64_coupling (ekf_dense64_live.hip) measures
+// what ties the live corner to the rest.  Where an operand sits in its buffer is ekf_dense64_layout.hpp's business; the
+// entry points see the typed views of ekf_dense_handle.hpp only.
+#include "ekf_dense_handle.hpp"
+
+using namespace ekfrt;
+
+ekf_status ekf_dense64_s::created() {
+    HIPC(ekf::dense64_correct_prepare());
+    const size_t in = L::corr_in_layout(ld).bytes;
+    HIPC(hipMalloc((void**)&x, sizeof(double) * ld));
+    HIPC(hipMemsetAsync(x, 0, sizeof(double) * ld, stream));
+    HIPC(hipMalloc((void**)&corr_in, in));
+    HIPC(hipMemsetAsync(corr_in, 0, in, stream));
+    HIPC(hipMalloc((void**)&corr_out, L::corr_out_layout().bytes));
+    live = N;
+    pl_full = pl_live = ekf::dense64_correct_plan(N, ld);
+    const size_t ws = pl_full.ws_doubles;
+    if (ws > (size_t)ld * ld) HIPC(hipMalloc((void**)&ws_own, sizeof(double) * ws));
+    HIPC(ekf::dense64_block_prepare());
+    HIPC(hipMalloc((void**)&blk_in, L::blk_in_layout().bytes));
+    HIPC(ekf::dense64_sparse_prepare());
+    HIPC(ekf::dense64_init_prepare());
+    HIPC(hipMalloc((void**)&ini_in, L::ini_in_layout().bytes));
+    HIPC(hipMalloc((void**)&rd_buf, L::rd_buf_layout().bytes));
+    return EKF_OK;
+}
+
+void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
+    for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p})
+        if (p) (void)hipFree(p);
+}
+
+namespace {
+
+constexpr int kMaxM = ekf::kDense64MaxM, kMaxR = ekf::kDense64MaxR, kMaxS = ekf::kDense64MaxS;
+constexpr int kMaxP = ekf::kDense64PendingMaxRows, kReadMax = ekf::kDense64ReadMax;
+constexpr int kScoreRows = ekf::kDense64ScoreMaxRows, kSparseRows = ekf::kDense64ScoreSparseMaxRows;
+
+// finish_timed of a correction: corr_out (nis | verdict) comes back in one copy; *verdict: 0 = applied, 1 = S singular.
+ekf_status finish_correction(ekf_dense64_s* d, double* elapsed_ms, double* nis, int* verdict) {
+    double out[2] = {0.0, 0.0};
+    EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
+    *nis = out[0];
+    std::memcpy(verdict, &out[1], sizeof(int));
+    return EKF_OK;
+}
+
+// every row of cols [rows][s]: indices in [0, N), no index twice
+bool index_lists_ok(std::vector<int>& stamp, int N, int rows, int s, const int* cols) {
+    stamp.assign(N, 0);
+    for (int j = 0; j < rows; j++)
+        for (int k = 0; k < s; k++) {
+            const int c = cols[(size_t)j * s + k];
+            if (c < 0 || c >= N || stamp[c] == j + 1) return false;
+            stamp[c] = j + 1;
+        }
+    return true;
+}
+
+// ---- a Jacobian given by its s non-zero columns ---------------------------------------------------------------------------
+// One sparse correction: cols, Hc, R, nu go up into the (otherwise unused) operand buffer of the dense correction
+// (CorrSparseLayout), the verdict and nis come back in one copy.  Eager: the pending rows are applied first, four launches.
+// Deferred: three launches (no pass over Sigma) unless the m new rows do not fit; K and T stay in the pending panels, which
+// the first call allocates.
+// The public entry point is checks | pend_reserve | uploads | e0 | correct_sparse_launch | correct_sparse_finish; a caller
+// that builds the operands on the device (the landmark front end) writes them through the same view and runs the last two.
+ekf_status pend_reserve(ekf_dense64_s* d, const char* fn) {
+    return d->pend.reserve(L::pend_layout(d->ld).bytes, d->stream, true, fn, "the pending panels");
+}
+
+// the launches of one correction on operands that sit in the operand buffer; behind e0
+void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool have_nu) {
+    const CorrSparseView in = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    const CorrOutView out = view(d->corr_out, L::corr_out_layout());
+    const double* dnu = have_nu ? in.nu : nullptr;
+    if (!deferred || d->pend_rows + m > kMaxP) d->flush_pending();   // deferred: only when there is no room for m more rows
+    const PendView p = d->panels();
+    if (deferred)
+        ekf::launch_dense64_correct_deferred(d->pl_live, d->S, d->x, d->workspace(), p.K, p.T, d->pend_rows, in.cols, in.Hc,
+                                             in.R, dnu, m, s, out.nis, out.verdict, d->stream);
+    else
+        ekf::launch_dense64_correct_sparse(d->pl_live, d->S, d->x, d->workspace(), in.cols, in.Hc, in.R, dnu, m, s, out.nis,
+                                           out.verdict, d->stream);
+}
+
+// the one synchronisation of a correction, its verdict, the count of the pending rows
+ekf_status correct_sparse_finish(ekf_dense64_s* d, const char* fn, bool deferred, int m, double* nis_out,
+                                 double* elapsed_ms) {
+    double nis = 0.0;
+    int verdict = 0;
+    EKFC(finish_correction(d, elapsed_ms, &nis, &verdict));
+    if (verdict != 0)
+        return fail(EKF_ERR_STATE, std::string(fn) + ": H Sigma H^T + R is singular or not finite (zero or non-finite pivot); " +
+                                       (deferred ? "state, Sigma and the pending rows are unchanged"
+                                                 : "state and Sigma are unchanged"));
+    if (deferred) d->pend_rows += m;
+    if (nis_out) *nis_out = nis;
+    return EKF_OK;
+}
+
+ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s, const int* cols, const double* Hc,
+                                  const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    const std::string fn = deferred ? "ekf_dense64_correct_sparse_deferred" : "ekf_dense64_correct_sparse";
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!cols || !Hc || !R || m < 1 || m > kMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, fn + ": bad argument");
+    if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
+        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N), below the live dimension");
+    HIPC(hipSetDevice(d->device));
+    if (deferred) EKFC(pend_reserve(d, fn.c_str()));
+    const CorrSparseView in = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    HIPC(hipMemcpyAsync(in.Hc, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(in.cols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(in.R, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(in.nu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    correct_sparse_launch(d, deferred, m, s, nu != nullptr);
+    return correct_sparse_finish(d, fn.c_str(), deferred, m, nis_out, elapsed_ms);
+}
+
+// Sparse scoring of J candidates: the operands go up into one buffer (SpsLayout), one launch, the outputs come straight back
+// into the caller's arrays.
+// The public entry point is checks | sps_layout | sps_reserve | uploads | e0 | score_sparse_launch | copies back; a caller
+// that builds the operands on the device (the landmark front end) writes them through the same view and launches the same.
+ekf_status sps_reserve(ekf_dense64_s* d, size_t need, const char* fn) {
+    return d->sps.reserve(need, d->stream, false, fn, "the candidates' buffer");
+}
+// the one launch on operands that sit in the buffer: eager, or read-through as rows are pending
+void score_sparse_launch(ekf_dense64_s* d, const SpsView& v, int J, int m, int s, bool r_shared, bool have_nu,
+                         bool want_nis) {
+    const PendView p = d->panels();   // (null before the first deferred call)
+    ekf::launch_dense64_score_sparse(d->S, p.K, d->pend_rows ? p.T : nullptr, d->pend_rows, v.cols, v.Hc, v.R,
+                                     r_shared ? 1 : 0, have_nu ? v.nu : nullptr, J, m, s, d->ld, want_nis ? v.nis : nullptr,
+                                     v.S, v.flag, nullptr, d->stream);
+}
+
+// ---- (re)initialisation of a block of states -----------------------------------------------------------------------------
+// the launches on operands that sit in ini_in (the public call after its uploads, the landmark front end after
+// k_dlm_decide): the pending rows carried or applied, then the one launch; behind e0
+void init_block_launch(ekf_dense64_s* d, int first, int r, int s, bool have_W, bool have_xb) {
+    const IniInView in = view(d->ini_in, L::ini_in_layout());
+    d->carry_or_flush([&](const PendView& p) {
+        ekf::launch_dense64_panel_map(p.K, p.T, d->pend_rows, in.G, s > 0 ? in.cols : nullptr, d->ld, first, r, s, d->stream);
+    });
+    ekf::launch_dense64_init(d->S, d->x, in.cols, in.G, have_W ? in.W : nullptr, have_xb ? in.xb : nullptr, d->live, d->ld,
+                             first, r, s, d->stream);
+}
+
+ekf_status dense64_state_block(const char* name, ekf_dense64_s* d, int first, int count, double* out, const double* x) {
+    if (!d) return fail(EKF_ERR_INVALID, std::string(name) + ": null handle");
+    if ((!out && !x) || count < 1 || first < 0 || count > d->N || first > d->N - count)
+        return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
+    HIPC(hipSetDevice(d->device));
+    if (out) HIPC(hipMemcpyAsync(out, d->x + first, sizeof(double) * count, hipMemcpyDeviceToHost, d->stream));
+    else HIPC(hipMemcpyAsync(d->x + first, x, sizeof(double) * count, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+
+ekf::Params landmark_params(const ekf_params* params) {
+    ekf_params p;
+    ekf_default_params(&p);
+    if (params) p = *params;
+    return ekf::Params{p.sigma0_landmark, p.q_pose, p.r_meas, p.gate_new, p.gate_update, p.straight_eps};
+}
+
+}  // namespace
+
+extern "C" {
+
+ekf_status ekf_dense64_set_state(ekf_dense64_handle d, const double* x) {
+    if (!d || !x) return fail(EKF_ERR_INVALID, "ekf_dense64_set_state: null argument");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipMemcpyAsync(d->x, x, sizeof(double) * d->N, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+ekf_status ekf_dense64_get_state(ekf_dense64_handle d, double* out) {
+    if (!d || !out) return fail(EKF_ERR_INVALID, "ekf_dense64_get_state: null argument");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipMemcpyAsync(out, d->x, sizeof(double) * d->N, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+ekf_status ekf_dense64_get_state_block(ekf_dense64_handle d, int first, int count, double* out) {
+    return dense64_state_block("ekf_dense64_get_state_block", d, first, count, out, nullptr);
+}
+ekf_status ekf_dense64_set_state_block(ekf_dense64_handle d, int first, int count, const double* x) {
+    return dense64_state_block("ekf_dense64_set_state_block", d, first, count, nullptr, x);
+}
+
+// One correction: the operands go up (H twice: as given, zero padded to ld, and transposed with m rounded up to 16), the six
+// launches are timed by the handle's events, the verdict and nis come back in one copy.
+ekf_status ekf_dense64_correct(ekf_dense64_handle d, int m, const double* H, const double* R, const double* nu,
+                               double* nis_out, double* elapsed_ms) {
+    if (!d || !H || !R || m < 1 || m > kMaxM || m > d->N || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_correct: bad argument");
+    HIPC(hipSetDevice(d->device));
+    const int N = d->N, ld = d->ld;
+    const L::CorrInLayout l = L::corr_in_layout(ld);
+    const int mp = round_up(m, 16);   // row length of the transposed copy
+    d->host_in.assign(l.bytes / sizeof(double), 0.0);
+    const CorrInView h = view(d->host_in.data(), l), in = view(d->corr_in, l);
+    for (int k = 0; k < m; k++)
+        for (int j = 0; j < N; j++) {
+            const double v = H[(size_t)k * N + j];
+            h.H[(size_t)k * ld + j] = v;
+            h.Ht[(size_t)j * mp + k] = v;
+        }
+    std::memcpy(h.R, R, sizeof(double) * m * m);
+    if (nu) std::memcpy(h.nu, nu, sizeof(double) * m);
+    HIPC(hipMemcpyAsync(in.H, h.H, sizeof(double) * m * ld, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(in.Ht, h.Ht, sizeof(double) * ld * mp, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(in.R, h.R, l.bytes - l.R, hipMemcpyHostToDevice, d->stream));   // R and nu, adjacent
+    const CorrOutView out = view(d->corr_out, L::corr_out_layout());
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_correct(d->pl_full, d->S, d->x, d->workspace(), in.H, in.Ht, in.R, nu ? in.nu : nullptr, m, out.nis,
+                                out.verdict, d->stream);
+    double nis = 0.0;
+    int verdict = 0;
+    EKFC(finish_correction(d, elapsed_ms, &nis, &verdict));
+    if (verdict != 0)
+        return fail(EKF_ERR_STATE, "ekf_dense64_correct: H Sigma H^T + R is singular or not finite (zero or non-finite "
+                                   "pivot); state and Sigma are unchanged");
+    if (nis_out) *nis_out = nis;
+    return EKF_OK;
+}
+
+// Scoring of J candidates.  The Jacobians go straight from the caller's array into their row groups on the device (one
+// strided copy when m divides 64, one per group otherwise); the outputs come straight back into the caller's arrays.
+ekf_status ekf_dense64_score(ekf_dense64_handle d, int J, int m, const double* H, const double* R, int r_shared,
+                             const double* nu, double* nis_out, double* S_out, int* flag_out, double* elapsed_ms) {
+    const char *fn = "ekf_dense64_score", *what = "the candidates' buffers";
+    if (!d || !H || !R || J < 1 || m < 1 || m > kMaxM || m > d->N || (long long)J * m > kScoreRows ||
+        (nis_out && !nu) || (!nis_out && !S_out && !flag_out))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score: bad argument");
+    HIPC(hipSetDevice(d->device));
+    const int N = d->N, ld = d->ld;
+    const ekf::Dense64ScorePlan sp = ekf::dense64_score_plan(N, ld, J, m);
+    const bool own_ws = sp.spart_doubles > (size_t)ld * ld;   // else the product buffer, dead between propagations
+    if (!d->sc_small.p) {
+        const hipError_t e = ekf::dense64_score_prepare();
+        if (e != hipSuccess) return DeviceBuf::refuse(e, fn, what);
+    }
+    EKFC(d->sc_small.reserve(L::sc_small_layout().bytes, d->stream, false, fn, what));
+    EKFC(d->sc_H.reserve(sizeof(double) * sp.h_doubles, d->stream, true, fn, what));
+    if (own_ws) EKFC(d->sc_ws.reserve(sizeof(double) * sp.spart_doubles, d->stream, false, fn, what));
+    const size_t mm = (size_t)m * m, w = sizeof(double) * N;
+    const int per = sp.cpg * m;   // rows of a full group
+    double* Hs = d->sc_H.as<double>();
+    if (per == ekf::kDense64ScoreGroup) {
+        HIPC(hipMemcpy2DAsync(Hs, sizeof(double) * ld, H, w, w, (size_t)J * m, hipMemcpyHostToDevice, d->stream));
+    } else {
+        for (int g = 0; g < sp.n_groups; g++) {
+            const int rows = std::min(sp.cpg, J - g * sp.cpg) * m;
+            HIPC(hipMemcpy2DAsync(Hs + (size_t)g * ekf::kDense64ScoreGroup * ld, sizeof(double) * ld,
+                                  H + (size_t)g * per * N, w, w, rows, hipMemcpyHostToDevice, d->stream));
+        }
+    }
+    const ScSmallView sm = view(d->sc_small.p, L::sc_small_layout());
+    HIPC(hipMemcpyAsync(sm.R, R, sizeof(double) * (r_shared ? mm : J * mm), hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(sm.nu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_score(sp, d->S, Hs, own_ws ? d->sc_ws.as<double>() : d->T, sm.R, r_shared ? 1 : 0,
+                              nu ? sm.nu : nullptr, J, m, nis_out ? sm.nis : nullptr, sm.S, sm.flag, d->stream);
+    return finish_timed(d, elapsed_ms, {{nis_out, sm.nis, sizeof(double) * J},
+                                        {S_out, sm.S, sizeof(double) * J * mm},
+                                        {flag_out, sm.flag, sizeof(int) * J}});
+}
+
+// The block-structured prediction: Fr, Qr and dx go up, one launch, timed by the handle's events.  The pending rows go
+// through the same congruence when the handle carries them (ekf_dense64_carry.hip).  The stored F and Q are not involved.
+ekf_status ekf_dense64_propagate_block(ekf_dense64_handle d, int first, int r, const double* Fr, const double* Qr,
+                                       const double* dx, double* elapsed_ms) {
+    if (!d || !Fr || r < 1 || r > kMaxR || first < 0 || r > d->live || first > d->live - r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_propagate_block: bad argument (the block must lie inside the live dimension)");
+    HIPC(hipSetDevice(d->device));
+    const BlkInView in = view(d->blk_in, L::blk_in_layout());
+    const size_t rr = sizeof(double) * r * r;
+    HIPC(hipMemcpyAsync(in.Fr, Fr, rr, hipMemcpyHostToDevice, d->stream));
+    if (Qr) HIPC(hipMemcpyAsync(in.Qr, Qr, rr, hipMemcpyHostToDevice, d->stream));
+    if (dx) HIPC(hipMemcpyAsync(in.dx, dx, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->carry_or_flush([&](const PendView& p) {
+        ekf::launch_dense64_panel_map(p.K, p.T, d->pend_rows, in.Fr, nullptr, d->ld, first, r, r, d->stream);
+    });
+    ekf::launch_dense64_block(d->S, d->x, in.Fr, Qr ? in.Qr : nullptr, dx ? in.dx : nullptr, d->live, d->ld, first, r,
+                              d->stream);
+    return finish_timed(d, elapsed_ms);
+}
+
+ekf_status ekf_dense64_correct_sparse(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
+                                      const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    return dense64_correct_sparse(d, false, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+}
+ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
+                                               const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
+    return dense64_correct_sparse(d, true, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+}
+
+ekf_status ekf_dense64_flush(ekf_dense64_handle d, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_flush: null handle");
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (d->pend_rows == 0) return EKF_OK;
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    return finish_timed(d, elapsed_ms);
+}
+ekf_status ekf_dense64_pending(ekf_dense64_handle d, int* rows) {
+    if (!d || !rows) return fail(EKF_ERR_INVALID, "ekf_dense64_pending: null argument");
+    *rows = d->pend_rows;
+    return EKF_OK;
+}
+ekf_status ekf_dense64_set_carry(ekf_dense64_handle d, int on) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_set_carry: null handle");
+    d->carry = on ? 1 : 0;
+    return EKF_OK;
+}
+ekf_status ekf_dense64_get_carry(ekf_dense64_handle d, int* on) {
+    if (!d || !on) return fail(EKF_ERR_INVALID, "ekf_dense64_get_carry: null argument");
+    *on = d->carry;
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_score_sparse(ekf_dense64_handle d, int J, int m, int s, const int* cols, const double* Hc,
+                                    const double* R, int r_shared, const double* nu, double* nis_out, double* S_out,
+                                    int* flag_out, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: null handle");
+    if (!cols || !Hc || !R || J < 1 || m < 1 || m > kMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live ||
+        (long long)J * m > kSparseRows || (nis_out && !nu) || (!nis_out && !S_out && !flag_out))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: bad argument");
+    if (!index_lists_ok(d->host_stamp, d->live, J, s, cols))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_sparse: every row of cols must hold distinct indices in [0, N), "
+                                     "below the live dimension");
+    HIPC(hipSetDevice(d->device));
+    const size_t mm = (size_t)m * m;
+    const L::SpsLayout l = L::sps_layout(J, m, s, r_shared != 0, S_out != nullptr);
+    EKFC(sps_reserve(d, l.bytes, "ekf_dense64_score_sparse"));
+    const SpsView v = view(d->sps.p, l, S_out != nullptr);
+    HIPC(hipMemcpyAsync(v.Hc, Hc, sizeof(double) * J * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(v.R, R, sizeof(double) * (r_shared ? mm : J * mm), hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(v.nu, nu, sizeof(double) * J * m, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(v.cols, cols, sizeof(int) * J * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    score_sparse_launch(d, v, J, m, s, r_shared != 0, nu != nullptr, nis_out != nullptr);
+    return finish_timed(d, elapsed_ms, {{nis_out, v.nis, sizeof(double) * J},
+                                        {S_out, v.S, sizeof(double) * J * mm},
+                                        {flag_out, v.flag, sizeof(int) * J}});
+}
+
+// G, W, xb and the list go up into the buffer allocated with the handle, one launch, timed by the handle's events.  The
+// stored F and Q of the handle are not involved.
+ekf_status ekf_dense64_init_block(ekf_dense64_handle d, int first, int r, int s, const int* cols, const double* G,
+                                  const double* W, const double* xb, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: null handle");
+    if (r < 1 || r > kMaxR || r > d->live || first < 0 || first > d->live - r || s < 0 || s > kMaxS || s > d->live - r ||
+        (s > 0 && (!cols || !G)))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: bad argument (the block must lie inside the live dimension)");
+    if (s > 0) {
+        if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
+            return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: cols must hold distinct indices in [0, N), below the live "
+                                         "dimension");
+        for (int k = 0; k < s; k++)
+            if (cols[k] >= first && cols[k] < first + r)
+                return fail(EKF_ERR_INVALID, "ekf_dense64_init_block: no index of cols may lie inside [first, first + r) "
+                                             "(the in-place case is ekf_dense64_propagate_block)");
+    }
+    HIPC(hipSetDevice(d->device));
+    const IniInView in = view(d->ini_in, L::ini_in_layout());
+    if (s > 0) {
+        HIPC(hipMemcpyAsync(in.G, G, sizeof(double) * r * s, hipMemcpyHostToDevice, d->stream));
+        HIPC(hipMemcpyAsync(in.cols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    }
+    if (W) HIPC(hipMemcpyAsync(in.W, W, sizeof(double) * r * r, hipMemcpyHostToDevice, d->stream));
+    if (xb) HIPC(hipMemcpyAsync(in.xb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    init_block_launch(d, first, r, s, W != nullptr, xb != nullptr);
+    return finish_timed(d, elapsed_ms);
+}
+
+// The exchange of two blocks: nothing goes up.  The pending rows take the same permutation (a congruence with A = P) when
+// the handle carries them, and are applied first otherwise.
+ekf_status ekf_dense64_swap_blocks(ekf_dense64_handle d, int first_a, int first_b, int r, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: null handle");
+    if (r < 1 || r > kMaxR || r > d->live || first_a < 0 || first_b < 0 || first_a > d->live - r || first_b > d->live - r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: bad argument (both blocks must lie inside the live dimension)");
+    if (std::abs(first_a - first_b) < r)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: the blocks must be disjoint, |first_a - first_b| >= r");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->carry_or_flush([&](const PendView& p) {
+        ekf::launch_dense64_panel_swap(p.K, p.T, d->pend_rows, d->ld, first_a, first_b, r, d->stream);
+    });
+    ekf::launch_dense64_swap(d->S, d->x, d->live, d->ld, first_a, first_b, r, d->stream);
+    return finish_timed(d, elapsed_ms);
+}
+
+// out[a][c] = Sigma[rows[a]][cols[c]]: the two lists go up, one gather launch into the handle's buffer, one copy back.
+ekf_status ekf_dense64_get_sigma_block(ekf_dense64_handle d, int nr, const int* rows, int nc, const int* cols,
+                                       double* out) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: null handle");
+    if (!rows || !cols || !out || nr < 1 || nc < 1 || (long long)nr * nc > kReadMax)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: bad argument");
+    for (int a = 0; a < nr; a++)
+        if (rows[a] < 0 || rows[a] >= d->N)
+            return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: every index of rows must lie in [0, N)");
+    for (int c = 0; c < nc; c++)
+        if (cols[c] < 0 || cols[c] >= d->N)
+            return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: every index of cols must lie in [0, N)");
+    HIPC(hipSetDevice(d->device));
+    const RdBufView rd = view(d->rd_buf, L::rd_buf_layout());
+    HIPC(hipMemcpyAsync(rd.rows, rows, sizeof(int) * nr, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(rd.cols, cols, sizeof(int) * nc, hipMemcpyHostToDevice, d->stream));
+    if (d->carries()) {   // Sigma_cur through the pending rows; read-only
+        const PendView p = d->panels();
+        ekf::launch_dense64_read_block_deferred(d->S, p.K, p.T, d->pend_rows, rd.rows, rd.cols, rd.out, nr, nc, d->ld, d->N,
+                                                d->live, d->stream);
+    } else {
+        d->flush_pending();
+        ekf::launch_dense64_read_block(d->S, rd.rows, rd.cols, rd.out, nr, nc, d->ld, d->stream);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out, rd.out, sizeof(double) * nr * nc, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+
+// The live dimension.  Growing: a pending row is zero on [old, ld) whatever the panels hold there from wider calls, so those
+// columns of the p waiting rows of both panels are set to zero -- up to the new width rounded up to 128, what the calls of
+// that width keep zero -- and nothing is flushed.  Shrinking: the rows have support up to the old width, so they are applied
+// first, at the old width.
+ekf_status ekf_dense64_set_live(ekf_dense64_handle d, int Na) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_set_live: null handle");
+    if (Na < 1 || Na > d->N) return fail(EKF_ERR_INVALID, "ekf_dense64_set_live: the live dimension must lie in [1, N]");
+    if (Na == d->live) return EKF_OK;
+    if (d->pend_rows > 0) {
+        HIPC(hipSetDevice(d->device));
+        if (Na < d->live) {
+            d->flush_pending();
+        } else {
+            const int upto = std::min(d->ld, round_up(Na, ekf::kDenseTile));
+            const PendView p = d->panels();
+            for (double* panel : {p.K, p.T})
+                HIPC(hipMemset2DAsync(panel + d->live, sizeof(double) * d->ld, 0, sizeof(double) * (upto - d->live),
+                                      d->pend_rows, d->stream));
+        }
+        HIPC(hipGetLastError());
+        HIPC(hipStreamSynchronize(d->stream));
+    }
+    d->live = Na;
+    d->pl_live = ekf::dense64_live_plan(d->pl_full, Na);
+    return EKF_OK;
+}
+ekf_status ekf_dense64_get_live(ekf_dense64_handle d, int* Na) {
+    if (!d || !Na) return fail(EKF_ERR_INVALID, "ekf_dense64_get_live: null argument");
+    *Na = d->live;
+    return EKF_OK;
+}
+
+// One streaming launch over the two rectangles; the two result words sit where a correction's nis and verdict do.
+ekf_status ekf_dense64_coupling(ekf_dense64_handle d, int Na, long long* nonzero, double* max_abs, double* elapsed_ms) {
+    if (!d || !nonzero) return fail(EKF_ERR_INVALID, "ekf_dense64_coupling: null argument");
+    if (Na < 1 || Na > d->N) return fail(EKF_ERR_INVALID, "ekf_dense64_coupling: Na must lie in [1, N]");
+    HIPC(hipSetDevice(d->device));
+    static_assert(sizeof(unsigned long long) == sizeof(double), "two words in corr_out");
+    unsigned long long out[2] = {0, 0};
+    HIPC(hipMemsetAsync(d->corr_out, 0, sizeof(out), d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_coupling(d->S, d->N, d->ld, Na, view(d->corr_out, L::corr_out_layout()).words, d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
+    *nonzero = (long long)out[0];
+    if (max_abs) std::memcpy(max_abs, &out[1], sizeof(double));
+    return EKF_OK;
+}
+
+// ---- the landmark front end: the reference's model and decision rule on the handle's own state -------------------------
+// calculate_maha_dis (:217-276) of one reading: k_dlm_terms writes the operands through the view the uploads of score_sparse
+// use, then that call's one launch; everything asked for comes back behind the one synchronisation.
+ekf_status ekf_dense64_score_landmarks(ekf_dense64_handle d, const ekf_params* params, double sx, double sy, int first_lm,
+                                       int count, double* nis_out, double* S_out, int* flag_out, int* cols_out,
+                                       double* Hc_out, double* nu_out, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_score_landmarks: null handle");
+    if (count < 1 || count > kSparseRows / 2 || first_lm < 0 || 3 + 2 * ((long long)first_lm + count) > d->live ||
+        (!nis_out && !S_out && !flag_out))
+        return fail(EKF_ERR_INVALID, "ekf_dense64_score_landmarks: bad argument (the landmarks must lie inside the live "
+                                     "dimension)");
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    const L::SpsLayout l = L::sps_layout(count, 2, 5, true, S_out != nullptr);
+    EKFC(sps_reserve(d, l.bytes, "ekf_dense64_score_landmarks"));
+    const SpsView v = view(d->sps.p, l, S_out != nullptr);
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_lm_terms(d->x, sx, sy, first_lm, count, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+    score_sparse_launch(d, v, count, 2, 5, true, true, nis_out != nullptr);
+    return finish_timed(d, elapsed_ms, {{nis_out, v.nis, sizeof(double) * count},
+                                        {S_out, v.S, sizeof(double) * count * 4},
+                                        {flag_out, v.flag, sizeof(int) * count},
+                                        {cols_out, v.cols, sizeof(int) * count * 5},
+                                        {Hc_out, v.Hc, sizeof(double) * count * 10},
+                                        {nu_out, v.nu, sizeof(double) * count * 2}});
+}
+
+// data_association (:278-402) for J readings.  Per reading: [terms | score | decide] and the 32-byte record back (the first
+// synchronisation); then, as the record says, [init_block] [terms of the winner, wrapped | correction | heading wrap] and
+// the correction's own synchronisation.  Nothing of the state comes down and no candidate array goes up.
+ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy,
+                                           int n_max, int* known, unsigned flags, int* assoc_out, double* best_out,
+                                           double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_associate_landmarks";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (J < 1) return fail(EKF_ERR_INVALID, fn + ": J must be at least 1");
+    if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
+        return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
+    if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
+    if (3 + 2 * *known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
+    if (flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
+        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    for (int j = 0; j < J; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+    }
+    HIPC(hipSetDevice(d->device));
+    EKFC(d->lm_rec.reserve(sizeof(ekf::Dense64LmRecord), d->stream, false, fnc, "the decision record"));
+    if (deferred) EKFC(pend_reserve(d, fnc));
+    // the scoring buffer once, for the full map: a map that is being discovered must not pay a hipMalloc and a hipFree
+    // (a device synchronisation) per new landmark
+    if (n_max > 0) EKFC(sps_reserve(d, L::sps_layout(n_max, 2, 5, true, false).bytes, fnc));
+    ekf::Dense64LmRecord* drec = d->lm_rec.as<ekf::Dense64LmRecord>();
+    const IniInView ini = view(d->ini_in, L::ini_in_layout());
+    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    double total = 0.0, ms = 0.0;
+    double* pms = elapsed_ms ? &ms : nullptr;
+    // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
+    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    for (int j = 0; j < J; j++) {
+        const double sx = meas_xy[2 * j], sy = meas_xy[2 * j + 1];
+        const int k = *known;
+        SpsView v{};
+        if (k > 0) v = view(d->sps.p, L::sps_layout(k, 2, 5, true, false), false);   // (k <= n_max: inside the buffer)
+        HIPC(hipEventRecord(d->e0, d->stream));
+        if (k > 0) {
+            ekf::launch_dense64_lm_terms(d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+            score_sparse_launch(d, v, k, 2, 5, true, true, true);
+        }
+        ekf::launch_dense64_lm_decide(v.nis, k, k, n_max, p.gate_new, p.gate_update, p.sigma0_landmark, d->x, sx, sy, drec,
+                                      ini.W, ini.xb, d->stream);
+        ekf::Dense64LmRecord rec{};
+        EKFC(leg(finish_timed(d, pms, {{&rec, drec, sizeof(rec)}})));
+        if (best_out) best_out[j] = rec.best;
+        if (rec.kind == 0) {   // dropped: nothing at all is written
+            if (assoc_out) assoc_out[j] = -1;
+            continue;
+        }
+        const bool fresh_lm = (rec.kind & ekf::kDense64LmNew) != 0, corrects = (rec.kind & ekf::kDense64LmCorrect) != 0;
+        if (fresh_lm && 3 + 2 * (k + 1) > d->live) {
+            if (!(flags & EKF_DENSE64_LM_GROW_LIVE))
+                return fail(EKF_ERR_INVALID, fn + ": a new landmark does not fit the live dimension (grow it with "
+                                                  "ekf_dense64_set_live, or pass EKF_DENSE64_LM_GROW_LIVE)");
+            EKFC(ekf_dense64_set_live(d, 3 + 2 * (k + 1)));
+        }
+        HIPC(hipEventRecord(d->e0, d->stream));
+        if (fresh_lm) init_block_launch(d, 3 + 2 * k, 2, 0, true, true);   // s = 0, W = sigma0 I, xb
+        if (!corrects) {   // (a gate_update <= 0: the landmark is initialised and not corrected)
+            EKFC(leg(finish_timed(d, pms)));
+            *known = k + 1;
+            if (assoc_out) assoc_out[j] = -1;
+            continue;
+        }
+        // the winner's operands from the current state, that is after an initialisation; the innovation wrapped (:183)
+        ekf::launch_dense64_lm_terms(d->x, sx, sy, rec.win, 1, 1, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
+        correct_sparse_launch(d, deferred, 2, 5, true);
+        ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
+        if (assoc_out) assoc_out[j] = -1;
+        // (a refused correction's launches ran and were timed)
+        const ekf_status st = leg(correct_sparse_finish(d, fnc, deferred, 2, nullptr, pms));
+        if (fresh_lm && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + 1;   // the initialisation stands
+        if (st != EKF_OK) return st;
+        if (assoc_out) assoc_out[j] = rec.win;
+    }
+    return EKF_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,11 @@
-// ekf_dense.hpp -- launcher of the fp32 MFMA GEMM used by the dense covariance propagation.
+// ekf_dense.hpp -- the launchers of the dense handles' kernels: the fp32 MFMA GEMM of the dense covariance propagation
+// (ekf_dense.hip), its fp64 twin (ekf_dense64.hip), and every other kernel file of the fp64 handle (ekf_dense64_*.hip), one
+// section each.  The limits of the fp64 calls (kDense64Max*) come from ekf_dense64_layout.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+
+#include "ekf_dense64_layout.hpp"
 
 namespace ekf {
 constexpr int kDenseTile = 128;  // ld must be a multiple of this
@@ -29,7 +33,6 @@ hipError_t dense64_gemm_prepare();  // raises the dynamic-LDS limit of the main 
 
 // ---- fp64 dense measurement update for a general m x N Jacobian (ekf_dense64_correct.hip), on the same ld x ld Sigma:
 //   T = H Sigma, U = Sigma H^T, S = T H^T + R, K = U S^-1, state += K nu, Sigma <- Sigma - K T, nis = nu^T S^-1 nu.
-constexpr int kDense64MaxM = 64;   // EKF_DENSE64_MAX_M
 // How one correction of an N x N covariance is cut, and where its panels sit in the workspace (offsets in doubles).
 struct Dense64CorrectPlan {
     int N, ld;
@@ -55,7 +58,6 @@ void launch_dense64_correct(const Dense64CorrectPlan& pl, double* Sigma, double*
 // ---- fp64 batched scoring of J candidate measurements (ekf_dense64_score.hip), read-only on the same Sigma:
 //   S_j = (H_j Sigma) H_j^T + R_j, nis_j = nu_j^T S_j^-1 nu_j, flag_j = S_j singular or not finite.
 constexpr int kDense64ScoreGroup = 64;      // rows of stacked Jacobians per row group; candidates are packed whole
-constexpr int kDense64ScoreMaxRows = 2048;  // EKF_DENSE64_SCORE_MAX_ROWS
 struct Dense64ScorePlan {
     Dense64CorrectPlan panels;   // strips / chunks of the pass over Sigma: those of the correction, a function of (N, ld)
     int cpg, n_groups;           // candidates per group = 64 / m, groups = ceil(J / cpg)
@@ -76,7 +78,6 @@ void launch_dense64_score(const Dense64ScorePlan& sp, const double* Sigma, const
 // ---- fp64 block-structured prediction (ekf_dense64_block.hip) on the same Sigma and state: F = identity with the r x r
 // Jacobian Fr in [first, first + r)^2, Q = zero with Qr in the same square.  One launch of 1 + 2 ceil(N / 64) workgroups
 // (the corner, the row panel and the column panel in strips of 64); touches nothing outside the block's rows and columns.
-constexpr int kDense64MaxR = 64;   // EKF_DENSE64_MAX_R
 size_t dense64_block_lds_bytes(int r);   // dynamic LDS of the launch: one r x 64 tile, 32.5 KiB at r = 64
 hipError_t dense64_block_prepare();      // nothing to raise at that size; kept so that every dense64 kernel file has one
 // Fr: r x r row-major, Qr: r x r or NULL, dx: r or NULL (state untouched), all on the device; 1 <= r <= 64,
@@ -89,9 +90,6 @@ void launch_dense64_block(double* Sigma, double* state, const double* Fr, const 
 // deferred: p <= 64 pending rows of two panels [64][ld], Kp[q][i] = K[i][q] and Tq[q][j] = T[q][j], stand for
 // Sigma_cur = Sigma - sum_{q < p} Kp[q]^T Tq[q]; the correction and the scoring read through them,
 // x = fma(-Kp[q][row], Tq[q][col], x) in ascending q before the dot products, and Sigma is rewritten once per flush.
-constexpr int kDense64MaxS = 64;                     // EKF_DENSE64_MAX_S
-constexpr int kDense64ScoreSparseMaxRows = 65536;    // EKF_DENSE64_SCORE_SPARSE_MAX_ROWS
-constexpr int kDense64PendingMaxRows = 64;           // EKF_DENSE64_PENDING_MAX_ROWS
 // raises the dynamic-LDS limits of both forms (gather 64.8 / 128.8 KiB, scoring up to 98.8 / 114.8 KiB)
 hipError_t dense64_sparse_prepare();
 // One launch: per candidate S_j = (Hc_j Sigma_cur[cols_j, cols_j]) Hc_j^T + R_j, flag_j, nis_j.  All pointers on the device:
@@ -129,7 +127,6 @@ void launch_dense64_flush(const Dense64CorrectPlan& pl, double* Sigma, const dou
 // and F[b, cols] = G, Q = zero with W in the block's square.  One launch of 1 + 2 ceil(N / 64) workgroups (the corner, the
 // row panel and the column panel in strips of 64); reads rows cols and columns cols outside b only (nothing at s = 0),
 // writes the block's rows and columns only.
-constexpr int kDense64ReadMax = 65536;   // EKF_DENSE64_READ_MAX: entries of one block readout
 size_t dense64_init_lds_bytes(int r, int s);   // dynamic LDS of the launch: 64.8 KiB at r = s = 64, none at s = 0
 hipError_t dense64_init_prepare();             // raises the dynamic-LDS limit to that
 // cols [s] (distinct, in [0, N), none in b: the launcher does not check), G: r x s row-major, both unused at s = 0;

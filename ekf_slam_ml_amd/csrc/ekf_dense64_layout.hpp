@@ -1,0 +1,62 @@
+// ekf_dense64_layout.hpp -- where every operand of the fp64 dense handle (ekf_dense64_s, ekf_dense_handle.hpp) sits inside
+// its device buffer: per buffer one function of what the layout depends on, returning byte offsets from the buffer's start
+// and the total size.  Pure arithmetic, nothing from HIP: tests/cpp/dense64_layout_dump.cpp prints every layout on a CPU
+// and tests/test_dense64_layout_host.py checks offsets, overlap and alignment.  The kernels rely on these offsets (16-byte
+// boundaries of Hc and nu, f64x4 reads); the typed pointers made from them are the views of ekf_dense_handle.hpp.
+#pragma once
+#include <stddef.h>
+
+namespace ekf {
+// the limits of the handle's calls (include/ekfslam.h: EKF_DENSE64_*)
+constexpr int kDense64MaxM = 64;                     // rows of one correction's Jacobian
+constexpr int kDense64ScoreMaxRows = 2048;           // J * m of one dense scoring call
+constexpr int kDense64MaxR = 64;                     // states of one block
+constexpr int kDense64MaxS = 64;                     // listed columns of a sparse Jacobian
+constexpr int kDense64ScoreSparseMaxRows = 65536;    // J * m of one sparse scoring call
+constexpr int kDense64PendingMaxRows = 64;           // rows of K and T that wait for the flush
+constexpr int kDense64ReadMax = 65536;               // entries of one block readout
+
+namespace d64 {
+constexpr size_t kF = sizeof(double), kI = sizeof(int), kM = kDense64MaxM, kR = kDense64MaxR, kS = kDense64MaxS;
+
+// corr_in as the dense correction sees it: H [64][ld] | H^T [ld][m rounded up to 16] (room for 64) | R [64 * 64] | nu [64]
+struct CorrInLayout { size_t H, Ht, R, nu, bytes; };
+inline CorrInLayout corr_in_layout(int ld) { const size_t Ht = kF * kM * ld, R = 2 * Ht, nu = R + kF * kM * kM; return {0, Ht, R, nu, nu + kF * kM}; }
+// ... and as the sparse correction sees it: Hc [64][64] and the list [64] behind it where H would sit (64 ld >= 8192), R and
+// nu in their usual places
+struct CorrSparseLayout { size_t Hc, cols, R, nu, bytes; };
+inline CorrSparseLayout corr_sparse_layout(int ld) { const CorrInLayout d = corr_in_layout(ld); return {0, kF * kM * kS, d.R, d.nu, d.bytes}; }
+// corr_out: nis | verdict (an int in the second double); the two 64-bit words of the coupling count sit on the same two
+struct CorrOutLayout { size_t nis, verdict, bytes; };
+inline CorrOutLayout corr_out_layout() { return {0, kF, 2 * kF}; }
+// sc_small: R [2048 * 64] | nu [2048] | nis [2048] | S [2048 * 64] | flags (ints) [2048]
+struct ScSmallLayout { size_t R, nu, nis, S, flag, bytes; };
+inline ScSmallLayout sc_small_layout() {
+    const size_t rows = kDense64ScoreMaxRows, nu = kF * rows * kM, nis = nu + kF * rows, S = nis + kF * rows,
+                 flag = S + kF * rows * kM;
+    return {0, nu, nis, S, flag, flag + kF * (rows / 2)};
+}
+// blk_in: Fr [64 * 64] | Qr [64 * 64] | dx [64]
+struct BlkInLayout { size_t Fr, Qr, dx, bytes; };
+inline BlkInLayout blk_in_layout() { return {0, kF * kR * kR, 2 * kF * kR * kR, 2 * kF * kR * kR + kF * kR}; }
+// ini_in: G [64 * 64] | W [64 * 64] | xb [64] | cols (ints) [64]
+struct IniInLayout { size_t G, W, xb, cols, bytes; };
+inline IniInLayout ini_in_layout() { const size_t W = kF * kR * kS, xb = W + kF * kR * kR, cols = xb + kF * kR; return {0, W, xb, cols, cols + kF * (kS / 2)}; }
+// rd_buf: out [65536] | rows (ints) [65536] | cols (ints) [65536]
+struct RdBufLayout { size_t out, rows, cols, bytes; };
+inline RdBufLayout rd_buf_layout() { const size_t n = kDense64ReadMax, rows = kF * n, cols = rows + kF * (n / 2); return {0, rows, cols, cols + kF * (n / 2)}; }
+// the pending panels: K^T [64][ld] | T [64][ld] | a word kept at zero (the flush's verdict argument)
+struct PendLayout { size_t K, T, zero, bytes; };
+inline PendLayout pend_layout(int ld) { const size_t T = kF * kDense64PendingMaxRows * ld; return {0, T, 2 * T, 2 * T + 2 * kF}; }
+// the one buffer of a sparse scoring call, cut per call: Hc | R | nu | nis | S | cols (ints) | flags (ints), every region
+// on a 16-byte boundary, S only when it is asked for
+struct SpsLayout { size_t Hc, R, nu, nis, S, cols, flag, bytes; };
+inline SpsLayout sps_layout(int J, int m, int s, bool r_shared, bool want_S) {
+    const size_t mm = (size_t)m * m, al = 16;
+    auto up = [&](size_t b) { return (b + al - 1) / al * al; };
+    const size_t R = up(kF * J * m * s), nu = R + up(kF * (r_shared ? mm : J * mm)), nis = nu + up(kF * J * m),
+                 S = nis + up(kF * J), cols = S + (want_S ? up(kF * J * mm) : 0), flag = cols + up(kI * J * s);
+    return {0, R, nu, nis, S, cols, flag, flag + up(kI * J)};
+}
+}  // namespace d64
+}  // namespace ekf

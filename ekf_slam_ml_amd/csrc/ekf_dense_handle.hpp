@@ -1,0 +1,155 @@
+// ekf_dense_handle.hpp -- the two dense handles behind include/ekfslam.h, shared by ekf_capi_dense.hip (the fp32 entry
+// points and the templates over the element type) and ekf_capi_dense64.hip (everything only the fp64 handle has).  The
+// templates reach what is particular to a handle through four hooks -- created, destroying, sigma_needed, sigma_replaced --
+// which are empty for fp32.  Also here: DeviceBuf, the one way a buffer is allocated after creation, the typed views of the
+// layouts of ekf_dense64_layout.hpp, and the end of a timed entry point.
+#pragma once
+#include "ekf_runtime.hpp"
+
+namespace ekfrt {
+
+// A device buffer that is allocated on first use and grows: nothing happens when it is large enough already; otherwise the
+// new buffer is allocated into a local (and zeroed on the stream), the old one is freed (which synchronises: no call is in
+// flight) and the members change only when everything succeeded.
+struct DeviceBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    static ekf_status refuse(hipError_t e, const char* fn, const char* what) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
+                    std::string(fn) + ": " + hipGetErrorString(e) + " while reserving " + what);
+    }
+    ekf_status reserve(size_t need, hipStream_t stream, bool zero_fill, const char* fn, const char* what) {
+        if (need <= bytes) return EKF_OK;
+        void* fresh = nullptr;
+        hipError_t e = hipMalloc(&fresh, need);
+        if (e == hipSuccess && zero_fill) e = hipMemsetAsync(fresh, 0, need, stream);
+        if (e != hipSuccess) {
+            if (fresh) {
+                (void)hipStreamSynchronize(stream);
+                (void)hipFree(fresh);
+            }
+            return refuse(e, fn, what);
+        }
+        if (p) (void)hipFree(p);
+        p = fresh;
+        bytes = need;
+        return EKF_OK;
+    }
+};
+
+template <class E>
+struct DenseHandle {
+    int device = -1, N = 0, ld = 0;
+    hipStream_t stream = nullptr;
+    E *F = nullptr, *S = nullptr, *T = nullptr, *Q = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    // the hooks of the shared templates; a handle with more than Sigma hides them with its own
+    ekf_status created() { return EKF_OK; }   // inside create, stream and Sigma exist: the handle's own buffers
+    void destroying() {}                      // inside destroy, the stream is idle: free them
+    void sigma_needed() {}                    // Sigma is about to be read or written in memory, inside the timed region
+    void sigma_replaced() {}                  // set() gave a new Sigma
+};
+
+// ---- typed views of the fp64 handle's operand buffers: a base pointer and a layout ---------------------------------------
+inline double* f64(void* base, size_t off) { return reinterpret_cast<double*>(static_cast<char*>(base) + off); }
+inline int* i32(void* base, size_t off) { return reinterpret_cast<int*>(static_cast<char*>(base) + off); }
+namespace L = ekf::d64;
+struct CorrInView { double *H, *Ht, *R, *nu; };
+inline CorrInView view(void* b, const L::CorrInLayout& l) { return {f64(b, l.H), f64(b, l.Ht), f64(b, l.R), f64(b, l.nu)}; }
+struct CorrSparseView { double* Hc; int* cols; double *R, *nu; };
+inline CorrSparseView view(void* b, const L::CorrSparseLayout& l) { return {f64(b, l.Hc), i32(b, l.cols), f64(b, l.R), f64(b, l.nu)}; }
+struct CorrOutView { double* nis; int* verdict; unsigned long long* words; };   // words: the coupling's two, on the same 16 bytes
+inline CorrOutView view(void* b, const L::CorrOutLayout& l) {
+    return {f64(b, l.nis), i32(b, l.verdict), reinterpret_cast<unsigned long long*>(f64(b, l.nis))};
+}
+struct ScSmallView { double *R, *nu, *nis, *S; int* flag; };
+inline ScSmallView view(void* b, const L::ScSmallLayout& l) { return {f64(b, l.R), f64(b, l.nu), f64(b, l.nis), f64(b, l.S), i32(b, l.flag)}; }
+struct BlkInView { double *Fr, *Qr, *dx; };
+inline BlkInView view(void* b, const L::BlkInLayout& l) { return {f64(b, l.Fr), f64(b, l.Qr), f64(b, l.dx)}; }
+struct IniInView { double *G, *W, *xb; int* cols; };
+inline IniInView view(void* b, const L::IniInLayout& l) { return {f64(b, l.G), f64(b, l.W), f64(b, l.xb), i32(b, l.cols)}; }
+struct RdBufView { double* out; int *rows, *cols; };
+inline RdBufView view(void* b, const L::RdBufLayout& l) { return {f64(b, l.out), i32(b, l.rows), i32(b, l.cols)}; }
+struct PendView { double *K, *T; const int* zero; };   // all null before the first deferred call
+inline PendView view(void* b, const L::PendLayout& l) {
+    return b ? PendView{f64(b, l.K), f64(b, l.T), i32(b, l.zero)} : PendView{nullptr, nullptr, nullptr};
+}
+struct SpsView { double *Hc, *R, *nu, *nis, *S; int *cols, *flag; };   // S null unless asked for
+inline SpsView view(void* b, const L::SpsLayout& l, bool want_S) {
+    return {f64(b, l.Hc), f64(b, l.R), f64(b, l.nu), f64(b, l.nis), want_S ? f64(b, l.S) : nullptr, i32(b, l.cols), i32(b, l.flag)};
+}
+
+// The end of a timed entry point: e1 behind the launches, the launch error, the copies back to the host (a null dst is
+// skipped), ONE synchronisation, the time between the handle's events.
+struct CopyBack { void* dst; const void* src; size_t bytes; };
+template <class H>
+ekf_status finish_timed(H* d, double* elapsed_ms, std::initializer_list<CopyBack> back = {}) {
+    HIPC(hipEventRecord(d->e1, d->stream));
+    HIPC(hipGetLastError());
+    for (const CopyBack& c : back)
+        if (c.dst) HIPC(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, d->e0, d->e1));
+        *elapsed_ms = ms;
+    }
+    return EKF_OK;
+}
+
+}  // namespace ekfrt
+
+struct ekf_dense_s : ekfrt::DenseHandle<float> {};
+
+struct ekf_dense64_s : ekfrt::DenseHandle<double> {
+    // allocated with the handle (created): the state vector, and the operands of the calls whose sizes are fixed
+    double* x = nullptr;         // [ld], zero beyond N
+    double* corr_in = nullptr;   // CorrInLayout (ekf_dense64_correct) or CorrSparseLayout (the sparse corrections)
+    double* corr_out = nullptr;  // CorrOutLayout
+    double* ws_own = nullptr;    // workspace of a handle too small for it to fit the product buffer T
+    double* blk_in = nullptr;    // BlkInLayout (ekf_dense64_propagate_block)
+    double* ini_in = nullptr;    // IniInLayout (ekf_dense64_init_block, the landmark front end)
+    double* rd_buf = nullptr;    // RdBufLayout (ekf_dense64_get_sigma_block)
+    // nothing until the first call that needs them; sc_H, sc_ws and sps grow with the calls
+    ekfrt::DeviceBuf sc_small;   // ScSmallLayout (ekf_dense64_score)
+    ekfrt::DeviceBuf sc_H;       // the stacked Jacobians, [groups * 64][ld], columns N .. ld zero
+    ekfrt::DeviceBuf sc_ws;      // the partial S blocks of a call that do not fit the product buffer T
+    ekfrt::DeviceBuf sps;        // SpsLayout (ekf_dense64_score_sparse, the landmark front end), cut per call
+    ekfrt::DeviceBuf pend;       // PendLayout (ekf_dense64_correct_sparse_deferred)
+    ekfrt::DeviceBuf lm_rec;     // ekf::Dense64LmRecord, the decision record of one reading (the landmark front end)
+    std::vector<double> host_in; // the dense correction's operands, packed for their three uploads
+    std::vector<int> host_stamp; // [N] the duplicate check of the index lists
+    int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
+    int carry = 0;               // ekf_dense64_set_carry: propagate_block, init_block, swap_blocks, get_sigma_block do not flush
+    // the live dimension (ekf_dense64_set_live): what the structured calls take for N; the plans change with it, not per call
+    int live = 0;                          // 1 .. N, N unless set
+    ekf::Dense64CorrectPlan pl_full{};     // of (N, ld): the dense correction, and the layout of the workspace
+    ekf::Dense64CorrectPlan pl_live{};     // of (live, ld) on that layout: the sparse corrections and the flush
+
+    ekf_status created();
+    void destroying();
+    void sigma_needed() { flush_pending(); }
+    void sigma_replaced() { pend_rows = 0; }   // the pending rows belonged to the covariance that was replaced
+
+    double* workspace() const { return ws_own ? ws_own : T; }   // (the product buffer is dead between propagations)
+    // ---- the pending rows: K and T of the deferred corrections, Sigma_cur = Sigma - K^T T ---------------------------------
+    ekfrt::PendView panels() const { return ekfrt::view(pend.p, ekf::d64::pend_layout(ld)); }
+    bool carries() const { return carry && pend_rows > 0; }   // this call leaves the rows pending and works through them
+    // Sigma <- Sigma_cur: one launch on the handle's stream when rows are pending, nothing otherwise.  For every entry point
+    // that reads or writes Sigma in memory, after its argument checks and inside its timed region.
+    void flush_pending() {
+        if (pend_rows == 0) return;
+        const ekfrt::PendView p = panels();
+        ekf::launch_dense64_flush(pl_live, S, p.K, p.T, pend_rows, p.zero, stream);
+        pend_rows = 0;
+    }
+    // A call that is a congruence on Sigma: the rows take it too (the caller's launch on the panels) when the handle carries
+    // them, and are applied first otherwise.
+    template <class Launch>
+    void carry_or_flush(Launch&& on_panels) {
+        if (carries()) on_panels(panels());
+        else flush_pending();
+    }
+};
