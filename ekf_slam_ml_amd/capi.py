@@ -5,6 +5,7 @@ constructor raises.  The classes mirror the reference's call surface:
 
   EKF_SLAM      rigid2d::EKF_SLAM                      rigid2d/include/rigid2d/ekf_slam.hpp:19-57
   BatchEKF      B independent EKF_SLAM objects driven by a device-resident log (configs[4])
+  DenseEKFSLAM  rigid2d::EKF_SLAM's three methods on one fp64 dense handle (DensePropagator64)
 """
 from __future__ import annotations
 
@@ -47,6 +48,7 @@ SYMBOLS = [
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
     "ekf_dense64_score_landmarks", "ekf_dense64_associate_landmarks",
+    "ekf_dense64_predict_landmarks", "ekf_dense64_measure_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
@@ -215,6 +217,8 @@ def load():
         "ekf_dense64_score_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip, _ip,
                                         _dp, _dp, _dp],
         "ekf_dense64_associate_landmarks": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, _ip, C.c_uint, _ip, _dp, _dp],
+        "ekf_dense64_predict_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, _dp, _dp, _dp],
+        "ekf_dense64_measure_landmarks": [h, C.POINTER(Params), C.c_int, _dp, _bp, _ip, C.c_uint, _ip, _dp, _dp, _dp],
         "ekf_dense64_set_carry": [h, C.c_int],
         "ekf_dense64_get_carry": [h, _ip],
         "ekf_dense64_set_live": [h, C.c_int],
@@ -1058,6 +1062,54 @@ class DensePropagator64(_DensePropagatorBase):
             raise
         return k.value, assoc, best, ms.value
 
+    def predict_landmarks(self, dtheta, dx, want_terms=False, params=None):
+        """prediction() (ekf_slam.cpp:55-106) for the twist (dtheta, dx) on the handle's own state: Fr = I + A, Qr = q_pose I
+        and the pose update are built on the device from state[0] (both branches of :79, |dtheta| < straight_eps is the
+        straight one), then exactly what propagate_block(0, Fr, Qr, dx) launches -- carry, pending rows and the live
+        dimension as there; the heading is not wrapped.  Nothing goes up, no state comes down.  Returns elapsed_ms, and
+        with want_terms (elapsed_ms, Fr (3, 3), dx (3,)) -- handed to propagate_block on a twin they give the same bits."""
+        Fr = np.empty((3, 3), dtype=np.float64) if want_terms else None
+        upd = np.empty(3, dtype=np.float64) if want_terms else None
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_predict_landmarks(
+            self._h, C.byref(params) if params is not None else None, float(dtheta), float(dx),
+            Fr.ctypes.data_as(_dp) if want_terms else None, upd.ctypes.data_as(_dp) if want_terms else None, C.byref(ms)))
+        return (ms.value, Fr, upd) if want_terms else ms.value
+
+    def measure_landmarks(self, sensor_xy, visible, initialised, deferred=False, want_terms=False, params=None):
+        """measurement() (ekf_slam.cpp:108-197) on the handle's own state: sensor_xy (n_lm, 2) holds a reading per
+        landmark, visible (n_lm,) says which are corrected, initialised is the reference's landmark_init_flag.  The pose
+        is captured once per call on the device and every correction of the call uses it; with initialised false ALL
+        n_lm landmarks are first placed from their readings (Sigma untouched).  Then per visible landmark, ascending:
+        correct_sparse (correct_sparse_deferred with deferred=True) on device-built operands and the heading wrap.
+        Returns (initialised, corrected, elapsed_ms), and with want_terms also (Hc (V, 2, 5), nu (V, 2) wrapped).  A
+        singular S raises EkfError (EKF_ERR_STATE); the exception carries .initialised and .corrected as they stood."""
+        z = np.ascontiguousarray(sensor_xy, dtype=np.float64)
+        if z.ndim == 1 and z.size % 2 == 0:
+            z = z.reshape(-1, 2)
+        if z.ndim != 2 or z.shape[1] != 2 or z.shape[0] < 1:
+            raise ValueError("sensor_xy must be n_lm x 2 with n_lm >= 1")
+        n_lm = z.shape[0]
+        vis = np.ascontiguousarray(np.asarray(visible) != 0, dtype=np.uint8)
+        if vis.shape != (n_lm,):
+            raise ValueError("visible must have length n_lm")
+        V = int(vis.sum())
+        Hc = np.empty((V, 2, 5), dtype=np.float64) if want_terms else None
+        nu = np.empty((V, 2), dtype=np.float64) if want_terms else None
+        flag, done, ms = C.c_int(1 if initialised else 0), C.c_int(0), C.c_double()
+        try:
+            _check(self._lib.ekf_dense64_measure_landmarks(
+                self._h, C.byref(params) if params is not None else None, n_lm, z.ctypes.data_as(_dp),
+                vis.ctypes.data_as(_bp), C.byref(flag), self.LM_DEFERRED if deferred else 0, C.byref(done),
+                Hc.ctypes.data_as(_dp) if want_terms else None, nu.ctypes.data_as(_dp) if want_terms else None,
+                C.byref(ms)))
+        except EkfError as e:
+            e.initialised, e.corrected = bool(flag.value), done.value
+            raise
+        if want_terms:
+            return bool(flag.value), done.value, ms.value, (Hc, nu)
+        return bool(flag.value), done.value, ms.value
+
     def init_block(self, first, G=None, cols=None, W=None, xb=None, r=None):
         """(Re)initialise the states b = [first, first + r) as a function of the s states in cols: Sigma <- F Sigma F^T + Q
         for F = identity with F[b, b] = 0, F[b, cols] = G and Q = zero with Q[b, b] = W; state[b] = xb.  G: r x s with cols
@@ -1174,6 +1226,81 @@ class DensePropagator64(_DensePropagatorBase):
     def launch_info(self):
         """{ld, tiles, n_big, n_tail}: how one product is cut into 128 x 128 tiles and a quarter-tile tail (test hook)"""
         return self._launch_info()
+
+
+class DenseEKFSLAM:
+    """rigid2d::EKF_SLAM (ekf_slam.hpp:19-57) on one DensePropagator64 handle: the reference's three methods, each one call
+    into the library, the state never leaving the device.  n landmarks in a handle with room for `capacity` (default n).
+    deferred: the corrections go through the pending rows; carry: prediction() and a new landmark leave them pending;
+    grow_live: the live dimension starts at the pose and data_association() grows it as the map is discovered
+    (measurement() places all n landmarks, so it raises it to 3 + 2 n).  `handle` is the DensePropagator64 underneath."""
+
+    PRIOR = 100.0   # the reference's landmark prior (ekf_slam.cpp:32)
+
+    def __init__(self, n, capacity=None, deferred=False, carry=False, grow_live=False, params=None, device=-1):
+        self.n = int(n)
+        cap = self.n if capacity is None else int(capacity)
+        if self.n < 1 or cap < self.n:
+            raise ValueError("n >= 1 and capacity >= n")
+        self.deferred, self.grow_live, self.params = bool(deferred), bool(grow_live), params
+        self.handle = d = DensePropagator64(3 + 2 * cap, device)
+        # the constructor's prior (:27-46): Sigma zero (as created) except 100 I on the landmarks; the state zero
+        for first in range(3, d.N, d.MAX_R):
+            r = min(d.MAX_R, d.N - first)
+            d.init_block(first, W=self.PRIOR * np.eye(r))
+        d.carry = bool(carry)
+        d.live = 3 if self.grow_live else 3 + 2 * self.n
+        self._known, self._init_flag = 0, False
+
+    def close(self):
+        self.handle.close()
+
+    def prediction(self, dtheta, dx):
+        """prediction(Twist2D(dtheta, dx, 0)); returns elapsed_ms"""
+        return self.handle.predict_landmarks(dtheta, dx, params=self.params)
+
+    def measurement(self, sensor_xy, visible):
+        """measurement(sensor_reading, visible_list, .); returns the number of corrections"""
+        d = self.handle
+        if d.live < 3 + 2 * self.n:
+            d.live = 3 + 2 * self.n
+        try:
+            self._init_flag, done, _ = d.measure_landmarks(sensor_xy, visible, self._init_flag, self.deferred,
+                                                           params=self.params)
+        except EkfError as e:
+            self._init_flag = e.initialised
+            raise
+        return done
+
+    def data_association(self, meas_xy):
+        """data_association(measures, known_list) with the known list kept by the object; returns assoc (J,) int32: the
+        landmark each reading corrected, -1 for a dropped one"""
+        try:
+            self._known, assoc, _, _ = self.handle.associate_landmarks(meas_xy, self._known, self.n, self.deferred,
+                                                                       self.grow_live, self.params)
+        except EkfError as e:
+            self._known = e.known
+            raise
+        return assoc
+
+    @property
+    def state(self):
+        """[theta, x, y, m1x, m1y, ...] of the n landmarks"""
+        return self.handle.state_block(0, 3 + 2 * self.n)
+
+    @property
+    def pose(self):
+        return self.handle.state_block(0, 3)
+
+    @property
+    def known(self):
+        """landmarks data_association() has initialised: landmarks 0 .. known - 1"""
+        return self._known
+
+    @property
+    def init_flag(self):
+        """the reference's landmark_init_flag: measurement() has placed the landmarks"""
+        return self._init_flag
 
 
 MAX_CLUSTERS = 128

@@ -3,7 +3,8 @@
 // scoring of candidates (ekf_dense64_score.hip), the block-structured prediction (ekf_dense64_block.hip), the update and
 // scoring for a Jacobian given by its non-zero columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states
 // and the block readout (ekf_dense64_init.hip), the exchange of two blocks (ekf_dense64_swap.hip), the landmark front end
-// (ekf_dense64_landmarks.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
+// (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), and the
+// deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 // The structured calls run at the handle's LIVE dimension (ekf_dense64_set_live, N by default): every launch of theirs is
@@ -48,9 +49,11 @@ constexpr int kMaxP = ekf::kDense64PendingMaxRows, kReadMax = ekf::kDense64ReadM
 constexpr int kScoreRows = ekf::kDense64ScoreMaxRows, kSparseRows = ekf::kDense64ScoreSparseMaxRows;
 
 // finish_timed of a correction: corr_out (nis | verdict) comes back in one copy; *verdict: 0 = applied, 1 = S singular.
-ekf_status finish_correction(ekf_dense64_s* d, double* elapsed_ms, double* nis, int* verdict) {
+// also, also2: further copies behind the same synchronisation (a null dst is skipped).
+ekf_status finish_correction(ekf_dense64_s* d, double* elapsed_ms, double* nis, int* verdict, const CopyBack& also = {},
+                             const CopyBack& also2 = {}) {
     double out[2] = {0.0, 0.0};
-    EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
+    EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}, also, also2}));
     *nis = out[0];
     std::memcpy(verdict, &out[1], sizeof(int));
     return EKF_OK;
@@ -96,10 +99,10 @@ void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool h
 
 // the one synchronisation of a correction, its verdict, the count of the pending rows
 ekf_status correct_sparse_finish(ekf_dense64_s* d, const char* fn, bool deferred, int m, double* nis_out,
-                                 double* elapsed_ms) {
+                                 double* elapsed_ms, const CopyBack& also = {}, const CopyBack& also2 = {}) {
     double nis = 0.0;
     int verdict = 0;
-    EKFC(finish_correction(d, elapsed_ms, &nis, &verdict));
+    EKFC(finish_correction(d, elapsed_ms, &nis, &verdict, also, also2));
     if (verdict != 0)
         return fail(EKF_ERR_STATE, std::string(fn) + ": H Sigma H^T + R is singular or not finite (zero or non-finite pivot); " +
                                        (deferred ? "state, Sigma and the pending rows are unchanged"
@@ -505,7 +508,7 @@ ekf_status ekf_dense64_score_landmarks(ekf_dense64_handle d, const ekf_params* p
     EKFC(sps_reserve(d, l.bytes, "ekf_dense64_score_landmarks"));
     const SpsView v = view(d->sps.p, l, S_out != nullptr);
     HIPC(hipEventRecord(d->e0, d->stream));
-    ekf::launch_dense64_lm_terms(d->x, sx, sy, first_lm, count, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+    ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, first_lm, count, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
     score_sparse_launch(d, v, count, 2, 5, true, true, nis_out != nullptr);
     return finish_timed(d, elapsed_ms, {{nis_out, v.nis, sizeof(double) * count},
                                         {S_out, v.S, sizeof(double) * count * 4},
@@ -560,7 +563,7 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
         if (k > 0) v = view(d->sps.p, L::sps_layout(k, 2, 5, true, false), false);   // (k <= n_max: inside the buffer)
         HIPC(hipEventRecord(d->e0, d->stream));
         if (k > 0) {
-            ekf::launch_dense64_lm_terms(d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+            ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
             score_sparse_launch(d, v, k, 2, 5, true, true, true);
         }
         ekf::launch_dense64_lm_decide(v.nis, k, k, n_max, p.gate_new, p.gate_update, p.sigma0_landmark, d->x, sx, sy, drec,
@@ -588,7 +591,8 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
             continue;
         }
         // the winner's operands from the current state, that is after an initialisation; the innovation wrapped (:183)
-        ekf::launch_dense64_lm_terms(d->x, sx, sy, rec.win, 1, 1, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
+        ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, rec.win, 1, 1, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu,
+                                     d->stream);
         correct_sparse_launch(d, deferred, 2, 5, true);
         ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
         if (assoc_out) assoc_out[j] = -1;
@@ -597,6 +601,84 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
         if (fresh_lm && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + 1;   // the initialisation stands
         if (st != EKF_OK) return st;
         if (assoc_out) assoc_out[j] = rec.win;
+    }
+    return EKF_OK;
+}
+
+// ---- the reference's prediction() and measurement() on the handle's own state ------------------------------------------
+// prediction (:55-106): k_dmd_predict writes Fr, Qr and dx from state[0] where propagate_block's uploads go, then exactly
+// what ekf_dense64_propagate_block(first = 0, r = 3) launches; the operands come down behind the one synchronisation.
+ekf_status ekf_dense64_predict_landmarks(ekf_dense64_handle d, const ekf_params* params, double dtheta, double dx,
+                                         double* Fr_out, double* dx_out, double* elapsed_ms) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_predict_landmarks: null handle");
+    if (d->live < 3)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_predict_landmarks: the pose block must lie inside the live dimension");
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    const BlkInView in = view(d->blk_in, L::blk_in_layout());
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_model_predict(d->x, dtheta, dx, p.q_pose, p.straight_eps, in.Fr, in.Qr, in.dx, d->stream);
+    d->carry_or_flush([&](const PendView& pv) {
+        ekf::launch_dense64_panel_map(pv.K, pv.T, d->pend_rows, in.Fr, nullptr, d->ld, 0, 3, 3, d->stream);
+    });
+    ekf::launch_dense64_block(d->S, d->x, in.Fr, in.Qr, in.dx, d->live, d->ld, 0, 3, d->stream);
+    return finish_timed(d, elapsed_ms, {{Fr_out, in.Fr, sizeof(double) * 9}, {dx_out, in.dx, sizeof(double) * 3}});
+}
+
+// measurement (:108-197).  [snapshot | init of all n_lm landmarks on the first call], then per visible landmark in
+// ascending order [terms at the snapshot pose, wrapped | correction | heading wrap] and the correction's own
+// synchronisation.  Nothing of the state comes down; the readings go up once, and only when the call initialises.
+ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle d, const ekf_params* params, int n_lm, const double* sensor_xy,
+                                         const uint8_t* visible, int* initialised, unsigned flags, int* corrected_out,
+                                         double* Hc_out, double* nu_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_measure_landmarks";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!sensor_xy || !visible || !initialised) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (n_lm < 1 || 3 + 2 * (long long)n_lm > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the n_lm >= 1 landmarks must lie inside the live dimension");
+    if (flags & ~EKF_DENSE64_LM_DEFERRED) return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0, init = *initialised == 0;
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (corrected_out) *corrected_out = 0;
+    HIPC(hipSetDevice(d->device));
+    if (deferred) EKFC(pend_reserve(d, fnc));
+    const L::LmMeasureLayout l = L::lm_measure_layout(n_lm);
+    EKFC(sps_reserve(d, l.bytes, fnc));
+    const LmMeasureView mv = view(d->sps.p, l);
+    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    if (init) HIPC(hipMemcpyAsync(mv.xy, sensor_xy, sizeof(double) * 2 * n_lm, hipMemcpyHostToDevice, d->stream));
+    double total = 0.0, ms = 0.0;
+    double* pms = elapsed_ms ? &ms : nullptr;
+    // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
+    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_model_snapshot(d->x, mv.pose, d->stream);                        // :109-111
+    if (init) ekf::launch_dense64_model_init(mv.pose, mv.xy, n_lm, d->x, d->stream);     // :113-128, Sigma untouched
+    bool open = true;   // e0 is recorded and nothing has synchronised behind it yet
+    int v = 0;
+    for (int i = 0; i < n_lm; i++) {
+        if (!visible[i]) continue;
+        if (!open) HIPC(hipEventRecord(d->e0, d->stream));
+        open = false;
+        // the pose of the snapshot, the landmark from the current state (get_tube_x(i)); the innovation wrapped (:183)
+        ekf::launch_dense64_lm_terms(d->x, mv.pose, sensor_xy[2 * i], sensor_xy[2 * i + 1], i, 1, 1, p.r_meas, cin.cols,
+                                     cin.Hc, cin.R, cin.nu, d->stream);
+        correct_sparse_launch(d, deferred, 2, 5, true);
+        ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187
+        // (a refused correction's launches ran and were timed)
+        const ekf_status st = leg(correct_sparse_finish(
+            d, fnc, deferred, 2, nullptr, pms, {Hc_out ? Hc_out + (size_t)v * 10 : nullptr, cin.Hc, sizeof(double) * 10},
+            {nu_out ? nu_out + (size_t)v * 2 : nullptr, cin.nu, sizeof(double) * 2}));
+        if (init && (st == EKF_OK || st == EKF_ERR_STATE)) *initialised = 1;   // the initialisation has completed and stands
+        if (st != EKF_OK) return st;
+        v++;
+        if (corrected_out) *corrected_out = v;
+    }
+    if (open) {   // nothing visible: the snapshot (and the initialisation) alone
+        EKFC(leg(finish_timed(d, pms)));
+        if (init) *initialised = 1;
     }
     return EKF_OK;
 }

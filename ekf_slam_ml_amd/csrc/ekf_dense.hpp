@@ -165,8 +165,10 @@ void launch_dense64_panel_swap(double* Kp, double* Tq, int p, int ld, int first_
 // One thread per candidate: cols [count][5] = {0, 1, 2, 3 + 2 i, 4 + 2 i}, Hc [count][2][5] (predicted_terms), nu [count][2]
 // = z - zhat with the bearing raw (wrap = 0, the score's) or wrapped (wrap = 1, the correction's), R [2][2] = r_meas I;
 // Hc and nu on 16-byte boundaries.  3 + 2 (first_lm + count) <= the state's length (the launcher does not check).
-void launch_dense64_lm_terms(const double* state, double sx, double sy, int first_lm, int count, int wrap, double r_meas,
-                             int* cols, double* Hc, double* R, double* nu, hipStream_t st);
+// pose [3]: (theta, x, y) the model is taken at -- `state` itself for calculate_maha_dis and data_association (:331-333), the
+// snapshot of measurement() (:109-111) otherwise; the landmark's position always comes from `state`.
+void launch_dense64_lm_terms(const double* state, const double* pose, double sx, double sy, int first_lm, int count,
+                             int wrap, double r_meas, int* cols, double* Hc, double* R, double* nu, hipStream_t st);
 // what k_dlm_decide leaves for the host: 32 bytes
 enum : int { kDense64LmCorrect = 1, kDense64LmNew = 2 };
 struct Dense64LmRecord {
@@ -185,6 +187,17 @@ void launch_dense64_lm_decide(const double* nis, int count, int known, int n_max
                               double* xb, hipStream_t st);
 // state[0] = normalize_angle(state[0]) unless *verdict != 0 (the correction before it refused and wrote nothing)
 void launch_dense64_lm_wrap(double* state, const int* verdict, hipStream_t st);
+
+// ---- the reference's motion model and the top of its measurement() on the handle's state (ekf_dense64_model.hip).
+// One thread: Fr [3][3] = eye + A, Qr [3][3] = q_pose I, upd [3] of prediction() (:67-96) for the heading state[0] and the
+// twist (dtheta, dx); |dtheta| < straight_eps takes the straight branch.  Fr, Qr, upd: where propagate_block's operands go.
+void launch_dense64_model_predict(const double* state, double dtheta, double dx, double q_pose, double straight_eps,
+                                  double* Fr, double* Qr, double* upd, hipStream_t st);
+// pose [3] = state[0..2] (:109-111)
+void launch_dense64_model_snapshot(const double* state, double* pose, hipStream_t st);
+// One thread per landmark: state[3 + 2 i], state[4 + 2 i] = the position reading i (sensor_xy [n_lm][2], on a 16-byte
+// boundary) has from `pose` (:114-125), for every i < n_lm; 3 + 2 n_lm <= the state's length (the launcher does not check).
+void launch_dense64_model_init(const double* pose, const double* sensor_xy, int n_lm, double* state, hipStream_t st);
 
 // ---- the coupling between the live corner and the tail (ekf_dense64_live.hip): over the two rectangles of an N x N Sigma
 // with exactly one index >= Na, the number of entries != 0 and the largest absolute value.  One streaming launch, integer

@@ -1,7 +1,8 @@
 // ekf_dense64_landmarks.hip -- the reference's range-bearing landmark model and its decision rule on the dense64 handle's
 // own state (gfx950, wave64): what a caller of the model-free sparse calls would otherwise compute on the host between them.
 //   k_dlm_terms   one thread per candidate landmark: cols, Hc, nu (measurement_terms of ekf_kernels.hpp) and the shared R,
-//                 written where k_dsp_score (or, with count = 1 and the wrapped innovation, the sparse correction) reads them
+//                 written where k_dsp_score (or, with count = 1 and the wrapped innovation, the sparse correction) reads them;
+//                 the pose through a pointer of its own (the state, or the snapshot of ekf_dense64_measure_landmarks)
 //   k_dlm_decide  one workgroup: the lexicographic (score, index) minimum of the scores with NaNs skipped, the rule of
 //                 data_association (:293-330), the inverse sensor model of a new landmark (:200-214), a 32-byte record
 //   k_dlm_wrap    state[0] = normalize_angle(state[0]) (:187 / :385), stored unconditionally unless the correction refused
@@ -18,13 +19,16 @@ constexpr int kLmThreads = 256;
 typedef double pair8 __attribute__((ext_vector_type(2), aligned(8)));
 typedef double pair16 __attribute__((ext_vector_type(2)));
 
-__global__ __launch_bounds__(kLmThreads) void k_dlm_terms(const double* __restrict__ state, double sx, double sy,
+__global__ __launch_bounds__(kLmThreads) void k_dlm_terms(const double* __restrict__ state,
+                                                          const double* __restrict__ pose, double sx, double sy,
                                                           int first_lm, int count, int wrap, double r_meas,
                                                           int* __restrict__ cols, double* __restrict__ Hc,
                                                           double* __restrict__ R, double* __restrict__ nu) {
     const int j = blockIdx.x * kLmThreads + threadIdx.x, lane = threadIdx.x & 63;
-    // the pose: three lanes load it, the wave takes it through the scalar file (every lane is still active here)
-    const double pv = state[lane < 3 ? lane : 0];
+    // the pose -- the state's own (data_association re-reads it per reading, :331-333) or the slot measurement() captured
+    // it in (:109-111); the landmarks always come from the state.  Three lanes load it, the wave takes it through the scalar
+    // file (every lane is still active here)
+    const double pv = pose[lane < 3 ? lane : 0];
     const double theta = lane_bcast(pv, 0), x = lane_bcast(pv, 1), y = lane_bcast(pv, 2);
     if (j == 0) {
         R[0] = r_meas; R[1] = 0.0; R[2] = 0.0; R[3] = r_meas;   // :172-175, shared by the candidates
@@ -130,10 +134,10 @@ __global__ void k_dlm_wrap(double* __restrict__ state, const int* __restrict__ v
 
 }  // namespace
 
-void launch_dense64_lm_terms(const double* state, double sx, double sy, int first_lm, int count, int wrap, double r_meas,
-                             int* cols, double* Hc, double* R, double* nu, hipStream_t st) {
-    hipLaunchKernelGGL(k_dlm_terms, dim3((count + kLmThreads - 1) / kLmThreads), dim3(kLmThreads), 0, st, state, sx, sy,
-                       first_lm, count, wrap, r_meas, cols, Hc, R, nu);
+void launch_dense64_lm_terms(const double* state, const double* pose, double sx, double sy, int first_lm, int count,
+                             int wrap, double r_meas, int* cols, double* Hc, double* R, double* nu, hipStream_t st) {
+    hipLaunchKernelGGL(k_dlm_terms, dim3((count + kLmThreads - 1) / kLmThreads), dim3(kLmThreads), 0, st, state, pose, sx,
+                       sy, first_lm, count, wrap, r_meas, cols, Hc, R, nu);
 }
 
 void launch_dense64_lm_decide(const double* nis, int count, int known, int n_max, double gate_new, double gate_update,

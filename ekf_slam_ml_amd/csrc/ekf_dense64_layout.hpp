@@ -58,5 +58,9 @@ inline SpsLayout sps_layout(int J, int m, int s, bool r_shared, bool want_S) {
                  S = nis + up(kF * J), cols = S + (want_S ? up(kF * J * mm) : 0), flag = cols + up(kI * J * s);
     return {0, R, nu, nis, S, cols, flag, flag + up(kI * J)};
 }
+// ekf_dense64_measure_landmarks' view of that same buffer (it scores nothing): the pose captured at the top of the call
+// (3 doubles in a 32-byte slot) | the call's readings [n_lm][2], on a 16-byte boundary, when the first call initialises
+struct LmMeasureLayout { size_t pose, xy, bytes; };
+inline LmMeasureLayout lm_measure_layout(int n_lm) { return {0, 4 * kF, 4 * kF + 2 * kF * (size_t)n_lm}; }
 }  // namespace d64
 }  // namespace ekf

@@ -80,6 +80,8 @@ struct SpsView { double *Hc, *R, *nu, *nis, *S; int *cols, *flag; };   // S null
 inline SpsView view(void* b, const L::SpsLayout& l, bool want_S) {
     return {f64(b, l.Hc), f64(b, l.R), f64(b, l.nu), f64(b, l.nis), want_S ? f64(b, l.S) : nullptr, i32(b, l.cols), i32(b, l.flag)};
 }
+struct LmMeasureView { double *pose, *xy; };
+inline LmMeasureView view(void* b, const L::LmMeasureLayout& l) { return {f64(b, l.pose), f64(b, l.xy)}; }
 
 // The end of a timed entry point: e1 behind the launches, the launch error, the copies back to the host (a null dst is
 // skipped), ONE synchronisation, the time between the handle's events.
@@ -116,7 +118,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf sc_small;   // ScSmallLayout (ekf_dense64_score)
     ekfrt::DeviceBuf sc_H;       // the stacked Jacobians, [groups * 64][ld], columns N .. ld zero
     ekfrt::DeviceBuf sc_ws;      // the partial S blocks of a call that do not fit the product buffer T
-    ekfrt::DeviceBuf sps;        // SpsLayout (ekf_dense64_score_sparse, the landmark front end), cut per call
+    ekfrt::DeviceBuf sps;        // SpsLayout (ekf_dense64_score_sparse, the landmark front end), cut per call; LmMeasureLayout
     ekfrt::DeviceBuf pend;       // PendLayout (ekf_dense64_correct_sparse_deferred)
     ekfrt::DeviceBuf lm_rec;     // ekf::Dense64LmRecord, the decision record of one reading (the landmark front end)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads

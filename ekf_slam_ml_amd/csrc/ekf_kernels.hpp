@@ -245,6 +245,39 @@ __device__ __forceinline__ void predicted_terms(double tx, double ty, double the
     m.H[1][3] = -yd; m.H[1][4] = xd;
 }
 
+// prediction() (ekf_slam.cpp:67-96) as a function of the heading and the twist (dtheta, dx), dy = 0: the update of the pose
+// and the two non-zero entries of A, both branches of :79 in the reference's own expression order (-(dx/dtheta) negates the
+// quotient, then multiplies).  At = eye + A, so At(1,0) = 0 + a10 and At(2,0) = 0 + a20: a -0.0 becomes +0.0 there.
+struct MotionTerms {
+    double upd[3];     // update(0..2,0)                         ekf_slam.cpp:80-82 / :89-91
+    double a10, a20;   // A(1,0), A(2,0)                         ekf_slam.cpp:85-86 / :93-94
+};
+__device__ __forceinline__ void motion_terms(double theta, double dtheta, double dx, double straight_eps, MotionTerms& m) {
+    if (fabs(dtheta) < straight_eps) {
+        m.upd[0] = 0;
+        m.upd[1] = dx * cos(theta);
+        m.upd[2] = dx * sin(theta);
+        m.a10 = -dx * sin(theta);
+        m.a20 = dx * cos(theta);
+    } else {
+        m.upd[0] = dtheta;
+        m.upd[1] = -(dx / dtheta) * sin(theta) + (dx / dtheta) * sin(theta + dtheta);
+        m.upd[2] = (dx / dtheta) * cos(theta) - (dx / dtheta) * cos(theta + dtheta);
+        m.a10 = -(dx / dtheta) * cos(theta) + (dx / dtheta) * cos(theta + dtheta);
+        m.a20 = -(dx / dtheta) * sin(theta) + (dx / dtheta) * sin(theta + dtheta);
+    }
+}
+
+// the first-call initialisation of measurement() (:115-123) and initialize_landmark (:204-212): where the reading (sx, sy)
+// taken from the pose (theta, x, y) puts a landmark
+__device__ __forceinline__ void landmark_from_reading(double sx, double sy, double theta, double x, double y, double& mx,
+                                                      double& my) {
+    const double ri = sqrt(sx * sx + sy * sy);
+    const double phii = atan2(sy, sx);
+    mx = x + ri * cos(phii + theta);
+    my = y + ri * sin(phii + theta);
+}
+
 // S = H Sigma H^T + R on the 5x5 sub-block, same summation order as the CPU restatement.
 __device__ __forceinline__ void innovation_cov(const double S55[5][5], const double H[2][5], double r_meas,
                                                double S[2][2]) {

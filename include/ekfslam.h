@@ -701,6 +701,67 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle h, const ekf_param
                                            double* best_out,  /* [J] winning score (gate_new when nothing won); nullable */
                                            double* elapsed_ms);
 
+/* The other two methods of rigid2d::EKF_SLAM on the handle's own state: prediction() (ekf_slam.cpp:55-106) and measurement()
+ * (:108-197).  After ekf_dense64_associate_landmarks the heading lives on the device only -- it is corrected there and
+ * nothing is read back -- so a caller of the model-free ekf_dense64_propagate_block would fetch state[0], evaluate four
+ * transcendentals and upload three operands per tick.  These two calls keep that on the device as well; with them both
+ * loops of the reference's nodes (slam: prediction + measurement; unknown_data_assoc: prediction + data_association) run
+ * without the state leaving the device.  Layers over propagate_block and correct_sparse[_deferred], which stay as they are.
+ * params: q_pose and straight_eps (prediction), r_meas (measurement) are used; NULL = the reference's constants.
+ * ekf_dense64_predict_landmarks: prediction(Twist2D(dtheta, dx, 0)).
+ *   OPERANDS, built by one thread on the device (the library's -ffp-contract=off) from theta = state[0]:
+ *     |dtheta| < straight_eps (strict):  update = (0, dx cos(theta), dx sin(theta));  A(1,0) = -dx sin(theta),
+ *       A(2,0) = dx cos(theta)                                                                          (:80-86)
+ *     otherwise:  update = (dtheta, -(dx/dtheta) sin(theta) + (dx/dtheta) sin(theta + dtheta),
+ *       (dx/dtheta) cos(theta) - (dx/dtheta) cos(theta + dtheta));  A(1,0) = -(dx/dtheta) cos(theta) + (dx/dtheta)
+ *       cos(theta + dtheta), A(2,0) = -(dx/dtheta) sin(theta) + (dx/dtheta) sin(theta + dtheta)         (:89-94)
+ *   in exactly that expression order.  Fr = I + A: the identity bit for bit except (1,0) and (2,0); Qr = q_pose I; they are
+ *   written into the buffer ekf_dense64_propagate_block uploads into.
+ *   THEN exactly what ekf_dense64_propagate_block(h, 0, 3, Fr, Qr, dx, ..) launches: the pending rows carried (mapped) or
+ *   flushed first as the carry policy says, then its one launch at the live dimension.  The heading is NOT wrapped (:99
+ *   does not wrap it).  State, Sigma and the pending rows afterwards are bit for bit those of a twin handle on which
+ *   ekf_dense64_propagate_block(h, 0, 3, Fr_out, q_pose I, dx_out, ..) is called.
+ *   FAILURES: a NULL handle, then live < 3 -> EKF_ERR_INVALID before the device is looked at, nothing changes.
+ *   ONE synchronisation; Fr_out [9] and dx_out [3] (both nullable) come down behind it.  Nothing goes up and no state comes
+ *   down.  elapsed_ms (nullable) = HIP-event time of the launches (the operand kernel included).
+ * ekf_dense64_measure_landmarks: measurement(sensor_reading, visible_list, .) for landmarks 0 .. n_lm - 1; sensor_xy
+ *   [n_lm][2] holds a reading per landmark (read only where visible[i] != 0, and everywhere by a call that initialises).
+ *   THE POSE (:109-111) is copied ONCE, at the top of the call, into a 24-byte device slot, and every correction of the call
+ *   takes theta, x, y from that slot while the landmark's position comes from the CURRENT state (get_tube_x(i), :152-159).
+ *   This is the one difference from the model of ekf_dense64_associate_landmarks, whose reference function re-reads the
+ *   pose per reading (:331-333): from the second visible landmark of a call on the two models differ.
+ *   *initialised (IN/OUT) is the reference's landmark_init_flag.  0: sensor_xy goes up once and one launch, a thread per
+ *   landmark, writes state[3 + 2 i], state[4 + 2 i] for EVERY i < n_lm -- the invisible ones included, as :113-128 do -- from
+ *   x + r cos(phi + theta), y + r sin(phi + theta) at the snapshot pose; Sigma is not touched; *initialised becomes 1 once
+ *   that launch has completed.  Non-zero: nothing of the sort happens and sensor_xy is read on the host only.
+ *   PER VISIBLE LANDMARK, in ascending i: the operands of ekf_dense64_associate_landmarks' correction (cols = {0, 1, 2,
+ *   3 + 2 i, 4 + 2 i}, Hc, R = r_meas I, the innovation with its bearing wrapped, :183) at the snapshot pose;
+ *   ekf_dense64_correct_sparse, or ekf_dense64_correct_sparse_deferred with EKF_DENSE64_LM_DEFERRED, through their internal
+ *   path (the eager one flushes pending rows first, the deferred one only when its two rows do not fit);
+ *   state[0] = normalize_angle(state[0]) stored unconditionally (:187); the correction's own synchronisation.
+ *   Hc_out [V][2][5] and nu_out [V][2] (nullable; V = the number of visible landmarks) receive the operands of the v-th
+ *   correction.  State, Sigma and the pending rows afterwards are bit for bit those of a twin handle on which the host
+ *   calls ekf_dense64_correct_sparse[_deferred] with those operands, cols as above and R = r_meas I, and sets the heading.
+ *   FAILURES: checked before the device is looked at, in this order: NULL handle; NULL sensor_xy, visible or initialised;
+ *   n_lm < 1 or 3 + 2 n_lm > live; a flag bit other than EKF_DENSE64_LM_DEFERRED (EKF_DENSE64_LM_GROW_LIVE included) ->
+ *   EKF_ERR_INVALID, nothing changes.  A singular or non-finite S returns EKF_ERR_STATE from that correction: state, Sigma
+ *   and the pending rows are as before that correction, the heading is not rewritten, earlier corrections (and the
+ *   initialisation) stand, later landmarks are not reached.  *corrected_out (nullable) = corrections completed.
+ *   SYNCHRONISATION: one per visible landmark; a call with nothing visible has one.  A reading goes up as sixteen bytes of
+ *   kernel arguments; no state comes down.  No floating-point atomics; the same inputs give the same bits on every run.
+ *   Memory: the operand buffers of the sparse correction, the scoring buffer of ekf_dense64_score_sparse (32 bytes for the
+ *   pose slot and 16 n_lm for the readings of an initialising call), the pending panels with EKF_DENSE64_LM_DEFERRED.
+ *   elapsed_ms (nullable) = HIP-event time of the launches, summed over the corrections, a refused one included. */
+ekf_status ekf_dense64_predict_landmarks(ekf_dense64_handle h, const ekf_params* params, double dtheta, double dx,
+                                         double* Fr_out /* [3][3] nullable */, double* dx_out /* [3] nullable */,
+                                         double* elapsed_ms);
+ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle h, const ekf_params* params, int n_lm,
+                                         const double* sensor_xy /* [n_lm][2] */, const uint8_t* visible /* [n_lm] */,
+                                         int* initialised /* IN/OUT: landmark_init_flag */, unsigned flags,
+                                         int* corrected_out /* corrections completed, nullable */,
+                                         double* Hc_out /* [V][2][5] nullable */, double* nu_out /* [V][2] wrapped, nullable */,
+                                         double* elapsed_ms);
+
 /* Carrying the pending rows across ticks: the caller chooses the flush cadence.  With the policy off (the default) every
  * entry point does exactly what is written above.  With it on and rows pending, the three calls a SLAM tick makes between
  * its corrections no longer flush:
