@@ -48,6 +48,7 @@ SYMBOLS = [
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
     "ekf_dense64_score_landmarks", "ekf_dense64_associate_landmarks",
+    "ekf_dense64_fit_scan", "ekf_dense64_associate_scan",
     "ekf_dense64_predict_landmarks", "ekf_dense64_measure_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
@@ -217,6 +218,9 @@ def load():
         "ekf_dense64_score_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip, _ip,
                                         _dp, _dp, _dp],
         "ekf_dense64_associate_landmarks": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, _ip, C.c_uint, _ip, _dp, _dp],
+        "ekf_dense64_fit_scan": [h, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp],
+        "ekf_dense64_associate_scan": [h, C.POINTER(Params), _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_uint, _ip, _dp, _ip,
+                                       _dp, _dp],
         "ekf_dense64_predict_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, _dp, _dp, _dp],
         "ekf_dense64_measure_landmarks": [h, C.POINTER(Params), C.c_int, _dp, _bp, _ip, C.c_uint, _ip, _dp, _dp, _dp],
         "ekf_dense64_set_carry": [h, C.c_int],
@@ -777,6 +781,7 @@ class DensePropagator64(_DensePropagatorBase):
     READ_MAX = 65536   # EKF_DENSE64_READ_MAX
     PENDING_MAX_ROWS = 64   # EKF_DENSE64_PENDING_MAX_ROWS
     LM_DEFERRED, LM_GROW_LIVE = 1, 2   # EKF_DENSE64_LM_DEFERRED, EKF_DENSE64_LM_GROW_LIVE
+    SCAN_MAX_BEAMS, SCAN_MAX_CIRCLES = 1024, 128   # EKF_DENSE64_SCAN_MAX_BEAMS, EKF_DENSE64_SCAN_MAX_CIRCLES
 
     _PREFIX, _DTYPE, _PTR = "ekf_dense64_", np.float64, _dp
 
@@ -1062,6 +1067,55 @@ class DensePropagator64(_DensePropagatorBase):
             raise
         return k.value, assoc, best, ms.value
 
+    @staticmethod
+    def _scan(ranges):
+        r = np.ascontiguousarray(ranges, dtype=np.float64)
+        if r.ndim != 1 or not 1 <= r.shape[0] <= DensePropagator64.SCAN_MAX_BEAMS:
+            raise ValueError(f"ranges must be one scan of 1 .. {DensePropagator64.SCAN_MAX_BEAMS} beams")
+        return r
+
+    def fit_scan(self, ranges, max_out=64, want_all=False):
+        """CircleFitting::approxCirclePositions (circle_fitting.cpp:11-304) of ONE scan on the handle's device and stream: one
+        workgroup, a wave per cluster; read-only with respect to the filter.  Returns (centres (k, 2), radii (k,),
+        elapsed_ms), the first max_out circles in cluster order, and with want_all (centres, radii, all (c, 4) = x, y, r,
+        is_circle of every cluster, elapsed_ms)."""
+        r = self._scan(ranges)
+        max_out = int(max_out)
+        if not 1 <= max_out <= self.SCAN_MAX_CIRCLES:
+            raise ValueError(f"1 <= max_out <= {self.SCAN_MAX_CIRCLES}")
+        cen, rad = np.empty((max_out, 2), dtype=np.float64), np.empty(max_out, dtype=np.float64)
+        allc = np.empty((self.SCAN_MAX_CIRCLES, 4), dtype=np.float64) if want_all else None
+        cnt, ncl, ms = C.c_int(), C.c_int(), C.c_double()
+        _check(self._lib.ekf_dense64_fit_scan(self._h, r.ctypes.data_as(_dp), r.shape[0], max_out, C.byref(cnt),
+                                              cen.ctypes.data_as(_dp), rad.ctypes.data_as(_dp),
+                                              allc.ctypes.data_as(_dp) if want_all else None, C.byref(ncl), C.byref(ms)))
+        if want_all:
+            return cen[:cnt.value].copy(), rad[:cnt.value].copy(), allc[:ncl.value].copy(), ms.value
+        return cen[:cnt.value].copy(), rad[:cnt.value].copy(), ms.value
+
+    def associate_scan(self, ranges, known, n_max, max_readings=64, deferred=False, grow_live=False, params=None):
+        """fit_scan(ranges, max_readings) followed by associate_landmarks' per-reading path on the circles it finds, in
+        cluster order, in one call: the landmarks node and the unknown_data_assoc node of the reference.  Returns (known,
+        centres (k, 2), assoc (k,) int32, best (k,)); a scan without a circle gives k = 0 and writes nothing.  A refused call
+        or a singular S raises EkfError; the exception carries .known, .centres, .assoc and .best as they stood."""
+        r = self._scan(ranges)
+        max_readings = int(max_readings)
+        if not 1 <= max_readings <= self.SCAN_MAX_CIRCLES:
+            raise ValueError(f"1 <= max_readings <= {self.SCAN_MAX_CIRCLES}")
+        k, cnt = C.c_int(int(known)), C.c_int(0)
+        cen = np.zeros((max_readings, 2), dtype=np.float64)
+        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
+        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        try:
+            _check(self._lib.ekf_dense64_associate_scan(
+                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
+                int(n_max), C.byref(k), flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
+                best.ctypes.data_as(_dp), None))
+        except EkfError as e:
+            e.known, e.centres, e.assoc, e.best = k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+            raise
+        return k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+
     def predict_landmarks(self, dtheta, dx, want_terms=False, params=None):
         """prediction() (ekf_slam.cpp:55-106) for the twist (dtheta, dx) on the handle's own state: Fr = I + A, Qr = q_pose I
         and the pose update are built on the device from state[0] (both branches of :79, |dtheta| < straight_eps is the
@@ -1282,6 +1336,17 @@ class DenseEKFSLAM:
             self._known = e.known
             raise
         return assoc
+
+    def scan_association(self, ranges):
+        """one LaserScan through the landmarks node (circle fitting) into data_association(), in one call; returns (centres
+        (k, 2), assoc (k,) int32) of the k circles found"""
+        try:
+            self._known, centres, assoc, _ = self.handle.associate_scan(ranges, self._known, self.n, deferred=self.deferred,
+                                                                        grow_live=self.grow_live, params=self.params)
+        except EkfError as e:
+            self._known = e.known
+            raise
+        return centres, assoc
 
     @property
     def state(self):

@@ -38,8 +38,9 @@ ekf_status ekf_dense64_s::created() {
 
 void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
     for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p})
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p})
         if (p) (void)hipFree(p);
+    scan_up.release();
 }
 
 namespace {
@@ -176,6 +177,130 @@ ekf::Params landmark_params(const ekf_params* params) {
     ekf_default_params(&p);
     if (params) p = *params;
     return ekf::Params{p.sigma0_landmark, p.q_pose, p.r_meas, p.gate_new, p.gate_update, p.straight_eps};
+}
+
+
+// ---- one laser scan -> circles (ekf_dense64_scan.hip) ---------------------------------------------------------------------
+// The ranges go up through a slot of the pinned ring, one launch on the handle's stream, and the record {circles kept,
+// clusters, centres, radii} (and every cluster's row when asked for) comes down into d->scan_rec behind ONE synchronisation.
+// The device buffer and the ring are reserved by the first call; a later call allocates nothing.  Read-only on the filter.
+constexpr int kScanBeams = ekf::kDense64ScanMaxBeams, kScanClusters = ekf::kDense64ScanMaxClusters;
+
+struct ScanRecord { int count, n_clusters; const double *centres, *radii, *all; };   // views of d->scan_rec
+
+ekf_status scan_fit(ekf_dense64_s* d, const char* fn, const double* ranges, int n_beams, int max_out, bool want_all,
+                    double* elapsed_ms, ScanRecord* rec) {
+    const L::ScanLayout l = L::scan_layout();
+    if (!d->scan.p) {
+        for (Staging& sg : d->scan_up.slot) EKFC(sg.reserve(sizeof(double) * kScanBeams));
+        d->scan_rec.assign((l.bytes - l.head) / sizeof(double), 0.0);
+    }
+    EKFC(d->scan.reserve(l.bytes, d->stream, true, fn, "the scan buffer"));
+    const ScanView v = view(d->scan.p, l);
+    Staging& sg = d->scan_up.acquire();
+    EKFC(sg.wait());
+    std::memcpy(sg.host, ranges, sizeof(double) * n_beams);
+    HIPC(hipMemcpyAsync(v.ranges, sg.host, sizeof(double) * n_beams, hipMemcpyHostToDevice, d->stream));
+    EKFC(sg.mark(d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_scan_circles(v.ranges, n_beams, max_out, v.head, v.centres, v.radii, v.all, d->stream);
+    char* host = reinterpret_cast<char*>(d->scan_rec.data());
+    EKFC(finish_timed(d, elapsed_ms, {{host, v.head, l.record_bytes},
+                                      {want_all ? host + (l.all - l.head) : nullptr, v.all, l.bytes - l.all}}));
+    const int* head = reinterpret_cast<const int*>(host);
+    if (head[0] < 0 || head[0] > max_out || head[1] < 0 || head[1] > kScanClusters)
+        return fail(EKF_ERR_HIP, std::string(fn) + ": the circle kernel left an impossible record");
+    *rec = ScanRecord{head[0], head[1], reinterpret_cast<const double*>(host + (l.centres - l.head)),
+                      reinterpret_cast<const double*>(host + (l.radii - l.head)),
+                      reinterpret_cast<const double*>(host + (l.all - l.head))};
+    return EKF_OK;
+}
+
+// ---- data_association (:278-402), shared by ekf_dense64_associate_landmarks and ekf_dense64_associate_scan -----------------
+// the argument checks both calls make, in their documented order, behind their own
+ekf_status associate_checks(ekf_dense64_s* d, const std::string& fn, int n_max, const int* known, unsigned flags) {
+    if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
+        return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
+    if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
+    if (3 + 2 * *known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
+    if (flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
+        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    return EKF_OK;
+}
+
+// what the loop below needs in memory
+ekf_status associate_reserve(ekf_dense64_s* d, const char* fnc, int n_max, bool deferred) {
+    EKFC(d->lm_rec.reserve(sizeof(ekf::Dense64LmRecord), d->stream, false, fnc, "the decision record"));
+    if (deferred) EKFC(pend_reserve(d, fnc));
+    // the scoring buffer once, for the full map: a map that is being discovered must not pay a hipMalloc and a hipFree
+    // (a device synchronisation) per new landmark
+    if (n_max > 0) EKFC(sps_reserve(d, L::sps_layout(n_max, 2, 5, true, false).bytes, fnc));
+    return EKF_OK;
+}
+
+// J readings in order.  Per reading: [terms | score | decide] and the 32-byte record back (the first synchronisation); then,
+// as the record says, [init_block] [terms of the winner, wrapped | correction | heading wrap] and the correction's own
+// synchronisation.  Nothing of the state comes down and no candidate array goes up.  *elapsed_ms (nullable) holds the time
+// of what ran before (0, or the circle fit's) and the legs of this loop join it.
+ekf_status associate_readings(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, int J, const double* meas_xy, int n_max,
+                              int* known, unsigned flags, int* assoc_out, double* best_out, double* elapsed_ms) {
+    const std::string fn = fnc;
+    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
+    ekf::Dense64LmRecord* drec = d->lm_rec.as<ekf::Dense64LmRecord>();
+    const IniInView ini = view(d->ini_in, L::ini_in_layout());
+    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    double total = elapsed_ms ? *elapsed_ms : 0.0, ms = 0.0;
+    double* pms = elapsed_ms ? &ms : nullptr;
+    // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
+    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    for (int j = 0; j < J; j++) {
+        const double sx = meas_xy[2 * j], sy = meas_xy[2 * j + 1];
+        const int k = *known;
+        SpsView v{};
+        if (k > 0) v = view(d->sps.p, L::sps_layout(k, 2, 5, true, false), false);   // (k <= n_max: inside the buffer)
+        HIPC(hipEventRecord(d->e0, d->stream));
+        if (k > 0) {
+            ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
+            score_sparse_launch(d, v, k, 2, 5, true, true, true);
+        }
+        ekf::launch_dense64_lm_decide(v.nis, k, k, n_max, p.gate_new, p.gate_update, p.sigma0_landmark, d->x, sx, sy, drec,
+                                      ini.W, ini.xb, d->stream);
+        ekf::Dense64LmRecord rec{};
+        EKFC(leg(finish_timed(d, pms, {{&rec, drec, sizeof(rec)}})));
+        if (best_out) best_out[j] = rec.best;
+        if (rec.kind == 0) {   // dropped: nothing at all is written
+            if (assoc_out) assoc_out[j] = -1;
+            continue;
+        }
+        const bool fresh_lm = (rec.kind & ekf::kDense64LmNew) != 0, corrects = (rec.kind & ekf::kDense64LmCorrect) != 0;
+        if (fresh_lm && 3 + 2 * (k + 1) > d->live) {
+            if (!(flags & EKF_DENSE64_LM_GROW_LIVE))
+                return fail(EKF_ERR_INVALID, fn + ": a new landmark does not fit the live dimension (grow it with "
+                                                  "ekf_dense64_set_live, or pass EKF_DENSE64_LM_GROW_LIVE)");
+            EKFC(ekf_dense64_set_live(d, 3 + 2 * (k + 1)));
+        }
+        HIPC(hipEventRecord(d->e0, d->stream));
+        if (fresh_lm) init_block_launch(d, 3 + 2 * k, 2, 0, true, true);   // s = 0, W = sigma0 I, xb
+        if (!corrects) {   // (a gate_update <= 0: the landmark is initialised and not corrected)
+            EKFC(leg(finish_timed(d, pms)));
+            *known = k + 1;
+            if (assoc_out) assoc_out[j] = -1;
+            continue;
+        }
+        // the winner's operands from the current state, that is after an initialisation; the innovation wrapped (:183)
+        ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, rec.win, 1, 1, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu,
+                                     d->stream);
+        correct_sparse_launch(d, deferred, 2, 5, true);
+        ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
+        if (assoc_out) assoc_out[j] = -1;
+        // (a refused correction's launches ran and were timed)
+        const ekf_status st = leg(correct_sparse_finish(d, fnc, deferred, 2, nullptr, pms));
+        if (fresh_lm && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + 1;   // the initialisation stands
+        if (st != EKF_OK) return st;
+        if (assoc_out) assoc_out[j] = rec.win;
+    }
+    return EKF_OK;
 }
 
 }  // namespace
@@ -529,14 +654,7 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
     if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (J < 1) return fail(EKF_ERR_INVALID, fn + ": J must be at least 1");
-    if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
-        return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
-    if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
-    if (3 + 2 * *known > d->live)
-        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
-    if (flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
-        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
-    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
+    EKFC(associate_checks(d, fn, n_max, known, flags));
     const ekf::Params p = landmark_params(params);
     if (elapsed_ms) *elapsed_ms = 0.0;
     for (int j = 0; j < J; j++) {
@@ -544,65 +662,64 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
         if (best_out) best_out[j] = p.gate_new;
     }
     HIPC(hipSetDevice(d->device));
-    EKFC(d->lm_rec.reserve(sizeof(ekf::Dense64LmRecord), d->stream, false, fnc, "the decision record"));
-    if (deferred) EKFC(pend_reserve(d, fnc));
-    // the scoring buffer once, for the full map: a map that is being discovered must not pay a hipMalloc and a hipFree
-    // (a device synchronisation) per new landmark
-    if (n_max > 0) EKFC(sps_reserve(d, L::sps_layout(n_max, 2, 5, true, false).bytes, fnc));
-    ekf::Dense64LmRecord* drec = d->lm_rec.as<ekf::Dense64LmRecord>();
-    const IniInView ini = view(d->ini_in, L::ini_in_layout());
-    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
-    double total = 0.0, ms = 0.0;
-    double* pms = elapsed_ms ? &ms : nullptr;
-    // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
-    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
-    for (int j = 0; j < J; j++) {
-        const double sx = meas_xy[2 * j], sy = meas_xy[2 * j + 1];
-        const int k = *known;
-        SpsView v{};
-        if (k > 0) v = view(d->sps.p, L::sps_layout(k, 2, 5, true, false), false);   // (k <= n_max: inside the buffer)
-        HIPC(hipEventRecord(d->e0, d->stream));
-        if (k > 0) {
-            ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
-            score_sparse_launch(d, v, k, 2, 5, true, true, true);
-        }
-        ekf::launch_dense64_lm_decide(v.nis, k, k, n_max, p.gate_new, p.gate_update, p.sigma0_landmark, d->x, sx, sy, drec,
-                                      ini.W, ini.xb, d->stream);
-        ekf::Dense64LmRecord rec{};
-        EKFC(leg(finish_timed(d, pms, {{&rec, drec, sizeof(rec)}})));
-        if (best_out) best_out[j] = rec.best;
-        if (rec.kind == 0) {   // dropped: nothing at all is written
-            if (assoc_out) assoc_out[j] = -1;
-            continue;
-        }
-        const bool fresh_lm = (rec.kind & ekf::kDense64LmNew) != 0, corrects = (rec.kind & ekf::kDense64LmCorrect) != 0;
-        if (fresh_lm && 3 + 2 * (k + 1) > d->live) {
-            if (!(flags & EKF_DENSE64_LM_GROW_LIVE))
-                return fail(EKF_ERR_INVALID, fn + ": a new landmark does not fit the live dimension (grow it with "
-                                                  "ekf_dense64_set_live, or pass EKF_DENSE64_LM_GROW_LIVE)");
-            EKFC(ekf_dense64_set_live(d, 3 + 2 * (k + 1)));
-        }
-        HIPC(hipEventRecord(d->e0, d->stream));
-        if (fresh_lm) init_block_launch(d, 3 + 2 * k, 2, 0, true, true);   // s = 0, W = sigma0 I, xb
-        if (!corrects) {   // (a gate_update <= 0: the landmark is initialised and not corrected)
-            EKFC(leg(finish_timed(d, pms)));
-            *known = k + 1;
-            if (assoc_out) assoc_out[j] = -1;
-            continue;
-        }
-        // the winner's operands from the current state, that is after an initialisation; the innovation wrapped (:183)
-        ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, rec.win, 1, 1, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu,
-                                     d->stream);
-        correct_sparse_launch(d, deferred, 2, 5, true);
-        ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
-        if (assoc_out) assoc_out[j] = -1;
-        // (a refused correction's launches ran and were timed)
-        const ekf_status st = leg(correct_sparse_finish(d, fnc, deferred, 2, nullptr, pms));
-        if (fresh_lm && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + 1;   // the initialisation stands
-        if (st != EKF_OK) return st;
-        if (assoc_out) assoc_out[j] = rec.win;
+    EKFC(associate_reserve(d, fnc, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
+    return associate_readings(d, fnc, p, J, meas_xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
+}
+
+// ---- a laser scan as the handle's input --------------------------------------------------------------------------------
+ekf_status ekf_dense64_fit_scan(ekf_dense64_handle d, const double* ranges, int n_beams, int max_out, int* count_out,
+                                double* centres_out, double* radii_out, double* all_clusters, int* n_clusters,
+                                double* elapsed_ms) {
+    const char* fn = "ekf_dense64_fit_scan";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!ranges || !count_out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null argument");
+    if (n_beams < 1 || n_beams > kScanBeams || max_out < 1 || max_out > kScanClusters)
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": n_beams must lie in [1, 1024] and max_out in [1, 128]");
+    HIPC(hipSetDevice(d->device));
+    ScanRecord rec{};
+    EKFC(scan_fit(d, fn, ranges, n_beams, max_out, all_clusters != nullptr, elapsed_ms, &rec));
+    *count_out = rec.count;
+    if (n_clusters) *n_clusters = rec.n_clusters;
+    for (int i = 0; i < max_out; i++) {   // entries beyond the count are zero
+        const bool in = i < rec.count;
+        if (centres_out) { centres_out[2 * i] = in ? rec.centres[2 * i] : 0.0; centres_out[2 * i + 1] = in ? rec.centres[2 * i + 1] : 0.0; }
+        if (radii_out) radii_out[i] = in ? rec.radii[i] : 0.0;
     }
+    if (all_clusters)
+        for (int i = 0; i < kScanClusters * 4; i++) all_clusters[i] = i < rec.n_clusters * 4 ? rec.all[i] : 0.0;
     return EKF_OK;
+}
+
+// ekf_dense64_fit_scan, then the loop of ekf_dense64_associate_landmarks on the first min(count, max_readings) centres
+ekf_status ekf_dense64_associate_scan(ekf_dense64_handle d, const ekf_params* params, const double* ranges, int n_beams,
+                                      int max_readings, int n_max, int* known, unsigned flags, int* count_out,
+                                      double* centres_out, int* assoc_out, double* best_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_associate_scan";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kScanClusters)
+        return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 128]");
+    EKFC(associate_checks(d, fn, n_max, known, flags));
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    *count_out = 0;
+    for (int j = 0; j < max_readings; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
+    }
+    HIPC(hipSetDevice(d->device));
+    EKFC(associate_reserve(d, fnc, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
+    ScanRecord rec{};
+    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
+    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
+    *count_out = J;
+    if (J == 0) return EKF_OK;
+    double xy[2 * kScanClusters];   // the loop's launches leave d->scan_rec alone; a copy keeps that out of the argument
+    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
+    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
+    return associate_readings(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
 }
 
 // ---- the reference's prediction() and measurement() on the handle's own state ------------------------------------------

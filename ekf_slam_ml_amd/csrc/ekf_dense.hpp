@@ -199,6 +199,15 @@ void launch_dense64_model_snapshot(const double* state, double* pose, hipStream_
 // boundary) has from `pose` (:114-125), for every i < n_lm; 3 + 2 n_lm <= the state's length (the launcher does not check).
 void launch_dense64_model_init(const double* pose, const double* sensor_xy, int n_lm, double* state, hipStream_t st);
 
+// ---- circle fitting of one laser scan, shaped for latency (ekf_dense64_scan.hip): rigid2d::CircleFitting::
+// approxCirclePositions on ranges [nb] in device memory.  ONE workgroup of four waves: clustering by ballots, one wave per
+// cluster, every sum in an order that depends on the cluster's point count alone.  head [2] = {circles kept, clusters};
+// centres [max_out][2], radii [max_out]: the first max_out circles in cluster order; all_out [clusters][4] = x, y, r,
+// is_circle of every cluster.  7 nb doubles of dynamic LDS.  1 <= nb <= kDense64ScanMaxBeams, 1 <= max_out <=
+// kDense64ScanMaxClusters (the launcher does not check).
+void launch_dense64_scan_circles(const double* ranges, int nb, int max_out, int* head, double* centres, double* radii,
+                                 double* all_out, hipStream_t st);
+
 // ---- the coupling between the live corner and the tail (ekf_dense64_live.hip): over the two rectangles of an N x N Sigma
 // with exactly one index >= Na, the number of entries != 0 and the largest absolute value.  One streaming launch, integer
 // atomics only.  out: two 64-bit words on the device, zero before the launch: the count, and the bits of the maximum.

@@ -15,6 +15,8 @@ constexpr int kDense64MaxS = 64;                     // listed columns of a spar
 constexpr int kDense64ScoreSparseMaxRows = 65536;    // J * m of one sparse scoring call
 constexpr int kDense64PendingMaxRows = 64;           // rows of K and T that wait for the flush
 constexpr int kDense64ReadMax = 65536;               // entries of one block readout
+constexpr int kDense64ScanMaxBeams = 1024;           // beams of one laser scan
+constexpr int kDense64ScanMaxClusters = 128;         // clusters of one scan, and the most circles a call returns
 
 namespace d64 {
 constexpr size_t kF = sizeof(double), kI = sizeof(int), kM = kDense64MaxM, kR = kDense64MaxR, kS = kDense64MaxS;
@@ -62,5 +64,13 @@ inline SpsLayout sps_layout(int J, int m, int s, bool r_shared, bool want_S) {
 // (3 doubles in a 32-byte slot) | the call's readings [n_lm][2], on a 16-byte boundary, when the first call initialises
 struct LmMeasureLayout { size_t pose, xy, bytes; };
 inline LmMeasureLayout lm_measure_layout(int n_lm) { return {0, 4 * kF, 4 * kF + 2 * kF * (size_t)n_lm}; }
+// scan: ranges [1024] | the record that comes down in one copy: head (ints: circles kept, clusters) | centres [128][2] |
+// radii [128] | every cluster's x, y, r, is_circle [128][4], which comes down only when it is asked for
+struct ScanLayout { size_t ranges, head, centres, radii, all, bytes, record_bytes; };
+inline ScanLayout scan_layout() {
+    const size_t nb = kDense64ScanMaxBeams, nc = kDense64ScanMaxClusters, head = kF * nb, centres = head + 2 * kI,
+                 radii = centres + kF * 2 * nc, all = radii + kF * nc;
+    return {0, head, centres, radii, all, all + kF * 4 * nc, all - head};
+}
 }  // namespace d64
 }  // namespace ekf

@@ -82,6 +82,8 @@ inline SpsView view(void* b, const L::SpsLayout& l, bool want_S) {
 }
 struct LmMeasureView { double *pose, *xy; };
 inline LmMeasureView view(void* b, const L::LmMeasureLayout& l) { return {f64(b, l.pose), f64(b, l.xy)}; }
+struct ScanView { double* ranges; int* head; double *centres, *radii, *all; };
+inline ScanView view(void* b, const L::ScanLayout& l) { return {f64(b, l.ranges), i32(b, l.head), f64(b, l.centres), f64(b, l.radii), f64(b, l.all)}; }
 
 // The end of a timed entry point: e1 behind the launches, the launch error, the copies back to the host (a null dst is
 // skipped), ONE synchronisation, the time between the handle's events.
@@ -121,6 +123,9 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf sps;        // SpsLayout (ekf_dense64_score_sparse, the landmark front end), cut per call; LmMeasureLayout
     ekfrt::DeviceBuf pend;       // PendLayout (ekf_dense64_correct_sparse_deferred)
     ekfrt::DeviceBuf lm_rec;     // ekf::Dense64LmRecord, the decision record of one reading (the landmark front end)
+    ekfrt::DeviceBuf scan;       // ScanLayout (ekf_dense64_fit_scan, ekf_dense64_associate_scan)
+    ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
+    std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads
     std::vector<int> host_stamp; // [N] the duplicate check of the index lists
     int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64

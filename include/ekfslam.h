@@ -701,6 +701,58 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle h, const ekf_param
                                            double* best_out,  /* [J] winning score (gate_new when nothing won); nullable */
                                            double* elapsed_ms);
 
+/* A laser scan as the handle's input.  What the reference's robot produces is a LaserScan of 360 ranges; it goes through
+ * nuslam/src/landmarks.cpp:141 and CircleFitting::approxCirclePositions (circle_fitting.cpp:11-304) and reaches
+ * data_association() as a list of circle centres (unknown_data_assoc.cpp:309-320, :414-415).  ekf_circle_fit_scans does that
+ * for thousands of scans at once, bound to no handle and no stream, with six allocations per call and a kernel that gives a
+ * cluster one lane.  These two calls do it for ONE scan on the handle's own device and stream.
+ * THE KERNEL (k_scan_circles) is one workgroup of four waves: every beam computes its own cluster boundary, starts, lengths
+ * and numbers come from ballot words and bit counts (clusters numbered in ascending beam order), the wrap merge follows, and
+ * each cluster is fitted by one WAVE with its points spread over the lanes.  Every quirk of the reference that
+ * ekf_circle_fit_scans keeps is kept: the `i != nb-1` boundary (the last beam always closes a cluster and belongs to none),
+ * "more than 6 points", the merge of the last cluster into the first when their end points are within 0.2, a lone cluster
+ * that merges with itself and vanishes, a scan without a cluster giving 0 circles (undefined in the reference), the
+ * sv[3] < 1e-12 branch, "smallest positive eigenvalue, start 1000", the classification 1.5708 < mean_angle < 2.3562 &&
+ * rad < 0.2, circles kept in cluster order up to max_out; at most 128 clusters, the first ones in beam order.
+ * NUMBERS: the sums run in another order than ekf_circle_fit_scans' and LAPACK's, so nothing is bit-identical to either; the
+ * contract is the one ekf_circle_fit_scans is held to against the checker: the same clusters, the same classification,
+ * kept circles within 1e-9 in centre and radius, the others within 1e-6 relative.  POSITION INDEPENDENCE: every sum over a
+ * cluster's points is a per-lane partial over k = lane, lane + 64, .. followed by a fixed butterfly, so a cluster's row of
+ * all_clusters is a function of its points alone, bit for bit -- not of the wave that fitted it, of its number, or of what
+ * else the scan holds.  No atomics; the same scan gives the same bits on every run.
+ * ekf_dense64_fit_scan: ranges [n_beams] go up through a ring of pinned buffers, one launch, and the record {*count_out,
+ *   *n_clusters, centres, radii} comes down in one copy behind ONE synchronisation; all_clusters ([128][4] = x, y, r,
+ *   is_circle of every cluster, nullable) comes in the same synchronisation when asked for.  centres_out [max_out][2] and
+ *   radii_out [max_out] (nullable) are zero beyond *count_out, all_clusters beyond *n_clusters.  READ-ONLY with respect to
+ *   the filter: the state, Sigma and the pending rows are untouched in bits, nothing is flushed.
+ *   1 <= n_beams <= EKF_DENSE64_SCAN_MAX_BEAMS, 1 <= max_out <= EKF_DENSE64_SCAN_MAX_CIRCLES.  Memory: one device buffer of
+ *   15.2 KB and the ring (8 x 8 KB pinned), reserved by the first call and reused; no later call allocates.
+ * ekf_dense64_associate_scan: ekf_dense64_fit_scan(max_out = max_readings) followed by exactly the per-reading path of
+ *   ekf_dense64_associate_landmarks on the first *count_out = min(circles, max_readings) centres in cluster order: THE RULE,
+ *   COMPOSITION, both flags, the failure semantics and the two synchronisations per reading of that call hold unchanged,
+ *   and the state, Sigma, the pending rows, *known, assoc_out and best_out afterwards are bit for bit those of a twin
+ *   handle on which ekf_dense64_fit_scan and ekf_dense64_associate_landmarks(J = count, centres) are called.  A scan
+ *   without a circle returns EKF_OK with *count_out = 0 after the fit's one synchronisation; nothing of the filter is
+ *   written.  centres_out [max_readings][2] (nullable): the readings, zero beyond the count; assoc_out [max_readings]
+ *   (nullable): as there, -2 beyond the count; best_out [max_readings] (nullable): gate_new beyond it.
+ * FAILURES, checked before the device is looked at, in this order: NULL handle; NULL ranges or count_out (or known);
+ * n_beams, max_out / max_readings out of range; then, for associate_scan, the checks of ekf_dense64_associate_landmarks in
+ * its order (n_max, *known, the live dimension, flag bits) -> EKF_ERR_INVALID, nothing changes.
+ * elapsed_ms (nullable) = HIP-event time of the launches: the circle kernel, plus the readings' as there. */
+#define EKF_DENSE64_SCAN_MAX_BEAMS 1024
+#define EKF_DENSE64_SCAN_MAX_CIRCLES 128
+ekf_status ekf_dense64_fit_scan(ekf_dense64_handle h, const double* ranges /* [n_beams] */, int n_beams, int max_out,
+                                int* count_out, double* centres_out /* [max_out][2] nullable */,
+                                double* radii_out /* [max_out] nullable */,
+                                double* all_clusters /* [128][4] nullable */, int* n_clusters /* nullable */,
+                                double* elapsed_ms);
+ekf_status ekf_dense64_associate_scan(ekf_dense64_handle h, const ekf_params* params,
+                                      const double* ranges /* [n_beams] */, int n_beams, int max_readings,
+                                      int n_max, int* known /* IN/OUT */, unsigned flags,
+                                      int* count_out, double* centres_out /* [max_readings][2] nullable */,
+                                      int* assoc_out /* [max_readings] nullable */,
+                                      double* best_out /* [max_readings] nullable */, double* elapsed_ms);
+
 /* The other two methods of rigid2d::EKF_SLAM on the handle's own state: prediction() (ekf_slam.cpp:55-106) and measurement()
  * (:108-197).  After ekf_dense64_associate_landmarks the heading lives on the device only -- it is corrected there and
  * nothing is read back -- so a caller of the model-free ekf_dense64_propagate_block would fetch state[0], evaluate four

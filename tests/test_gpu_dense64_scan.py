@@ -1,0 +1,343 @@
+"""GPU: a laser scan as the dense fp64 handle's input -- ekf_dense64_fit_scan (k_scan_circles: one workgroup, clustering by
+ballots, a wave per cluster) and ekf_dense64_associate_scan (the fit, then associate_landmarks' per-reading path).  The fit is
+held to the checker with the tolerances tests/test_gpu_circles.py holds k_circles to (clusters and classification identical,
+circles within 1e-9, the others within 1e-6 relative) and to k_circles itself; where the checker has undefined behaviour or
+no say (fewer beams than a cluster, NaN and inf ranges) to k_circles alone.  The bit-level claims are tested as such:
+position independence on a cluster that changes wave, number and place; read-only on state, Sigma and the pending rows; the
+association against a twin handle driven by fit_scan + associate_landmarks.  tests/test_dense64_scan_host.py shows that no
+simulated scan has a cluster within 1e-9 of a classification threshold, so nothing is left out of that comparison."""
+import ctypes as C
+import time
+
+import numpy as np
+import pytest
+
+import dense_landmark_cases as lc
+import dense_scan_cases as sc
+from parity import FP64_TOL, worst
+from test_circle_oracle import RANGES
+
+pytestmark = pytest.mark.gpu
+INVALID = 1
+
+
+def _bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _handle(hip, x, S, pending=0, carry=False, live=None):
+    """a handle with the state x, the covariance S, the live dimension `live` and `pending` rows left by a seeded deferred
+    correction inside it; built twice it holds the same bits twice"""
+    d = hip.DensePropagator64(len(x))
+    d.set(Sigma=S)
+    if live is not None:
+        d.live = live
+    if pending:
+        rng = np.random.default_rng(55)
+        cols = rng.choice(d.live, size=5, replace=False)
+        d.correct_sparse_deferred(cols, 0.1 * rng.standard_normal((pending, 5)), np.eye(pending),
+                                  0.01 * rng.standard_normal(pending))
+    assert d.pending == pending
+    d.state = x
+    d.carry = carry
+    return d
+
+
+def _snapshot(d):
+    """pending count, state, and Sigma after a flush"""
+    p = d.pending
+    d.flush()
+    return p, d.state, d.sigma
+
+
+def _same(got, want):
+    assert got[0] == want[0], (got[0], want[0])
+    assert _bits(got[1], want[1]), np.argwhere(got[1] != want[1])[:4]
+    assert _bits(got[2], want[2]), np.argwhere(got[2] != want[2])[:4]
+
+
+@pytest.fixture(scope="module")
+def dev(hip):
+    d = hip.DensePropagator64(23)
+    yield d
+    d.close()
+
+
+@pytest.fixture(scope="module")
+def sim(oracle):
+    """the 300 simulated scans and what the checker makes of them, computed once"""
+    _, scans = sc.simulated_scans()
+    return scans, [oracle.approx_circle_positions(r, max_out=32) for r in scans]
+
+
+def _hold(got, want, what, structure_only=False):
+    """(centres, radii, all) against (centres, radii, all): the tolerances of tests/test_gpu_circles.py"""
+    cen, rad, allc = got
+    c_o, r_o, a_o = want
+    assert len(allc) == len(a_o), f"{what}: cluster count {len(allc)} != {len(a_o)}"
+    assert np.array_equal(allc[:, 3], a_o[:, 3]), f"{what}: classification"
+    assert len(cen) == len(c_o) == len(rad), what
+    if structure_only:
+        return 0.0, 0.0
+    circ = notc = 0.0
+    if len(c_o):
+        circ = max(np.abs(cen - c_o).max(), np.abs(rad - r_o).max())
+        assert circ < 1e-9, f"{what}: circles {circ:.3e}"
+    no = a_o[:, 3] == 0
+    if no.any():
+        notc = np.abs(allc[no, :3] - a_o[no, :3]).max() / (1.0 + np.abs(a_o[no, :3]).max())
+        assert notc <= 1e-6, f"{what}: non-circles {notc:.3e}"
+    return circ, notc
+
+
+def _fit(d, r, max_out=32):
+    cen, rad, allc, _ = d.fit_scan(r, max_out=max_out, want_all=True)
+    return cen, rad, allc
+
+
+def _kc(hip, r, max_out=32):
+    cen, rad, allc = hip.circle_fit_scans(r, max_out=max_out, want_all=True)
+    return cen[0], rad[0], allc[0]
+
+
+# ---- 1. the checker and k_circles ---------------------------------------------------------------------------------------------
+
+def test_simulated_scans_against_the_checker(dev, sim):
+    scans, want = sim
+    worst_c = worst_n = 0.0
+    circles = 0
+    for s, r in enumerate(scans):
+        c, n = _hold(_fit(dev, r), want[s], f"scan {s}")
+        worst_c, worst_n, circles = max(worst_c, c), max(worst_n, n), circles + len(want[s][0])
+    print(f"300 scans against the checker: circles {worst_c:.3e}, non-circles {worst_n:.3e} relative, {circles} circles")
+    assert circles > 300
+
+
+def test_simulated_scans_against_k_circles(hip, dev, sim):
+    scans, _ = sim
+    cen, rad, allc = hip.circle_fit_scans(scans, max_out=32, want_all=True)
+    worst_c = 0.0
+    for s, r in enumerate(scans):
+        got = _fit(dev, r)
+        _hold(got, (cen[s], rad[s], allc[s]), f"scan {s}", structure_only=True)
+        if len(cen[s]):
+            worst_c = max(worst_c, np.abs(got[0] - cen[s]).max(), np.abs(got[1] - rad[s]).max())
+    print(f"300 scans against k_circles: circles {worst_c:.3e}")
+    assert worst_c < 1e-9
+
+
+@pytest.mark.parametrize("nb", [90, 720, 1024])
+def test_other_beam_counts(dev, oracle, nb):
+    for s, r in enumerate(sc.beam_count_scans(nb)):
+        _hold(_fit(dev, r), oracle.approx_circle_positions(r), f"{nb} beams, scan {s}")
+
+
+def test_reference_kat_scan(dev, oracle):
+    # nuslam/tests/circle_tests.cpp:8-22,65-76: two clusters, none classified as a circle
+    got = _fit(dev, np.array(RANGES))
+    assert len(got[0]) == 0 and len(got[2]) == 2 and not got[2][:, 3].any()
+    _hold(got, oracle.approx_circle_positions(np.array(RANGES)), "KAT")
+
+
+# ---- 2. edges --------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nb", [1, 7, 8, 64, 65])
+def test_few_beams_against_k_circles(hip, dev, nb):
+    """fewer beams than a cluster needs, exactly enough for one of 7, one and two ballot words"""
+    for name, r in (("flat", np.full(nb, 1.0)), ("ramp", sc.ramp_scan(nb)), ("saw", sc.saw(nb))):
+        got, want = _fit(dev, r), _kc(hip, r)
+        _hold(got, want, f"{name}, {nb} beams")
+        assert len(got[2]) == len(sc.np_clusters(r)), (name, nb)
+    assert len(_fit(dev, sc.ramp_scan(8))[2]) == 1 and len(_fit(dev, sc.ramp_scan(7))[2]) == 0
+
+
+@pytest.mark.parametrize("case", ["len6", "len7", "len65", "len129", "len300", "many", "flat", "wrap", "saw"])
+def test_edge_scans_against_the_checker(dev, oracle, case):
+    n = 360
+    wrap = np.full(n, 3.0); wrap[:10] = 1.0; wrap[-12:] = 1.05
+    r = {"len6": lambda: sc.length_scan(6), "len7": lambda: sc.length_scan(7), "len65": lambda: sc.long_cluster_scan(65),
+         "len129": lambda: sc.long_cluster_scan(129), "len300": lambda: sc.long_cluster_scan(300),
+         "many": sc.many_clusters_scan, "flat": lambda: np.full(n, 1.0), "wrap": lambda: wrap, "saw": lambda: sc.saw(n)}[case]()
+    got, want = _fit(dev, r), oracle.approx_circle_positions(r)
+    c, nn = _hold(got, want, case)
+    print(f"{case}: {len(want[2])} clusters, {len(want[0])} circles; circles {c:.3e}, non-circles {nn:.3e}")
+    assert len(got[2]) == {"len6": 1, "len7": 2, "len65": 2, "len129": 2, "len300": 2, "many": 20, "flat": 0, "wrap": 2,
+                           "saw": 0}[case]
+
+
+def test_max_out_keeps_the_first_circles(dev, oracle):
+    r = sc.circles_scan(3)
+    full = _fit(dev, r)
+    assert len(full[0]) == 3
+    for max_out in (1, 2):
+        cen, rad, allc = _fit(dev, r, max_out)
+        assert _bits(cen, full[0][:max_out]) and _bits(rad, full[1][:max_out]) and _bits(allc, full[2])
+    with pytest.raises(ValueError):
+        dev.fit_scan(r, max_out=129)
+
+
+def test_nan_and_inf_ranges_against_k_circles(hip, dev, sim):
+    r = sim[0][3].copy()
+    r[50], r[200], r[201] = np.nan, np.inf, np.inf
+    got, want = _fit(dev, r), _kc(hip, r)
+    assert len(got[2]) == len(want[2]) > 0 and np.isfinite(got[2]).all() and np.isfinite(want[2]).all()
+    _hold(got, want, "NaN and inf")
+
+
+# ---- 3. position independence, in bits ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nb,length", [(360, 9), (1024, 129)])
+def test_position_independence(dev, nb, length):
+    rows = []
+    for r, number in sc.position_scans(nb, length):
+        allc = _fit(dev, r)[2]
+        rows.append(allc[number].copy())
+        assert _bits(_fit(dev, r)[2], allc)                                    # two runs of the same call
+    assert np.isfinite(rows[0]).all()
+    assert _bits(rows[0], rows[1]) and _bits(rows[0], rows[2]), rows
+
+
+# ---- 4. read-only ----------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("pending", [0, 2])
+def test_fit_scan_is_read_only(hip, sim, pending):
+    x, S = lc.spiral_map(10)
+    d, ref = _handle(hip, x, S, pending), _handle(hip, x, S, pending)
+    for r in (sim[0][0], sc.circles_scan(3), sc.saw(360)):
+        d.fit_scan(r)
+    assert d.pending == pending
+    assert _bits(d.state, ref.state)
+    _same(_snapshot(d), _snapshot(ref))
+    d.close(); ref.close()
+
+
+# ---- 5. association against a twin --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mode", ["eager", "deferred", "deferred_grow_carry"])
+@pytest.mark.parametrize("circles,max_readings", [(0, 64), (1, 64), (3, 64), (3, 1)])
+def test_associate_scan_twin(hip, mode, circles, max_readings):
+    n, known0 = 10, 4
+    x, S = lc.spiral_map(n)                                                    # N = 23
+    x[3:5] = x[:3][1:] + np.array([1.25, 0.0])                                 # landmark 0 near where the first tube is seen
+    deferred, grow = mode != "eager", mode == "deferred_grow_carry"
+    live = 3 + 2 * known0 if grow else None
+    a, b = (_handle(hip, x, S, 2 if deferred else 0, grow, live) for _ in range(2))
+    r = sc.circles_scan(circles)
+    ka, cen, assoc, best = a.associate_scan(r, known0, n, max_readings, deferred, grow)
+    cen_b, _, _ = b.fit_scan(r, max_out=max_readings)
+    want = min(circles, max_readings)
+    assert len(cen) == len(assoc) == len(best) == want and _bits(cen, cen_b)
+    kb = known0
+    if want:
+        kb, assoc_b, best_b, _ = b.associate_landmarks(cen_b, known0, n, deferred, grow)
+        assert _bits(assoc, assoc_b) and _bits(best, best_b), (assoc, assoc_b)
+        assert (assoc >= 0).any()
+    assert ka == kb and a.live == b.live
+    if not want:
+        assert ka == known0
+    _same(_snapshot(a), _snapshot(b))
+    if want:
+        assert not _bits(a.state, x)
+    else:
+        assert _bits(a.state, x)                                               # nothing of the filter was written
+    a.close(); b.close()
+
+
+# ---- 6. argument checks ----------------------------------------------------------------------------------------------------------
+
+def test_scan_refusals_change_nothing(hip):
+    n = 10
+    x, S = lc.spiral_map(n)
+    live = 3 + 2 * 8
+    d, ref = _handle(hip, x, S, 2, live=live), _handle(hip, x, S, 2, live=live)
+    lib, h = d._lib, d._h
+    r = (C.c_double * 360)(*sc.circles_scan(3))
+    cnt, known = C.c_int(-7), C.c_int(4)
+
+    def fit(hh, rr, nb, mo, cc):
+        return lib.ekf_dense64_fit_scan(hh, rr, nb, mo, cc, None, None, None, None, None), lib.ekf_last_error()
+
+    def asc(hh, rr, nb, mr, nmax, kk, flags, cc):
+        return (lib.ekf_dense64_associate_scan(hh, None, rr, nb, mr, nmax, kk, flags, cc, None, None, None, None),
+                lib.ekf_last_error())
+
+    def refused(res, text):
+        assert res[0] == INVALID and text in res[1], res
+
+    # each check, and in front of it the one that comes before: the first of two faults is the one reported
+    refused(fit(None, None, 0, 0, None), b"null handle")
+    refused(fit(h, None, 0, 0, C.byref(cnt)), b"null argument")
+    refused(fit(h, r, 0, 0, None), b"null argument")
+    for nb, mo in ((0, 32), (1025, 32), (-1, 32), (360, 0), (360, 129)):
+        refused(fit(h, r, nb, mo, C.byref(cnt)), b"n_beams must lie")
+    refused(asc(None, None, 0, 0, -1, None, 4, None), b"null handle")
+    refused(asc(h, None, 0, 0, -1, C.byref(known), 4, C.byref(cnt)), b"null argument")
+    refused(asc(h, r, 0, 0, -1, C.byref(known), 4, None), b"null argument")
+    refused(asc(h, r, 0, 0, -1, None, 4, C.byref(cnt)), b"null argument")
+    for nb, mr in ((0, 32), (1025, 32), (360, 0), (360, 129)):
+        refused(asc(h, r, nb, mr, -1, C.byref(known), 4, C.byref(cnt)), b"n_beams must lie")
+    bad_known, beyond_live = C.c_int(11), C.c_int(9)
+    refused(asc(h, r, 360, 32, -1, C.byref(bad_known), 4, C.byref(cnt)), b"n_max must lie")
+    refused(asc(h, r, 360, 32, 11, C.byref(known), 4, C.byref(cnt)), b"n_max must lie")
+    refused(asc(h, r, 360, 32, n, C.byref(bad_known), 4, C.byref(cnt)), b"*known must lie")
+    refused(asc(h, r, 360, 32, n, C.byref(beyond_live), 4, C.byref(cnt)), b"inside the live dimension")
+    refused(asc(h, r, 360, 32, n, C.byref(known), 4, C.byref(cnt)), b"unknown flag bits")
+    assert (cnt.value, known.value, bad_known.value, beyond_live.value) == (-7, 4, 11, 9)
+    _same(_snapshot(d), _snapshot(ref))
+    assert len(d.fit_scan(np.array(r))[0]) == 3                                # and the handle works
+    d.close(); ref.close()
+
+
+# ---- 7. the two nodes of the reference, end to end ---------------------------------------------------------------------------
+
+def test_scan_to_filter_pipeline(hip, oracle):
+    """the 60 ticks of tests/test_gpu_circles.py::test_scan_to_filter_pipeline through DenseEKFSLAM.prediction +
+    scan_association against the checker's approx_circle_positions + data_association"""
+    from ekf_slam_ml_amd import synth
+    cfg = synth.config1(steps=60)
+    cfg.seed = 99
+    log = synth.make_unknown_log(cfg)
+    world = np.stack([synth.TUBE_X, synth.TUBE_Y], axis=1)
+    scans = synth.make_scans(log.true_pose[:, 0], world=world, seed=5)
+    n = 10
+    f, o = hip.DenseEKFSLAM(n), oracle.OracleEKF(n, oracle.DENSE)
+    ko = np.zeros(n, dtype=np.uint8)
+    for t in range(60):
+        c_o, _, _ = oracle.approx_circle_positions(scans[t])
+        f.prediction(*log.twist[t, 0]); o.prediction(*log.twist[t, 0])
+        cen, a = f.scan_association(scans[t])
+        b = o.data_association(c_o, ko)
+        assert len(cen) == len(c_o) and (len(c_o) == 0 or np.abs(cen - c_o).max() < 1e-9), t
+        assert np.array_equal(a, b), (t, a, b)
+        assert f.known == int(ko.sum()) and ko[:f.known].all(), (t, f.known, ko)
+    assert f.known >= 4
+    w, e = worst(f.state, f.handle.sigma, o.state, o.cov)
+    f.close()
+    print(f"scan -> circles -> association through DenseEKFSLAM, 60 ticks: {w:.3e}")
+    assert w <= FP64_TOL, e
+
+
+# ---- 8. the call against the one it replaces ---------------------------------------------------------------------------------
+
+def test_fit_scan_is_quicker_than_the_unbound_call(hip, dev, sim):
+    """wall clock of fit_scan against ekf_circle_fit_scans(S = 1) -- six allocations, three memsets, up to six blocking copies
+    and six frees per call -- on the same scan in the same process: medians of 9 after 2, with the margin of the larger
+    spread (max - min) of the two sets of nine"""
+    r = sim[0][0]
+
+    def nine(call):
+        for _ in range(2):
+            call()
+        out = []
+        for _ in range(9):
+            t0 = time.perf_counter()
+            call()
+            out.append(time.perf_counter() - t0)
+        return np.median(out), max(out) - min(out)
+
+    new, new_spread = nine(lambda: dev.fit_scan(r, max_out=32))
+    old, old_spread = nine(lambda: hip.circle_fit_scans(r, max_out=32))
+    print(f"fit_scan {1e3 * new:.3f} ms (spread {1e3 * new_spread:.3f}), ekf_circle_fit_scans(S = 1) {1e3 * old:.3f} ms "
+          f"(spread {1e3 * old_spread:.3f})")
+    assert new < old + max(new_spread, old_spread)
