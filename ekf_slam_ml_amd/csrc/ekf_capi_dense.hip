@@ -1,6 +1,6 @@
-// ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: the fp32 handle (configs[3],
-// ekf_dense.hip) and what its fp64 twin (ekf_dense64.hip) shares with it.  create, destroy, set, propagate, get_sigma,
-// launch_info and tile_map of the two handles are one template over the element type, the kernels stay separate; what a
+// ekf_capi_dense.hip -- C ABI of include/ekfslam.h, dense general-F covariance propagation: the fp32 handle (configs[3])
+// and what its fp64 twin shares with it.  create, destroy, set, propagate, get_sigma, launch_info and tile_map of the two
+// handles are one template over the element type, and so are the kernels behind them (ekf_dense.hip); what a
 // handle owns beyond Sigma it sets up, releases and keeps consistent in the hooks of ekf_dense_handle.hpp.  Everything else
 // the fp64 handle can do is in ekf_capi_dense64.hip.
 #include "ekf_dense_handle.hpp"
@@ -9,24 +9,8 @@ using namespace ekfrt;
 
 namespace {
 
-// per element type: the launcher, the split report and the LDS-limit set-up of ekf_dense.hpp
-struct DenseOps32 {
-    static hipError_t prepare() { return ekf::dense_gemm_prepare(); }
-    static void gemm(const float* A, const float* B, float* C, const float* Qadd, int ld, bool bt, hipStream_t s, int n) {
-        ekf::launch_dense_gemm(A, B, C, Qadd, ld, bt, s, n);
-    }
-    static void split(int ld, int* tiles, int* n_big, int* n_tail) { ekf::dense_gemm_split(ld, tiles, n_big, n_tail); }
-    static void tile_map(int ld, unsigned char* map) { ekf::dense_gemm_tile_map(ld, map); }
-};
-struct DenseOps64 {
-    static hipError_t prepare() { return ekf::dense64_gemm_prepare(); }
-    static void gemm(const double* A, const double* B, double* C, const double* Qadd, int ld, bool bt, hipStream_t s,
-                     int n) {
-        ekf::launch_dense64_gemm(A, B, C, Qadd, ld, bt, s, n);
-    }
-    static void split(int ld, int* tiles, int* n_big, int* n_tail) { ekf::dense64_gemm_split(ld, tiles, n_big, n_tail); }
-    static void tile_map(int ld, unsigned char* map) { ekf::dense64_gemm_tile_map(ld, map); }
-};
+// the element type of a handle: what picks the instantiation of the launcher, the split report and the LDS-limit set-up
+template <class H> using elem_t = std::remove_pointer_t<decltype(H::F)>;
 
 template <class H>
 ekf_status dense_destroy(H* d) {
@@ -43,7 +27,7 @@ ekf_status dense_destroy(H* d) {
     return EKF_OK;
 }
 
-template <class H, class Ops>
+template <class H>
 ekf_status dense_create(const char* name, int N, int device, H** out) {
     if (!out || N <= 0) return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
     *out = nullptr;
@@ -66,7 +50,7 @@ ekf_status dense_create(const char* name, int N, int device, H** out) {
     auto body = [&]() -> ekf_status {
         HIPC(hipSetDevice(device));
         HIPC(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-        HIPC(Ops::prepare());
+        HIPC(ekf::dense_gemm_prepare<elem_t<H>>());
         for (auto** p : {&d->F, &d->S, &d->T, &d->Q}) {
             HIPC(hipMalloc((void**)p, bytes));
             HIPC(hipMemsetAsync(*p, 0, bytes, d->stream));
@@ -100,31 +84,31 @@ ekf_status dense_set(H* d, const E* F, const E* Sigma, const E* Q) {
     return EKF_OK;
 }
 
-template <class Ops, class H>
+template <class H>
 ekf_status dense_propagate(const char* name, H* d, int iterations, double* elapsed_ms) {
     if (!d || iterations < 0) return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
     HIPC(hipSetDevice(d->device));
     HIPC(hipEventRecord(d->e0, d->stream));
     d->sigma_needed();
     for (int it = 0; it < iterations; it++) {
-        Ops::gemm(d->F, d->S, d->T, nullptr, d->ld, false, d->stream, d->N);  // T = At*sigma (:102)
-        Ops::gemm(d->T, d->F, d->S, d->Q, d->ld, true, d->stream, d->N);      // sigma = T*At.t() + Q
+        ekf::launch_dense_gemm<elem_t<H>>(d->F, d->S, d->T, nullptr, d->ld, false, d->stream, d->N);  // T = At*sigma (:102)
+        ekf::launch_dense_gemm<elem_t<H>>(d->T, d->F, d->S, d->Q, d->ld, true, d->stream, d->N);      // sigma = T*At.t() + Q
     }
     return finish_timed(d, elapsed_ms);
 }
 
-template <class Ops, class H>
+template <class H>
 ekf_status dense_launch_info(H* d, int* ld, int* tiles, int* n_big, int* n_tail) {
     if (!d) return fail(EKF_ERR_INVALID, "null handle");
     if (ld) *ld = d->ld;
-    Ops::split(d->ld, tiles, n_big, n_tail);
+    ekf::dense_gemm_split<elem_t<H>>(d->ld, tiles, n_big, n_tail);
     return EKF_OK;
 }
 
-template <class Ops, class H>
+template <class H>
 ekf_status dense_tile_map(H* d, unsigned char* map) {
     if (!d || !map) return fail(EKF_ERR_INVALID, "null argument");
-    Ops::tile_map(d->ld, map);
+    ekf::dense_gemm_tile_map<elem_t<H>>(d->ld, map);
     return EKF_OK;
 }
 
@@ -144,35 +128,35 @@ ekf_status dense_get_sigma(H* d, E* out) {
 extern "C" {
 
 ekf_status ekf_dense_create(int N, int device, ekf_dense_handle* out) {
-    return dense_create<ekf_dense_s, DenseOps32>("ekf_dense_create", N, device, out);
+    return dense_create<ekf_dense_s>("ekf_dense_create", N, device, out);
 }
 ekf_status ekf_dense_destroy(ekf_dense_handle d) { return dense_destroy(d); }
 ekf_status ekf_dense_set(ekf_dense_handle d, const float* F, const float* Sigma, const float* Q) {
     return dense_set(d, F, Sigma, Q);
 }
 ekf_status ekf_dense_propagate(ekf_dense_handle d, int iterations, double* elapsed_ms) {
-    return dense_propagate<DenseOps32>("ekf_dense_propagate", d, iterations, elapsed_ms);
+    return dense_propagate("ekf_dense_propagate", d, iterations, elapsed_ms);
 }
 ekf_status ekf_dense_launch_info(ekf_dense_handle d, int* ld, int* tiles, int* n_big, int* n_tail) {
-    return dense_launch_info<DenseOps32>(d, ld, tiles, n_big, n_tail);
+    return dense_launch_info(d, ld, tiles, n_big, n_tail);
 }
-ekf_status ekf_dense_tile_map(ekf_dense_handle d, unsigned char* map) { return dense_tile_map<DenseOps32>(d, map); }
+ekf_status ekf_dense_tile_map(ekf_dense_handle d, unsigned char* map) { return dense_tile_map(d, map); }
 ekf_status ekf_dense_get_sigma(ekf_dense_handle d, float* out) { return dense_get_sigma(d, out); }
 
 ekf_status ekf_dense64_create(int N, int device, ekf_dense64_handle* out) {
-    return dense_create<ekf_dense64_s, DenseOps64>("ekf_dense64_create", N, device, out);
+    return dense_create<ekf_dense64_s>("ekf_dense64_create", N, device, out);
 }
 ekf_status ekf_dense64_destroy(ekf_dense64_handle d) { return dense_destroy(d); }
 ekf_status ekf_dense64_set(ekf_dense64_handle d, const double* F, const double* Sigma, const double* Q) {
     return dense_set(d, F, Sigma, Q);
 }
 ekf_status ekf_dense64_propagate(ekf_dense64_handle d, int iterations, double* elapsed_ms) {
-    return dense_propagate<DenseOps64>("ekf_dense64_propagate", d, iterations, elapsed_ms);
+    return dense_propagate("ekf_dense64_propagate", d, iterations, elapsed_ms);
 }
 ekf_status ekf_dense64_launch_info(ekf_dense64_handle d, int* ld, int* tiles, int* n_big, int* n_tail) {
-    return dense_launch_info<DenseOps64>(d, ld, tiles, n_big, n_tail);
+    return dense_launch_info(d, ld, tiles, n_big, n_tail);
 }
-ekf_status ekf_dense64_tile_map(ekf_dense64_handle d, unsigned char* map) { return dense_tile_map<DenseOps64>(d, map); }
+ekf_status ekf_dense64_tile_map(ekf_dense64_handle d, unsigned char* map) { return dense_tile_map(d, map); }
 ekf_status ekf_dense64_get_sigma(ekf_dense64_handle d, double* out) { return dense_get_sigma(d, out); }
 
 }  // extern "C"

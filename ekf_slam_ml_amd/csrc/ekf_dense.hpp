@@ -1,35 +1,31 @@
-// ekf_dense.hpp -- the launchers of the dense handles' kernels: the fp32 MFMA GEMM of the dense covariance propagation
-// (ekf_dense.hip), its fp64 twin (ekf_dense64.hip), and every other kernel file of the fp64 handle (ekf_dense64_*.hip), one
-// section each.  The limits of the fp64 calls (kDense64Max*) come from ekf_dense64_layout.hpp.
+// ekf_dense.hpp -- the launchers of the dense handles' kernels: the MFMA GEMM of the dense covariance propagation, one
+// template over the element type for the fp32 and the fp64 handle (ekf_dense.hip, kernels in ekf_dense_gemm.hpp), and every
+// other kernel file of the fp64 handle (ekf_dense64_*.hip), one section each.  The limits of the fp64 calls (kDense64Max*)
+// come from ekf_dense64_layout.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "ekf_dense64_layout.hpp"
+#include "ekf_dense_split.hpp"   // kDenseTile = 128: ld must be a multiple of it
 
 namespace ekf {
-constexpr int kDenseTile = 128;  // ld must be a multiple of this
-// C[ld x ld] = A * B (+ Qadd), all row-major fp32 with zero padding up to ld.
+// ---- the GEMM of the propagation, E = float (v_mfma_f32_32x32x2_f32) or double (v_mfma_f64_16x16x4_f64); instantiated for
+// these two in ekf_dense.hip.
+// C[ld x ld] = A * B (+ Qadd), all row-major with zero padding up to ld.
 // b_transposed: B is supplied as Bt[j][k] (i.e. C = A * Bt^T).
 // n_rows (0 = ld): rows of C that are not padding; A's rows from there on are zero and C's were allocated zero.
-void launch_dense_gemm(const float* A, const float* B, float* C, const float* Qadd, int ld, bool b_transposed,
-                       hipStream_t s, int n_rows = 0);
-// how launch_dense_gemm cuts a product: *tiles = ld / 128; n_big tiles of 256 x 128 on the main kernel (k_gemm_f32_big,
-// whole rounds of resident workgroups); n_rem tiles of 128 x 128 -- the rest of the big-tile list and the bottom strip of
-// an ld that is an odd multiple of 128 -- done as 4 * n_rem quarter tiles (k_gemm_f32_tail)
-void dense_gemm_split(int ld, int* tiles, int* n_big, int* n_rem);
+template <class E>
+void launch_dense_gemm(const E* A, const E* B, E* C, const E* Qadd, int ld, bool b_transposed, hipStream_t s, int n_rows = 0);
+// how launch_dense_gemm cuts a product (ekf_dense_split.hpp): *tiles = ld / 128; n_big main tiles -- 256 x 128 in fp32,
+// 128 x 128 in fp64 -- on the main kernel (k_gemm_big, whole rounds of resident workgroups); n_rem tiles of 128 x 128 -- the
+// rest of the main-tile list and, in fp32, the bottom strip of an ld that is an odd multiple of 128 -- done as 4 * n_rem
+// quarter tiles of 64 x 64 (k_gemm_tail) behind it
+template <class E> void dense_gemm_split(int ld, int* tiles, int* n_big, int* n_rem);
 // map [tiles][tiles] over the 128 x 128 blocks of C: 0 = computed by the main kernel, 1 = by the tail kernel (255 never)
-void dense_gemm_tile_map(int ld, unsigned char* map);
-hipError_t dense_gemm_prepare();  // raises the dynamic-LDS limit of the main kernel (49.4 KB per workgroup)
-
-// ---- fp64 twin (ekf_dense64.hip): the same contract with double operands, on v_mfma_f64_16x16x4_f64.
-// *tiles = ld / 128; n_big tiles of 128 x 128 on the main kernel (k_gemm_f64_big, whole rounds of resident workgroups);
-// n_rem tiles of 128 x 128 left over, done as 4 * n_rem quarter tiles of 64 x 64 (k_gemm_f64_tail) behind it.
-void launch_dense64_gemm(const double* A, const double* B, double* C, const double* Qadd, int ld, bool b_transposed,
-                         hipStream_t s, int n_rows = 0);
-void dense64_gemm_split(int ld, int* tiles, int* n_big, int* n_rem);
-void dense64_gemm_tile_map(int ld, unsigned char* map);   // as dense_gemm_tile_map
-hipError_t dense64_gemm_prepare();  // raises the dynamic-LDS limit of the main kernel (64.8 KiB per workgroup)
+template <class E> void dense_gemm_tile_map(int ld, unsigned char* map);
+// raises the dynamic-LDS limit of the main kernel (49.4 KB per workgroup in fp32, 64.8 KiB in fp64)
+template <class E> hipError_t dense_gemm_prepare();
 
 // ---- fp64 dense measurement update for a general m x N Jacobian (ekf_dense64_correct.hip), on the same ld x ld Sigma:
 //   T = H Sigma, U = Sigma H^T, S = T H^T + R, K = U S^-1, state += K nu, Sigma <- Sigma - K T, nis = nu^T S^-1 nu.

@@ -22,17 +22,15 @@
 //                   from the (cache-resident) K^T panel, T from LDS, k = m rounded up to 4 with zero fill
 // Launches 5 and 6 read the verdict on the device and return before their first write when it is set, so state and Sigma
 // stay exactly as they were and the host needs one synchronisation per correction, not two.
-// Lane maps of v_mfma_f64_16x16x4_f64 (as gemm64_tile in ekf_dense64.hip): A: lane l holds A[i = l & 15][k = l >> 4];
+// Lane maps of v_mfma_f64_16x16x4_f64 (as GemmTraits<double> in ekf_dense_gemm.hpp): A: lane l holds A[i = l & 15][k = l >> 4];
 // B: B[k = l >> 4][j = l & 15]; C/D: col = l & 15, row = (l >> 4) + 4 * reg.
 #include <hip/hip_runtime.h>
 
 #include "ekf_dense.hpp"
+#include "ekf_dense_gemm.hpp"   // f64x4, f64x2, GemmTraits<double>::mfma
 #include "ekf_dense64_invert.hpp"
 
 namespace ekf {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -42,10 +40,6 @@ constexpr int kTileS = kTile + 2;     // LDS row stride: 2 (mod 32) doubles -> t
 constexpr int kStripTiles = 4;        // column tiles per super-tile (strip = 256 columns)
 constexpr int kUpdCols = 128;         // column strip of the rank-m update
 constexpr int kGainRows = 32;         // rows of K per workgroup of the gain kernel
-
-__device__ __forceinline__ f64x4 mfma64(double a, double b, f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // ---- 1: panels --------------------------------------------------------------------------------------------------------
 // Ht: H transposed, [ld][16 MB] (k contiguous; MB = m rounded up to 16, in sixteens), zero for k >= m and for rows >= N.
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(256) void k_dc_panels(const double* __restrict__ S,
                     const double b = tile[(4 * s + lk) * kTileS + 16 * w + li];
 #pragma unroll
                     for (int kb = 0; kb < MB; kb++)
-                        accT[ct][kb] = mfma64(hr[(4 * s + lk) * HS + 16 * kb + li], b, accT[ct][kb]);
+                        accT[ct][kb] = GemmTraits<double>::mfma(hr[(4 * s + lk) * HS + 16 * kb + li], b, accT[ct][kb]);
                 }
                 // U^T[k][i] += H[k][j] Sigma[i][j]: wave w owns the 16 rows i = 16 w + (0..15) of the tile
 #pragma unroll 4
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(256) void k_dc_panels(const double* __restrict__ S,
                     const double b = tile[(16 * w + li) * kTileS + 4 * s + lk];
 #pragma unroll
                     for (int kb = 0; kb < MB; kb++)
-                        accU[kb] = mfma64(hc[(4 * s + lk) * HS + 16 * kb + li], b, accU[kb]);
+                        accU[kb] = GemmTraits<double>::mfma(hc[(4 * s + lk) * HS + 16 * kb + li], b, accU[kb]);
                 }
             }
         }
@@ -354,8 +348,8 @@ __global__ __launch_bounds__(256) void k_dc_update(double* __restrict__ S, const
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const f64x2 tv = *reinterpret_cast<const f64x2*>(dc_smem + k * kUpdCols + 32 * g + 2 * li);
-                ae[g] = mfma64(a, tv[0], ae[g]);
-                ao[g] = mfma64(a, tv[1], ao[g]);
+                ae[g] = GemmTraits<double>::mfma(a, tv[0], ae[g]);
+                ao[g] = GemmTraits<double>::mfma(a, tv[1], ao[g]);
             }
         }
         double* base = S + (size_t)(b * 16 + lk) * ld + c0 + 2 * li;

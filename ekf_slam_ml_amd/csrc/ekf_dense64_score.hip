@@ -22,12 +22,10 @@
 #include <hip/hip_runtime.h>
 
 #include "ekf_dense.hpp"
+#include "ekf_dense_gemm.hpp"   // f64x4, f64x2, GemmTraits<double>::mfma
 #include "ekf_dense64_invert.hpp"
 
 namespace ekf {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -36,10 +34,6 @@ constexpr int kGroup = kDense64ScoreGroup;   // rows of H per group
 constexpr int kTile = 64;
 constexpr int kTileS = kTile + 2;            // as k_dc_panels
 constexpr int kStripTiles = 4;
-
-__device__ __forceinline__ f64x4 mfma64(double a, double b, f64x4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 // Hs: the stacked Jacobians, [n_groups * 64][ld] row-major, row g * 64 + q * m + r = row r of candidate g * cpg + q;
 // columns N .. ld are zero.  Spart: [n_chunks * n_strips][J][m * m].
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(256) void k_ds_panels(const double* __restrict__ S,
                     const double b = tile[(4 * s + lk) * kTileS + 16 * w + li];
 #pragma unroll
                     for (int kb = 0; kb < MB; kb++)
-                        accT[ct][kb] = mfma64(ht[(4 * s + lk) * HS + 16 * kb + li], b, accT[ct][kb]);
+                        accT[ct][kb] = GemmTraits<double>::mfma(ht[(4 * s + lk) * HS + 16 * kb + li], b, accT[ct][kb]);
                 }
             }
         }
@@ -138,7 +132,7 @@ __global__ __launch_bounds__(256) void k_ds_panels(const double* __restrict__ S,
                     const double b = ht[(4 * s + lk) * HS + 16 * w + li];
 #pragma unroll
                     for (int kb = 0; kb < MB; kb++)
-                        accS[kb] = mfma64(tile[(16 * kb + li) * kTileS + 4 * s + lk], b, accS[kb]);
+                        accS[kb] = GemmTraits<double>::mfma(tile[(16 * kb + li) * kTileS + 4 * s + lk], b, accS[kb]);
                 }
             }
         }

@@ -81,7 +81,7 @@ def test_dense_reproduces_the_structured_prediction(hip, oracle):
 
 
 # ---- the path the published N = 10003 figure comes from: the main kernel runs whole rounds of 256 x 128 tiles (grouped
-# ---- order, XCD-remapped), k_gemm_f32_tail finishes the rest of the list and the bottom strip of an ld that is an odd
+# ---- order, XCD-remapped), k_gemm_tail<float> finishes the rest of the list and the bottom strip of an ld that is an odd
 # ---- multiple of 128 as 64 x 64 quarters behind it (ekf_dense.hip launch_dense_gemm).  Which kernel computes
 # ---- which 128 x 128 block comes from the library itself (ekf_dense_tile_map: the host side of the kernels' own maps).
 

@@ -1,5 +1,5 @@
 """-m gpu: dense general-F covariance propagation Sigma <- F Sigma F^T + Q in fp64 on the matrix cores
-(ekf_dense64_*, ekf_dense64.hip) -- the fp64 twin of test_gpu_dense.py, held to the library's fp64 contract:
+(ekf_dense64_*; the double instantiation of ekf_dense_gemm.hpp) -- the fp64 twin of test_gpu_dense.py, held to the library's fp64 contract:
 integer operands bit-exact, random operands within 1e-12 per block of numpy fp64, the reference's motion model
 within FP64_TOL of the checker's prediction()."""
 import ctypes

@@ -1,6 +1,6 @@
-// A/B of the fp64 tile for the dense propagation (ekf_dense64.hip): the same 128 x 128 x 16 block tile, 256 threads,
+// A/B of the fp64 tile for the dense propagation (ekf_dense_gemm.hpp, instantiated in ekf_dense.hip): the same 128 x 128 x 16 block tile, 256 threads,
 // double-buffered LDS, grouped tile order, one product C = A * B (NN) at N = 10003 (ld = 10112), built two ways:
-//   M  the product's k_gemm_f64_big: 4 waves x (4 x 4) v_mfma_f64_16x16x4_f64 accumulators
+//   M  the product's k_gemm_big<double>: 4 waves x (4 x 4) v_mfma_f64_16x16x4_f64 accumulators
 //   V  register-blocked v_fma_f64: every thread owns an 8 x 8 block of C (rows / columns 32 c + 2 t + e), operands read
 //      from LDS as b128 pairs, 64 explicit fma() per k (the library is built with -ffp-contract=off)
 // Both run the whole tile list in ONE launch of 6241 workgroups (12.2 rounds of 512 resident), so they differ in the
@@ -11,7 +11,7 @@
 // (tools/micro/mfma_f64_peak.hip's 46 TF feeds at most 4 accumulators and adds a v_add_f64 to the operand every
 // iteration: it is no ceiling for a tile that keeps 16 accumulators in flight.)
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -o tools/micro/dense64_tile_ab tools/micro/dense64_tile_ab.hip
-#include "../../ekf_slam_ml_amd/csrc/ekf_dense64.hip"
+#include "../../ekf_slam_ml_amd/csrc/ekf_dense.hip"
 
 #include <algorithm>
 #include <cmath>
@@ -29,7 +29,7 @@
 
 namespace {
 using ekf::f64x2;
-constexpr int BK = ekf::BK64;
+constexpr int BK = ekf::GemmMainTile<double, false>::BK;
 constexpr int S = 130;   // LDS row stride in doubles: odd in 16-B units
 constexpr int BUF = 2 * BK * S;
 
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256, 2) void k_valu(const double* __restrict__ A, c
                                                  double* __restrict__ C, int ld, int kdim, int tiles) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     int tm, tn;
-    ekf::tile64_of(blockIdx.x, tiles, tm, tn);
+    ekf::big_tile_of(blockIdx.x, tiles, tiles, tm, tn);
     const int row0 = tm * 128, col0 = tn * 128;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const double* Ag = A + (size_t)row0 * ld;
@@ -159,18 +159,18 @@ int main(int argc, char** argv) {
     const unsigned fb = (unsigned)(((size_t)ld * ld + 255) / 256);
     hipLaunchKernelGGL(k_fill, dim3(fb), dim3(256), 0, 0, A, ld, N, 1u);
     hipLaunchKernelGGL(k_fill, dim3(fb), dim3(256), 0, 0, B, ld, N, 2u);
-    CK(ekf::dense64_gemm_prepare());
-    const size_t lds_m = ekf::lds64_bytes(128, 128, false, 2), lds_v = sizeof(double) * 2 * BUF;
+    CK(ekf::dense_gemm_prepare<double>());
+    const size_t lds_m = ekf::GemmMainTile<double, false>::kLdsBytes, lds_v = sizeof(double) * 2 * BUF;
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_valu), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_v));
-    ekf::Dense64Split one{};   // the whole tile list on one launch of the main kernel (no XCD remap: 6241 % 8 != 0)
-    one.ld = ld; one.tiles = tiles; one.n_big = tiles * tiles; one.n_small = 0; one.n_rows = N;
+    ekf::DenseSplit one{};   // the whole tile list on one launch of the main kernel (no XCD remap: 6241 % 8 != 0)
+    one.ld = ld; one.tiles_m = one.tiles_n = tiles; one.n_big = tiles * tiles; one.n_rows = N;
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     auto timed = [&](int which) -> float {
         hipEventRecord(e0, 0);
-        if (which == 0) hipLaunchKernelGGL((ekf::k_gemm_f64_big<false>), dim3(one.n_big), dim3(256), lds_m, 0, A, B, CM, nullptr, one);
+        if (which == 0) hipLaunchKernelGGL((ekf::k_gemm_big<double, false>), dim3(one.n_big), dim3(256), lds_m, 0, A, B, CM, nullptr, one);
         else if (which == 1) hipLaunchKernelGGL(k_valu, dim3(tiles * tiles), dim3(256), lds_v, 0, A, B, CV, ld, N, tiles);
-        else ekf::launch_dense64_gemm(A, B, CM, nullptr, ld, false, 0, N);
+        else ekf::launch_dense_gemm<double>(A, B, CM, nullptr, ld, false, 0, N);
         hipEventRecord(e1, 0);
         hipEventSynchronize(e1);
         float ms = 0.f;
