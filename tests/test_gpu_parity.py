@@ -338,11 +338,20 @@ def test_all_rank2_tile_shapes(hip, oracle, n):
     """Every (TX, CH) instantiation of the rank-2 kernel, incl. ragged last column chunk."""
     cfg = synth.SimConfig(n=n, steps=5, half_extent=3.0, min_spacing=0.05, max_visible_dis=1e9, vmax=3, seed=n)
     log = synth.make_known_log(cfg)
+    # the nearest three never reach the end of the map (highest index 510 at n = 1030): the last step observes landmark
+    # n - 1 as well, so that the ragged last chunk takes a non-zero correction (the full matrix: test_gpu_dense_sigma.py)
+    if log.lm_idx[4, 0].max() < n - 1:
+        rf = synth._robot_frame(log.world, log.true_pose[4])[0, n - 1]
+        noise = cfg.sensor_std * synth.normal01(cfg.seed, 0, 4, synth.KIND_SENSOR, np.array([2 * (n - 1), 2 * (n - 1) + 1], dtype=np.uint64))
+        log.lm_idx[4, 0, 2], log.z_xy[4, 0, 2] = n - 1, rf + noise
+    last = log.lm_idx[4, 0][log.lm_idx[4, 0] >= 0]
+    assert last[-1] == n - 1 and (np.diff(last) > 0).all()
     f, o = hip.EKF_SLAM(n), oracle.OracleEKF(n, oracle.STRUCTURED)
     for t in range(5):
         sensor, vis = log.expand_step(t)
         f.prediction(log.twist[t, 0]); o.prediction(*log.twist[t, 0])
         f.measurement(sensor, vis); o.measurement(sensor, vis)
+    assert vis[n - 1] and np.abs(o.cov[-1, :3]).min() > 0.0
     assert_parity(f.state, f.cov, o.state, o.cov, 1e-11, f"n={n}")
     f.close()
 
