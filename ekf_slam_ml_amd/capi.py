@@ -10,6 +10,7 @@ constructor raises.  The classes mirror the reference's call surface:
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import sys
 
@@ -52,6 +53,7 @@ SYMBOLS = [
     "ekf_dense64_predict_landmarks", "ekf_dense64_measure_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
+    "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -228,6 +230,10 @@ def load():
         "ekf_dense64_set_live": [h, C.c_int],
         "ekf_dense64_get_live": [h, _ip],
         "ekf_dense64_coupling": [h, C.c_int, C.POINTER(C.c_longlong), _dp, _dp],
+        "ekf_dense64_pairs_launch_info": [h, _ip, _ip],
+        "ekf_dense64_score_landmark_pairs": [h, C.c_int, C.c_double, C.c_double, _ip, _dp, C.POINTER(C.c_longlong),
+                                             C.POINTER(C.c_longlong), _dp],
+        "ekf_dense64_merge_landmarks": [h, C.POINTER(Params), C.c_int, C.c_int, C.c_double, _ip, C.c_int, _ip, _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
@@ -959,6 +965,59 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_coupling(self._h, int(Na), C.byref(count), C.byref(most), C.byref(ms)))
         return count.value, most.value, ms.value
 
+    @staticmethod
+    def _r_merge(r_merge):
+        r_merge = float(r_merge)
+        if not (math.isfinite(r_merge) and r_merge >= 0.0):
+            raise ValueError("r_merge must be finite and >= 0")
+        return r_merge
+
+    def landmark_pairs(self, n_lm, r_merge, gate=math.inf):
+        """The Mahalanobis test of every pair a < b of the first n_lm landmarks (landmark i = states 3 + 2 i, 4 + 2 i) in
+        one pass over Sigma's landmark corner: d2(a, b) is bit for bit the nis of score_sparse() for cols = [3 + 2a,
+        4 + 2a, 3 + 2b, 4 + 2b], Hc = [[1, 0, -1, 0], [0, 1, 0, -1]], R = r_merge I, nu = x_a - x_b.  Returns (nearest
+        (n_lm,) int32: the partner with the smallest score, lowest index on a tie, -1 with none; d2 (n_lm,): that score,
+        +inf with none; n_below: unordered pairs with d2 < gate; n_flagged: pairs with a singular or non-finite S, which
+        never win; elapsed_ms).  Flushes the pending rows first, otherwise read-only; 3 + 2 n_lm <= live."""
+        n_lm, gate = int(n_lm), float(gate)
+        if not 1 <= n_lm <= (self.N - 3) // 2:
+            raise ValueError("1 <= n_lm <= (N - 3) // 2")
+        r_merge = self._r_merge(r_merge)
+        if gate != gate:
+            raise ValueError("gate must not be a NaN")
+        nearest, d2 = np.empty(n_lm, dtype=np.int32), np.empty(n_lm, dtype=np.float64)
+        below, flagged, ms = C.c_longlong(), C.c_longlong(), C.c_double()
+        _check(self._lib.ekf_dense64_score_landmark_pairs(self._h, n_lm, r_merge, gate, nearest.ctypes.data_as(_ip),
+                                                          d2.ctypes.data_as(_dp), C.byref(below), C.byref(flagged),
+                                                          C.byref(ms)))
+        return nearest, d2, below.value, flagged.value, ms.value
+
+    def pairs_launch_info(self):
+        """{tile_landmarks, threads}: the side of landmark_pairs()' tiles in landmarks and its workgroup size (test hook)"""
+        tl, th = C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_pairs_launch_info(self._h, C.byref(tl), C.byref(th)))
+        return {"tile_landmarks": tl.value, "threads": th.value}
+
+    def merge_landmarks(self, a, b, r_merge, known, flags=0, params=None):
+        """Fuse landmarks a and b (either order) of the `known` ones and remove the higher: correct_sparse() -- with
+        LM_DEFERRED in flags correct_sparse_deferred() -- on landmark_pairs()' operands for (min, max), built on the
+        device; then swap_blocks(max, last) unless max is the last, init_block(last, W = sigma0 I) and known - 1; with
+        LM_GROW_LIVE also live = 3 + 2 known.  Bit for bit that sequence spelled.  Returns (known, moved_from: the old index
+        of the landmark that now sits in slot max, or -1; d2: the correction's nis; elapsed_ms).  A singular S raises
+        EkfError (EKF_ERR_STATE) and leaves everything as it was."""
+        a, b, known, flags = int(a), int(b), int(known), int(flags)
+        if not 0 <= known <= (self.N - 3) // 2:
+            raise ValueError("0 <= known <= (N - 3) // 2")
+        if a == b or not (0 <= a < known and 0 <= b < known):
+            raise ValueError("a and b must be two different landmarks in [0, known)")
+        r_merge = self._r_merge(r_merge)
+        if flags & ~(self.LM_DEFERRED | self.LM_GROW_LIVE):
+            raise ValueError("flags: LM_DEFERRED | LM_GROW_LIVE")
+        k, moved, d2, ms = C.c_int(known), C.c_int(-1), C.c_double(), C.c_double()
+        _check(self._lib.ekf_dense64_merge_landmarks(self._h, C.byref(params) if params is not None else None, a, b, r_merge,
+                                                     C.byref(k), flags, C.byref(moved), C.byref(d2), C.byref(ms)))
+        return k.value, moved.value, d2.value, ms.value
+
     def _correct_sparse(self, entry, cols, Hc, R, nu):
         cols = self._index_lists(cols, 1)
         s = cols.shape[0]
@@ -1347,6 +1406,22 @@ class DenseEKFSLAM:
             self._known = e.known
             raise
         return centres, assoc
+
+    def find_duplicates(self, gate, r_merge):
+        """the pairs (a, b), a < b, of known landmarks that are each other's nearest partner with d2 < gate, in ascending
+        a, from one landmark_pairs() scan -> (pairs [(a, b, d2)], n_below)"""
+        if self._known < 2:
+            return [], 0
+        nearest, d2, below, _, _ = self.handle.landmark_pairs(self._known, r_merge, gate)
+        pairs = [(a, int(b), float(d2[a])) for a, b in enumerate(nearest) if b > a and nearest[b] == a and d2[a] < gate]
+        return pairs, below
+
+    def merge(self, a, b, r_merge):
+        """fuse the known landmarks a and b and remove the higher (merge_landmarks on the object's paths); the last known
+        landmark moves into its slot.  Returns (moved_from, d2)"""
+        flags = (self.handle.LM_DEFERRED if self.deferred else 0) | (self.handle.LM_GROW_LIVE if self.grow_live else 0)
+        self._known, moved, d2, _ = self.handle.merge_landmarks(a, b, r_merge, self._known, flags, self.params)
+        return moved, d2
 
     @property
     def state(self):

@@ -3,8 +3,8 @@
 // scoring of candidates (ekf_dense64_score.hip), the block-structured prediction (ekf_dense64_block.hip), the update and
 // scoring for a Jacobian given by its non-zero columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states
 // and the block readout (ekf_dense64_init.hip), the exchange of two blocks (ekf_dense64_swap.hip), the landmark front end
-// (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), and the
-// deferred form of the sparse update: pending rows of K and T that the sparse calls
+// (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), the
+// scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 // The structured calls run at the handle's LIVE dimension (ekf_dense64_set_live, N by default): every launch of theirs is
@@ -38,7 +38,7 @@ ekf_status ekf_dense64_s::created() {
 
 void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
     for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p})
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, pairs.p})
         if (p) (void)hipFree(p);
     scan_up.release();
 }
@@ -613,6 +613,81 @@ ekf_status ekf_dense64_coupling(ekf_dense64_handle d, int Na, long long* nonzero
     EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
     *nonzero = (long long)out[0];
     if (max_abs) std::memcpy(max_abs, &out[1], sizeof(double));
+    return EKF_OK;
+}
+
+// ---- duplicate landmarks: the all-pairs scan (ekf_dense64_pairs.hip) and the merge, a layer over the calls above ----------
+ekf_status ekf_dense64_pairs_launch_info(ekf_dense64_handle d, int* tile_landmarks, int* threads) {
+    if (!d || !tile_landmarks || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_pairs_launch_info: null argument");
+    *tile_landmarks = ekf::kDense64PairsTile;
+    *threads = ekf::kDense64PairsThreads;
+    return EKF_OK;
+}
+
+// The counters are zeroed, the pending rows applied, two launches; nearest, d2 and the two counts come back behind the one
+// synchronisation.  The workspace grows with n_lm and is the only thing the call changes in the handle.
+ekf_status ekf_dense64_score_landmark_pairs(ekf_dense64_handle d, int n_lm, double r_merge, double gate, int* nearest,
+                                            double* d2, long long* n_below, long long* n_flagged, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_score_landmark_pairs";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!nearest && !d2) return fail(EKF_ERR_INVALID, std::string(fn) + ": nearest and d2 are both NULL");
+    if (n_lm < 1 || 3 + 2 * (long long)n_lm > d->live)
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": the n_lm >= 1 landmarks must lie inside the live dimension");
+    if (!(r_merge >= 0.0) || !std::isfinite(r_merge) || gate != gate)
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": r_merge must be finite and >= 0, gate not a NaN");
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64PairsPlan pl = ekf::dense64_pairs_plan(n_lm);
+    EKFC(d->pairs.reserve(pl.bytes, d->stream, false, fn, "the pair scan's workspace"));
+    char* ws = d->pairs.as<char>();
+    unsigned long long counts[2] = {0, 0};
+    HIPC(hipMemsetAsync(ws + pl.off_count, 0, sizeof(counts), d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_pairs(pl, d->S, d->x, d->ld, r_merge, gate, ws, d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{nearest, ws + pl.off_nearest, sizeof(int) * n_lm},
+                                      {d2, ws + pl.off_d2, sizeof(double) * n_lm},
+                                      {counts, ws + pl.off_count, sizeof(counts)}}));
+    if (n_below) *n_below = (long long)counts[0];
+    if (n_flagged) *n_flagged = (long long)counts[1];
+    return EKF_OK;
+}
+
+// [terms | the sparse correction, eager or deferred] and its synchronisation, then -- through the public calls, so that
+// carry, pending rows and live behave as in the spelled sequence -- [swap_blocks] init_block [set_live].
+ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* params, int a, int b, double r_merge,
+                                       int* known, int flags, int* moved_from, double* d2_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_merge_landmarks";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!known) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (*known < 0 || 3 + 2 * (long long)*known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
+    if (a == b || a < 0 || b < 0 || a >= *known || b >= *known)
+        return fail(EKF_ERR_INVALID, fn + ": a and b must be two different landmarks in [0, *known)");
+    if (!(r_merge >= 0.0) || !std::isfinite(r_merge)) return fail(EKF_ERR_INVALID, fn + ": r_merge must be finite and >= 0");
+    if ((unsigned)flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
+        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
+    const ekf::Params p = landmark_params(params);
+    const int lo = std::min(a, b), hi = std::max(a, b), last = *known - 1;
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    HIPC(hipSetDevice(d->device));
+    if (deferred) EKFC(pend_reserve(d, fnc));
+    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    double total = 0.0, ms = 0.0;
+    double* pms = elapsed_ms ? &ms : nullptr;
+    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_pair_terms(d->x, lo, hi, r_merge, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
+    correct_sparse_launch(d, deferred, 2, 4, true);
+    EKFC(leg(correct_sparse_finish(d, fnc, deferred, 2, d2_out, pms)));   // singular: nothing was written, *known stands
+    // the removal of hi ("Removing a landmark")
+    const double W[4] = {p.sigma0_landmark, 0.0, 0.0, p.sigma0_landmark};
+    if (hi != last) EKFC(leg(ekf_dense64_swap_blocks(d, 3 + 2 * hi, 3 + 2 * last, 2, pms)));
+    EKFC(leg(ekf_dense64_init_block(d, 3 + 2 * last, 2, 0, nullptr, nullptr, W, nullptr, pms)));
+    *known = last;
+    if (moved_from) *moved_from = hi != last ? last : -1;
+    if (flags & EKF_DENSE64_LM_GROW_LIVE) EKFC(ekf_dense64_set_live(d, 3 + 2 * last));
     return EKF_OK;
 }
 

@@ -208,4 +208,26 @@ void launch_dense64_scan_circles(const double* ranges, int nb, int max_out, int*
 // with exactly one index >= Na, the number of entries != 0 and the largest absolute value.  One streaming launch, integer
 // atomics only.  out: two 64-bit words on the device, zero before the launch: the count, and the bits of the maximum.
 void launch_dense64_coupling(const double* Sigma, int N, int ld, int Na, unsigned long long* out, hipStream_t st);
+
+// ---- all pairs of landmarks scored against each other (ekf_dense64_pairs.hip): d2(a, b), a < b < n_lm, is the nis of
+// ekf_dense64_score_sparse for m = 2, s = 4, cols = {3 + 2a, 4 + 2a, 3 + 2b, 4 + 2b}, Hc = [[1, 0, -1, 0], [0, 1, 0, -1]],
+// R = r_merge I, nu = x[a] - x[b], bit for bit; per landmark the partner with the smallest score (lowest index on a tie, a
+// flagged pair never), and the counts of pairs below `gate` and of flagged pairs.  One read of Sigma's landmark corner:
+// a workgroup per tile (A <= B) of kDense64PairsTile landmarks a side, then a fold of tiles + 1 records per landmark.
+constexpr int kDense64PairsTile = 32;
+constexpr int kDense64PairsThreads = 256;
+// the workspace of a call, byte offsets: count (two 64-bit words, zero before the launch: below, flagged) | d2 [n_lm] |
+// the per-tile records | nearest [n_lm]
+struct Dense64PairsPlan {
+    int n_lm, tiles;
+    size_t off_count, off_d2, off_part_d2, off_part_idx, off_nearest, bytes;
+};
+Dense64PairsPlan dense64_pairs_plan(int n_lm);
+// Two launches.  Reads Sigma and state below index 3 + 2 n_lm only (<= the dimension: the launcher does not check).
+void launch_dense64_pairs(const Dense64PairsPlan& p, const double* Sigma, const double* state, int ld, double r_merge,
+                          double gate, void* ws, hipStream_t st);
+// One thread: the operands above for the pair (lo, hi) where the sparse correction reads them, with nu = x[hi] - x[lo]: the
+// innovation of the reading 0 of x[lo] - x[hi], the exact negative of the score's nu (S and nis keep their bits).
+void launch_dense64_pair_terms(const double* state, int lo, int hi, double r_merge, int* cols, double* Hc, double* R,
+                               double* nu, hipStream_t st);
 }  // namespace ekf

@@ -973,6 +973,60 @@ ekf_status ekf_dense64_init_block(ekf_dense64_handle h, int first, int r, int s,
 ekf_status ekf_dense64_swap_blocks(ekf_dense64_handle h, int first_a, int first_b, int r,
                                    double* elapsed_ms); /* HIP-event time of the launches only (nullable) */
 
+/* Duplicate landmarks: find them, merge them.  The reference's rule creates a landmark whenever the best score of a reading
+ * is >= gate_new (ekf_slam.cpp:300-327), so one reading taken at a drifted pose leaves a second copy of an existing tube in
+ * the map.  The repair is a landmark-to-landmark Mahalanobis test, a fusion of the two states and the removal of one.
+ * State layout as everywhere: landmark i sits at 3 + 2 i, 4 + 2 i.
+ * ekf_dense64_score_landmark_pairs: ALL pairs of the first n_lm landmarks in one pass over Sigma's landmark corner
+ * (8 (3 + 2 n_lm)^2 bytes read once; ekf_dense64_score_sparse takes 65536 rows a call, all pairs of 5000 landmarks would
+ * be about 380 calls).  DEFINITION: for a < b, d2(a, b) is the nis ekf_dense64_score_sparse returns, bit for bit, for
+ *   m = 2, s = 4, cols = {3 + 2a, 4 + 2a, 3 + 2b, 4 + 2b}, Hc = [[1, 0, -1, 0], [0, 1, 0, -1]], R = r_merge I,
+ *   nu = x[3 + 2a .. 4 + 2a] - x[3 + 2b .. 4 + 2b]   (one plain subtraction each)
+ * under that call's ORDER OF ARITHMETIC: fused multiply-adds from +0 in ascending k, so T[0][j] = fl(Sigma[a0][j] -
+ * Sigma[b0][j]) and S[0][0] = fl(T[0][a0] - T[0][b0]) + R; Sigma is never symmetrised (the blocks Sigma_ab and Sigma_ba
+ * both enter); the elimination and the quadratic form are those of that call at m = 2, with its pivot rule (largest
+ * |entry|, lowest row on a tie) and its verdict (non-finite S, zero or non-finite pivot, non-finite inverse: the pair is
+ * FLAGGED and its d2 is a NaN).  d2(b, a) = d2(a, b) in bits (every operand is negated exactly).
+ *   nearest[a]  the partner b != a with the smallest d2(min(a, b), max(a, b)); the lowest index on equal scores; a flagged
+ *               pair never wins; -1 with no valid partner (n_lm = 1, or every pair of a flagged)
+ *   d2[a]       that score, +Inf with no valid partner
+ *   *n_below    (nullable) unordered pairs with d2 < gate          *n_flagged  (nullable) flagged pairs
+ * At least one of nearest, d2 is given.  Integer counters and a pure (min, lowest index) argmin, no floating-point atomics:
+ * every order of reduction gives the same bits and a run repeats bit for bit.
+ * The call is read-only on Sigma and the state.  It needs Sigma in memory, so it FLUSHES THE PENDING ROWS FIRST, after its
+ * own argument checks, as ekf_dense64_coupling does.  1 <= n_lm and 3 + 2 n_lm <= live; nothing at an index >= 3 + 2 n_lm
+ * is read (Sigma, state, padding: the tiles' loads are masked element by element), so the results are those of a handle
+ * created with N = 3 + 2 n_lm that holds the same corner.  A NULL handle (checked first), nearest and d2 both NULL, a bad
+ * n_lm, an r_merge that is negative or not finite, a NaN gate return EKF_ERR_INVALID before the device is looked at and
+ * change nothing, the pending rows included.  The workspace (12 bytes per landmark and tile of 32, about 9.5 MB at
+ * n_lm = 5000) is allocated by the first call and grows with n_lm; a failure there returns EKF_ERR_NOMEM and leaves the
+ * handle as it was.  Two launches (a workgroup per tile (A <= B) of 32 x 32 pairs, then a fold per landmark), one
+ * synchronisation; ekf_dense64_pairs_launch_info reports the tile side in landmarks and the workgroup size.
+ * elapsed_ms (nullable) = HIP-event time of the launches, the flush included.
+ * ekf_dense64_merge_landmarks: landmarks a and b (either order; lo = min, hi = max) become one, a layer over the calls
+ * above with no arithmetic of its own: a one-thread kernel writes the operands of the definition for (lo, hi) on the device
+ * (no state comes down) -- cols, Hc and R as they stand, and for the innovation that of the reading z = 0 of x_lo - x_hi,
+ * z - H x = x_hi - x_lo, the exact negative of the definition's nu, so S and nis keep their bits and the correction pulls
+ * the two copies together --, ekf_dense64_correct_sparse -- with EKF_DENSE64_LM_DEFERRED ekf_dense64_correct_sparse_deferred
+ * -- applies them (the constraint x_lo = x_hi with noise r_merge I), and hi is removed by the recipe of
+ * ekf_dense64_swap_blocks: swap_blocks(hi, last) unless hi is the last known landmark, init_block(last, s = 0,
+ * W = sigma0_landmark I), --*known; with EKF_DENSE64_LM_GROW_LIVE also ekf_dense64_set_live(3 + 2 *known).  The same
+ * internal paths run, so carry, pending rows and live behave as in that sequence spelled by the caller, and the result is
+ * bit for bit the spelled sequence's.  *moved_from (nullable) = the old index of the landmark that now sits in slot hi, -1
+ * when hi was the last (the library keeps no ids: the caller's bookkeeping follows it).  *d2_out (nullable) = the
+ * correction's nis: the bits of the scan's d2(lo, hi) when nothing changed in between.  A singular S (r_merge = 0 on
+ * perfectly correlated copies) returns EKF_ERR_STATE with the state, Sigma, the pending rows and *known untouched.  A NULL
+ * handle or known, the known landmarks outside the live dimension, a == b, an index outside [0, *known), a bad r_merge,
+ * unknown flag bits return EKF_ERR_INVALID before the device is looked at.  params: NULL = the reference's constants (only
+ * sigma0_landmark is used).  elapsed_ms (nullable) = HIP-event time of the launches of every leg. */
+ekf_status ekf_dense64_pairs_launch_info(ekf_dense64_handle h, int* tile_landmarks, int* threads);
+ekf_status ekf_dense64_score_landmark_pairs(ekf_dense64_handle h, int n_lm, double r_merge, double gate,
+                                            int* nearest /* [n_lm], nullable */, double* d2 /* [n_lm], nullable */,
+                                            long long* n_below, long long* n_flagged, double* elapsed_ms);
+ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle h, const ekf_params* params, int a, int b, double r_merge,
+                                       int* known, int flags /* EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE */,
+                                       int* moved_from, double* d2_out, double* elapsed_ms);
+
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
  * ekf_dense64_get_sigma_block: out[a][c] = Sigma[rows[a]][cols[c]], nr x nc row-major; one gather launch into a buffer
