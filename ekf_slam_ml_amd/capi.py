@@ -50,6 +50,8 @@ SYMBOLS = [
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
     "ekf_dense64_score_landmarks", "ekf_dense64_associate_landmarks",
     "ekf_dense64_fit_scan", "ekf_dense64_associate_scan",
+    "ekf_dense64_score_readings", "ekf_dense64_joint_operands", "ekf_dense64_associate_joint",
+    "ekf_dense64_associate_scan_joint",
     "ekf_dense64_predict_landmarks", "ekf_dense64_measure_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
@@ -223,6 +225,11 @@ def load():
         "ekf_dense64_fit_scan": [h, _dp, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _ip, _dp],
         "ekf_dense64_associate_scan": [h, C.POINTER(Params), _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_uint, _ip, _dp, _ip,
                                        _dp, _dp],
+        "ekf_dense64_score_readings": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, C.c_int, _dp, _ip, _dp],
+        "ekf_dense64_joint_operands": [h, C.POINTER(Params), C.c_int, _ip, _dp, _ip, _dp, _dp, _dp],
+        "ekf_dense64_associate_joint": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, _ip, C.c_uint, _ip, _dp, _ip, _dp],
+        "ekf_dense64_associate_scan_joint": [h, C.POINTER(Params), _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_uint, _ip, _dp,
+                                             _ip, _dp, _dp],
         "ekf_dense64_predict_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, _dp, _dp, _dp],
         "ekf_dense64_measure_landmarks": [h, C.POINTER(Params), C.c_int, _dp, _bp, _ip, C.c_uint, _ip, _dp, _dp, _dp],
         "ekf_dense64_set_carry": [h, C.c_int],
@@ -788,6 +795,7 @@ class DensePropagator64(_DensePropagatorBase):
     PENDING_MAX_ROWS = 64   # EKF_DENSE64_PENDING_MAX_ROWS
     LM_DEFERRED, LM_GROW_LIVE = 1, 2   # EKF_DENSE64_LM_DEFERRED, EKF_DENSE64_LM_GROW_LIVE
     SCAN_MAX_BEAMS, SCAN_MAX_CIRCLES = 1024, 128   # EKF_DENSE64_SCAN_MAX_BEAMS, EKF_DENSE64_SCAN_MAX_CIRCLES
+    JOINT_MAX_READINGS, JOINT_MAX_PAIRS = 128, 30   # EKF_DENSE64_JOINT_MAX_READINGS, EKF_DENSE64_JOINT_MAX_PAIRS
 
     _PREFIX, _DTYPE, _PTR = "ekf_dense64_", np.float64, _dp
 
@@ -1175,6 +1183,96 @@ class DensePropagator64(_DensePropagatorBase):
             raise
         return k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
 
+    @staticmethod
+    def _readings(readings, most):
+        z = np.ascontiguousarray(readings, dtype=np.float64)
+        if z.ndim != 2 or z.shape[1] != 2 or not 1 <= z.shape[0] <= most:
+            raise ValueError(f"readings must be J x 2 with 1 <= J <= {most}")
+        return z
+
+    def score_readings(self, readings, first_lm=0, count=None, params=None):
+        """score_landmarks() for the readings (J, 2) of a whole scan at once: candidate (j, i) is reading j against landmark
+        first_lm + i, its nis and flag bit for bit those of score_landmarks for reading j alone.  The readings go up in one
+        copy, the launches are cut at 32768 / count readings, one synchronisation; read-only.  Returns (nis (J, count),
+        flags (J, count), elapsed_ms)."""
+        z = self._readings(readings, self.JOINT_MAX_READINGS)
+        first_lm = int(first_lm)
+        if count is None:
+            count = (self.live - 3) // 2 - first_lm
+        count = int(count)
+        if first_lm < 0 or not 1 <= count <= self.SCORE_SPARSE_MAX_ROWS // 2:
+            raise ValueError(f"first_lm >= 0 and 1 <= count <= {self.SCORE_SPARSE_MAX_ROWS // 2}")
+        J = z.shape[0]
+        nis, flags = np.empty((J, count), dtype=np.float64), np.empty((J, count), dtype=np.int32)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_score_readings(
+            self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), first_lm, count,
+            nis.ctypes.data_as(_dp), flags.ctypes.data_as(_ip), C.byref(ms)))
+        return nis, flags, ms.value
+
+    def joint_operands(self, lm_idx, readings, params=None):
+        """The stacked operands the joint correction would use for the V pairs (landmark lm_idx[v], reading v), built on the
+        device from the current state; read-only.  Returns (cols (3 + 2V,), Hc (2V, 3 + 2V), nu (2V,) bearing wrapped,
+        elapsed_ms); R = r_meas I is implied.  Handed to correct_sparse[_deferred] they are one group of associate_joint."""
+        z = self._readings(readings, self.JOINT_MAX_PAIRS)
+        lm = np.ascontiguousarray(lm_idx, dtype=np.int32)
+        V = z.shape[0]
+        if lm.shape != (V,):
+            raise ValueError("lm_idx must hold one landmark per reading")
+        cols = np.empty(3 + 2 * V, dtype=np.int32)
+        Hc, nu = np.empty((2 * V, 3 + 2 * V), dtype=np.float64), np.empty(2 * V, dtype=np.float64)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_joint_operands(
+            self._h, C.byref(params) if params is not None else None, V, lm.ctypes.data_as(_ip), z.ctypes.data_as(_dp),
+            cols.ctypes.data_as(_ip), Hc.ctypes.data_as(_dp), nu.ctypes.data_as(_dp), C.byref(ms)))
+        return cols, Hc, nu, ms.value
+
+    def associate_joint(self, readings, known, n_max, deferred=False, grow_live=False, params=None):
+        """A whole scan associated jointly: all readings (J, 2) are scored against the state on entry, ONE assignment is made
+        (of the readings that claim one landmark the lowest score keeps it, the readings under no gate take new slots in
+        order), the new landmarks are initialised in groups of 32 and the matched and new readings are corrected in stacked
+        updates of up to 30 readings (correct_sparse, or correct_sparse_deferred with deferred=True).  Not the sequential
+        rule of associate_landmarks -- with one reading the two are the same in bits.  Two readings of one unseen object
+        give two landmarks; find_duplicates / merge_landmarks is the repair.  Returns (known, assoc (J,) int32: landmark
+        corrected / -1 dropped, best (J,), n_groups, elapsed_ms).  A refused call or a singular S raises EkfError; the
+        exception carries .known, .assoc and .best as they stood."""
+        z = self._readings(readings, self.JOINT_MAX_READINGS)
+        J = z.shape[0]
+        k, ng = C.c_int(int(known)), C.c_int(0)
+        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
+        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        ms = C.c_double()
+        try:
+            _check(self._lib.ekf_dense64_associate_joint(
+                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
+                flags, assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), C.byref(ng), C.byref(ms)))
+        except EkfError as e:
+            e.known, e.assoc, e.best = k.value, assoc, best
+            raise
+        return k.value, assoc, best, ng.value, ms.value
+
+    def associate_scan_joint(self, ranges, known, n_max, max_readings=64, deferred=False, grow_live=False, params=None):
+        """fit_scan(ranges, max_readings) followed by associate_joint's path on the circles it finds, in one call.  Returns
+        (known, centres (k, 2), assoc (k,) int32, best (k,)) as associate_scan does; the exception of a refused call or a
+        singular S carries .known, .centres, .assoc and .best as they stood."""
+        r = self._scan(ranges)
+        max_readings = int(max_readings)
+        if not 1 <= max_readings <= self.SCAN_MAX_CIRCLES:
+            raise ValueError(f"1 <= max_readings <= {self.SCAN_MAX_CIRCLES}")
+        k, cnt = C.c_int(int(known)), C.c_int(0)
+        cen = np.zeros((max_readings, 2), dtype=np.float64)
+        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
+        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        try:
+            _check(self._lib.ekf_dense64_associate_scan_joint(
+                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
+                int(n_max), C.byref(k), flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
+                best.ctypes.data_as(_dp), None))
+        except EkfError as e:
+            e.known, e.centres, e.assoc, e.best = k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+            raise
+        return k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+
     def predict_landmarks(self, dtheta, dx, want_terms=False, params=None):
         """prediction() (ekf_slam.cpp:55-106) for the twist (dtheta, dx) on the handle's own state: Fr = I + A, Qr = q_pose I
         and the pose update are built on the device from state[0] (both branches of :79, |dtheta| < straight_eps is the
@@ -1396,12 +1494,24 @@ class DenseEKFSLAM:
             raise
         return assoc
 
-    def scan_association(self, ranges):
-        """one LaserScan through the landmarks node (circle fitting) into data_association(), in one call; returns (centres
-        (k, 2), assoc (k,) int32) of the k circles found"""
+    def joint_association(self, meas_xy):
+        """the readings of one scan associated jointly (DensePropagator64.associate_joint): all scored against the state on
+        entry, one assignment, stacked corrections; returns assoc (J,) int32 as data_association() does"""
         try:
-            self._known, centres, assoc, _ = self.handle.associate_scan(ranges, self._known, self.n, deferred=self.deferred,
-                                                                        grow_live=self.grow_live, params=self.params)
+            self._known, assoc, _, _, _ = self.handle.associate_joint(meas_xy, self._known, self.n, self.deferred,
+                                                                      self.grow_live, self.params)
+        except EkfError as e:
+            self._known = e.known
+            raise
+        return assoc
+
+    def scan_association(self, ranges, joint=False):
+        """one LaserScan through the landmarks node (circle fitting) into data_association() -- or, with joint=True, into
+        joint_association() -- in one call; returns (centres (k, 2), assoc (k,) int32) of the k circles found"""
+        call = self.handle.associate_scan_joint if joint else self.handle.associate_scan
+        try:
+            self._known, centres, assoc, _ = call(ranges, self._known, self.n, deferred=self.deferred,
+                                                  grow_live=self.grow_live, params=self.params)
         except EkfError as e:
             self._known = e.known
             raise

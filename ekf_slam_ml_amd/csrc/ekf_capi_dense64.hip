@@ -38,7 +38,7 @@ ekf_status ekf_dense64_s::created() {
 
 void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
     for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, pairs.p})
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p})
         if (p) (void)hipFree(p);
     scan_up.release();
 }
@@ -152,13 +152,13 @@ void score_sparse_launch(ekf_dense64_s* d, const SpsView& v, int J, int m, int s
 // ---- (re)initialisation of a block of states -----------------------------------------------------------------------------
 // the launches on operands that sit in ini_in (the public call after its uploads, the landmark front end after
 // k_dlm_decide): the pending rows carried or applied, then the one launch; behind e0
-void init_block_launch(ekf_dense64_s* d, int first, int r, int s, bool have_W, bool have_xb) {
+// W, xb: on the device (ini_in's own, or the stacked ones of the joint association), null as the public call defines
+void init_block_launch(ekf_dense64_s* d, int first, int r, int s, const double* W, const double* xb) {
     const IniInView in = view(d->ini_in, L::ini_in_layout());
     d->carry_or_flush([&](const PendView& p) {
         ekf::launch_dense64_panel_map(p.K, p.T, d->pend_rows, in.G, s > 0 ? in.cols : nullptr, d->ld, first, r, s, d->stream);
     });
-    ekf::launch_dense64_init(d->S, d->x, in.cols, in.G, have_W ? in.W : nullptr, have_xb ? in.xb : nullptr, d->live, d->ld,
-                             first, r, s, d->stream);
+    ekf::launch_dense64_init(d->S, d->x, in.cols, in.G, W, xb, d->live, d->ld, first, r, s, d->stream);
 }
 
 ekf_status dense64_state_block(const char* name, ekf_dense64_s* d, int first, int count, double* out, const double* x) {
@@ -281,7 +281,7 @@ ekf_status associate_readings(ekf_dense64_s* d, const char* fnc, const ekf::Para
             EKFC(ekf_dense64_set_live(d, 3 + 2 * (k + 1)));
         }
         HIPC(hipEventRecord(d->e0, d->stream));
-        if (fresh_lm) init_block_launch(d, 3 + 2 * k, 2, 0, true, true);   // s = 0, W = sigma0 I, xb
+        if (fresh_lm) init_block_launch(d, 3 + 2 * k, 2, 0, ini.W, ini.xb);   // s = 0, W = sigma0 I, xb
         if (!corrects) {   // (a gate_update <= 0: the landmark is initialised and not corrected)
             EKFC(leg(finish_timed(d, pms)));
             *known = k + 1;
@@ -300,6 +300,123 @@ ekf_status associate_readings(ekf_dense64_s* d, const char* fnc, const ekf::Para
         if (st != EKF_OK) return st;
         if (assoc_out) assoc_out[j] = rec.win;
     }
+    return EKF_OK;
+}
+
+// ---- the same for a whole scan at once (ekf_dense64_joint.hip), shared by ekf_dense64_score_readings,
+// ekf_dense64_associate_joint and ekf_dense64_associate_scan_joint ----------------------------------------------------------
+constexpr int kJointReadings = ekf::kDense64JointMaxReadings, kJointPairs = ekf::kDense64JointMaxPairs;
+constexpr int kJointInit = ekf::kDense64JointInitGroup;
+
+// readings of one scoring launch against `count` landmarks: a launch stays within the sparse scoring call's rows (m = 2)
+int joint_chunk(int J, int count) { return std::min(J, (kSparseRows / 2) / count); }
+
+ekf_status joint_reserve(ekf_dense64_s* d, const char* fnc) {
+    return d->joint.reserve(L::joint_layout().bytes, d->stream, true, fnc, "the joint association's buffer");
+}
+
+// J readings (in jv.xy) against landmarks [first_lm, first_lm + count), cut into launches of `chunk` readings: per launch
+// [terms | score], then what the caller does with that launch's scores (first reading, readings, the view) behind it
+template <class Each>
+void score_readings_launch(ekf_dense64_s* d, const ekf::Params& p, const JointView& jv, int J, int first_lm, int count,
+                           int chunk, bool want_nis, Each&& each) {
+    const SpsView v = view(d->sps.p, L::sps_layout(chunk * count, 2, 5, true, false), false);
+    for (int j0 = 0; j0 < J; j0 += chunk) {
+        const int nr = std::min(chunk, J - j0);
+        ekf::launch_dense64_joint_terms(d->x, d->x, jv.xy + 2 * j0, nr, first_lm, count, p.r_meas, v.cols, v.Hc, v.R, v.nu,
+                                        d->stream);
+        score_sparse_launch(d, v, nr * count, 2, 5, true, true, want_nis);
+        each(j0, nr, v);
+    }
+}
+
+// One stacked correction on pairs whose landmarks and readings sit in device memory (lm, rj: nullable = reading v): the
+// operands from the current state into correct_sparse's buffer, the correction, the heading; behind e0
+void joint_correct_launch(ekf_dense64_s* d, const ekf::Params& p, const JointView& jv, const int* lm, const int* rj, int V,
+                          bool deferred) {
+    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    ekf::launch_dense64_joint_operands(d->x, jv.xy, lm, rj, V, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
+    correct_sparse_launch(d, deferred, 2 * V, 3 + 2 * V, true);
+    ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
+}
+
+// The joint rule on J readings (include/ekfslam.h).  [upload | per launch: terms | score | argmin | resolve] and the record
+// back (the FIRST synchronisation); the live dimension once; [init per 32 new landmarks | per 30 pairs: operands | correction
+// | heading wrap] with each correction's own synchronisation.  *elapsed_ms as in associate_readings.
+ekf_status associate_joint(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, int J, const double* meas_xy, int n_max,
+                           int* known, unsigned flags, int* assoc_out, double* best_out, int* n_groups_out,
+                           double* elapsed_ms) {
+    const std::string fn = fnc;
+    const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
+    const L::JointLayout jl = L::joint_layout();
+    const JointView jv = view(d->joint.p, jl);
+    double total = elapsed_ms ? *elapsed_ms : 0.0, ms = 0.0;
+    double* pms = elapsed_ms ? &ms : nullptr;
+    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    const int k = *known;
+    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    if (k > 0)
+        // (cut as for the full map, whatever is known: the launches stay inside the buffer reserved for it)
+        score_readings_launch(d, p, jv, J, 0, k, joint_chunk(J, n_max), true, [&](int j0, int nr, const SpsView& v) {
+            ekf::launch_dense64_joint_argmin(v.nis, nr, k, p.gate_new, p.gate_update, jv.pre + j0, d->stream);
+        });
+    else
+        ekf::launch_dense64_joint_argmin(nullptr, J, 0, p.gate_new, p.gate_update, jv.pre, d->stream);
+    ekf::launch_dense64_joint_resolve(jv.pre, J, k, n_max, p.gate_update, p.sigma0_landmark, d->x, jv.xy, jv.head, jv.rec,
+                                      jv.pair_lm, jv.pair_j, jv.xb, jv.W_full, jv.W_last, d->stream);
+    struct { int n_match, n_new, n_pairs, zero; ekf::Dense64LmRecord rec[kJointReadings]; double xb[2 * kJointReadings]; } down;
+    static_assert(sizeof(down) == sizeof(int) * 4 + 32 * kJointReadings + 16 * kJointReadings, "the record of one copy");
+    EKFC(leg(finish_timed(d, pms, {{&down, jv.head, jl.record_bytes}})));
+    const int n_new = down.n_new, n_pairs = down.n_pairs;
+    if (n_new < 0 || k + n_new > n_max || n_pairs < 0 || n_pairs > J || down.n_match < 0 || down.n_match + n_new > J)
+        return fail(EKF_ERR_HIP, fn + ": the resolve kernel left an impossible record");
+    const int n_groups = (n_pairs + kJointPairs - 1) / kJointPairs;
+    if (n_groups_out) *n_groups_out = n_groups;
+    for (int j = 0; j < J; j++) {
+        if (best_out) best_out[j] = down.rec[j].best;
+        if (assoc_out) assoc_out[j] = (down.rec[j].kind & ekf::kDense64LmCorrect) ? -2 : -1;
+    }
+    if (n_new == 0 && n_pairs == 0) return EKF_OK;   // every reading dropped: nothing at all is written
+    if (3 + 2 * (k + n_new) > d->live) {
+        if (!(flags & EKF_DENSE64_LM_GROW_LIVE))
+            return fail(EKF_ERR_INVALID, fn + ": the new landmarks do not fit the live dimension (grow it with "
+                                              "ekf_dense64_set_live, or pass EKF_DENSE64_LM_GROW_LIVE)");
+        EKFC(ekf_dense64_set_live(d, 3 + 2 * (k + n_new)));
+    }
+    HIPC(hipEventRecord(d->e0, d->stream));
+    for (int g0 = 0; g0 < n_new; g0 += kJointInit) {   // s = 0, W = sigma0 I, the group's xb
+        const int n = std::min(kJointInit, n_new - g0);
+        init_block_launch(d, 3 + 2 * (k + g0), 2 * n, 0, n == kJointInit ? jv.W_full : jv.W_last, jv.xb + 2 * g0);
+    }
+    if (n_pairs == 0) {   // (a gate_update <= 0: the landmarks are initialised and not corrected)
+        EKFC(leg(finish_timed(d, pms)));
+        *known = k + n_new;
+        return EKF_OK;
+    }
+    int j_next = 0;   // the readings of the pairs, in ascending j, as the groups consume them
+    for (int g = 0; g < n_groups; g++) {
+        const int V = std::min(kJointPairs, n_pairs - g * kJointPairs);
+        if (g > 0) HIPC(hipEventRecord(d->e0, d->stream));
+        joint_correct_launch(d, p, jv, jv.pair_lm + g * kJointPairs, jv.pair_j + g * kJointPairs, V, deferred);
+        // (a refused correction's launches ran and were timed)
+        const ekf_status st = leg(correct_sparse_finish(d, fnc, deferred, 2 * V, nullptr, pms));
+        if (g == 0 && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + n_new;   // the initialisations stand
+        for (int v = 0; v < V; j_next++) {
+            if (!(down.rec[j_next].kind & ekf::kDense64LmCorrect)) continue;
+            if (assoc_out) assoc_out[j_next] = st == EKF_OK ? down.rec[j_next].win : -1;
+            v++;
+        }
+        if (st != EKF_OK) return st;
+    }
+    return EKF_OK;
+}
+
+// what the joint path needs in memory: the buffer of its own, the pending panels, the scoring buffer once for the full map
+ekf_status associate_joint_reserve(ekf_dense64_s* d, const char* fnc, int J, int n_max, bool deferred) {
+    EKFC(joint_reserve(d, fnc));
+    if (deferred) EKFC(pend_reserve(d, fnc));
+    if (n_max > 0) EKFC(sps_reserve(d, L::sps_layout(joint_chunk(J, n_max) * n_max, 2, 5, true, false).bytes, fnc));
     return EKF_OK;
 }
 
@@ -516,7 +633,7 @@ ekf_status ekf_dense64_init_block(ekf_dense64_handle d, int first, int r, int s,
     if (W) HIPC(hipMemcpyAsync(in.W, W, sizeof(double) * r * r, hipMemcpyHostToDevice, d->stream));
     if (xb) HIPC(hipMemcpyAsync(in.xb, xb, sizeof(double) * r, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
-    init_block_launch(d, first, r, s, W != nullptr, xb != nullptr);
+    init_block_launch(d, first, r, s, W ? in.W : nullptr, xb ? in.xb : nullptr);
     return finish_timed(d, elapsed_ms);
 }
 
@@ -795,6 +912,129 @@ ekf_status ekf_dense64_associate_scan(ekf_dense64_handle d, const ekf_params* pa
     std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
     if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
     return associate_readings(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
+}
+
+// ---- a whole scan at once: every reading against one state, one assignment, one stacked correction ----------------------
+// calculate_maha_dis of J readings: the readings go up in one copy, per launch of at most 32768 / count readings the
+// candidates' operands and score_sparse's one launch, the outputs queued behind it; ONE synchronisation.
+ekf_status ekf_dense64_score_readings(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy,
+                                      int first_lm, int count, double* nis_out, int* flag_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_score_readings";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null handle");
+    if (!meas_xy || J < 1 || J > kJointReadings || count < 1 || count > kSparseRows / 2 || first_lm < 0 ||
+        3 + 2 * ((long long)first_lm + count) > d->live || (!nis_out && !flag_out))
+        return fail(EKF_ERR_INVALID, std::string(fnc) + ": bad argument (1 <= J <= 128, 1 <= count <= 32768, the landmarks "
+                                                        "inside the live dimension)");
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    EKFC(joint_reserve(d, fnc));
+    const int chunk = joint_chunk(J, count);
+    EKFC(sps_reserve(d, L::sps_layout(chunk * count, 2, 5, true, false).bytes, fnc));
+    const JointView jv = view(d->joint.p, L::joint_layout());
+    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    hipError_t queued = hipSuccess;
+    score_readings_launch(d, p, jv, J, first_lm, count, chunk, nis_out != nullptr, [&](int j0, int nr, const SpsView& v) {
+        const size_t at = (size_t)j0 * count, n = (size_t)nr * count;
+        if (j0 + nr == J) return;   // the last launch's outputs come down with finish_timed, behind e1
+        if (nis_out && queued == hipSuccess)
+            queued = hipMemcpyAsync(nis_out + at, v.nis, sizeof(double) * n, hipMemcpyDeviceToHost, d->stream);
+        if (flag_out && queued == hipSuccess)
+            queued = hipMemcpyAsync(flag_out + at, v.flag, sizeof(int) * n, hipMemcpyDeviceToHost, d->stream);
+    });
+    HIPC(queued);
+    const int j_last = (J - 1) / chunk * chunk;
+    const size_t at = (size_t)j_last * count, n = (size_t)(J - j_last) * count;
+    const SpsView v = view(d->sps.p, L::sps_layout(chunk * count, 2, 5, true, false), false);
+    return finish_timed(d, elapsed_ms, {{nis_out ? nis_out + at : nullptr, v.nis, sizeof(double) * n},
+                                        {flag_out ? flag_out + at : nullptr, v.flag, sizeof(int) * n}});
+}
+
+// The stacked operands of V pairs from the current state: the two lists go up, one launch into the sparse correction's
+// operand buffer (which every correction fills anew), one synchronisation.  Read-only.
+ekf_status ekf_dense64_joint_operands(ekf_dense64_handle d, const ekf_params* params, int V, const int* lm_idx,
+                                      const double* meas_xy, int* cols_out, double* Hc_out, double* nu_out,
+                                      double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_joint_operands";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null handle");
+    if (!lm_idx || !meas_xy || V < 1 || V > kJointPairs || (!cols_out && !Hc_out && !nu_out))
+        return fail(EKF_ERR_INVALID, std::string(fnc) + ": bad argument (1 <= V <= 30)");
+    for (int v = 0; v < V; v++) {
+        if (lm_idx[v] < 0 || 3 + 2 * ((long long)lm_idx[v] + 1) > d->live)
+            return fail(EKF_ERR_INVALID, std::string(fnc) + ": every landmark must lie inside the live dimension");
+        for (int u = 0; u < v; u++)
+            if (lm_idx[u] == lm_idx[v]) return fail(EKF_ERR_INVALID, std::string(fnc) + ": the landmarks must be distinct");
+    }
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    EKFC(joint_reserve(d, fnc));
+    const JointView jv = view(d->joint.p, L::joint_layout());
+    const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    const int m = 2 * V, s = 3 + 2 * V;
+    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * V, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(jv.pair_lm, lm_idx, sizeof(int) * V, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_joint_operands(d->x, jv.xy, jv.pair_lm, nullptr, V, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu,
+                                       d->stream);
+    return finish_timed(d, elapsed_ms, {{cols_out, cin.cols, sizeof(int) * s},
+                                        {Hc_out, cin.Hc, sizeof(double) * m * s},
+                                        {nu_out, cin.nu, sizeof(double) * m}});
+}
+
+ekf_status ekf_dense64_associate_joint(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy,
+                                       int n_max, int* known, unsigned flags, int* assoc_out, double* best_out,
+                                       int* n_groups_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_associate_joint";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (J < 1 || J > kJointReadings) return fail(EKF_ERR_INVALID, fn + ": J must lie in [1, 128]");
+    EKFC(associate_checks(d, fn, n_max, known, flags));
+    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (n_groups_out) *n_groups_out = 0;
+    for (int j = 0; j < J; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+    }
+    HIPC(hipSetDevice(d->device));
+    EKFC(associate_joint_reserve(d, fnc, J, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
+    return associate_joint(d, fnc, p, J, meas_xy, n_max, known, flags, assoc_out, best_out, n_groups_out, elapsed_ms);
+}
+
+// ekf_dense64_fit_scan, then the path of ekf_dense64_associate_joint on the first min(count, max_readings) centres
+ekf_status ekf_dense64_associate_scan_joint(ekf_dense64_handle d, const ekf_params* params, const double* ranges,
+                                            int n_beams, int max_readings, int n_max, int* known, unsigned flags,
+                                            int* count_out, double* centres_out, int* assoc_out, double* best_out,
+                                            double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_associate_scan_joint";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kScanClusters)
+        return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 128]");
+    EKFC(associate_checks(d, fn, n_max, known, flags));
+    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    *count_out = 0;
+    for (int j = 0; j < max_readings; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
+    }
+    HIPC(hipSetDevice(d->device));
+    EKFC(associate_joint_reserve(d, fnc, max_readings, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
+    ScanRecord rec{};
+    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
+    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
+    *count_out = J;
+    if (J == 0) return EKF_OK;
+    double xy[2 * kScanClusters];
+    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
+    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
+    return associate_joint(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, nullptr, elapsed_ms);
 }
 
 // ---- the reference's prediction() and measurement() on the handle's own state ------------------------------------------

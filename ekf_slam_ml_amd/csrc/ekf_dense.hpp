@@ -184,6 +184,34 @@ void launch_dense64_lm_decide(const double* nis, int count, int known, int n_max
 // state[0] = normalize_angle(state[0]) unless *verdict != 0 (the correction before it refused and wrote nothing)
 void launch_dense64_lm_wrap(double* state, const int* verdict, hipStream_t st);
 
+// ---- the landmark front end for a whole scan at once (ekf_dense64_joint.hip): all readings scored against one state, one
+// assignment, one stacked correction.  xy [J][2]: the readings in device memory, on a 16-byte boundary.
+// One thread per candidate: candidate j * count + i is reading j of xy [n_readings][2] against landmark first_lm + i, its
+// operands exactly those launch_dense64_lm_terms (wrap = 0) writes for reading j alone, at the same place of a buffer cut
+// for n_readings * count <= kDense64ScoreSparseMaxRows / 2 candidates.
+void launch_dense64_joint_terms(const double* state, const double* pose, const double* xy, int n_readings, int first_lm,
+                                int count, double r_meas, int* cols, double* Hc, double* R, double* nu, hipStream_t st);
+// One workgroup per reading over nis [n_readings][count] (count = the known landmarks; 0: nis unread).  pre [b]: best and the
+// runner-up as launch_dense64_lm_decide leaves them; kind = kDense64LmCorrect and win = the landmark for a MATCH (win < count
+// and best < gate_update), kind = kDense64LmNew and win = count for a NEW reading (nothing under gate_new), kind = 0 and
+// win = -1 for a DROP.
+void launch_dense64_joint_argmin(const double* nis, int n_readings, int count, double gate_new, double gate_update,
+                                 Dense64LmRecord* pre, hipStream_t st);
+// One workgroup, J <= kDense64JointMaxReadings threads.  Of the MATCH readings that claim one landmark the smallest (best, j)
+// keeps it, the others drop; the NEW readings take the slots known, known + 1, .. in ascending j while slot < n_max (win =
+// the slot, kind = New | Correct when 0 < gate_update), beyond that they drop.  rec [J]: the final records; head [4] =
+// {n_match, n_new, n_pairs, 0}; pair_lm, pair_j [n_pairs]: landmark and reading of every record with Correct, ascending j;
+// xb [n_new][2] = initialize_landmark (:200-214) at state[0..2]; W_full = sigma0 I at r = 64 (written when n_new >= 32),
+// W_last = sigma0 I at r = 2 (n_new % 32).
+void launch_dense64_joint_resolve(const Dense64LmRecord* pre, int J, int known, int n_max, double gate_update, double sigma0,
+                                  const double* state, const double* xy, int* head, Dense64LmRecord* rec, int* pair_lm,
+                                  int* pair_j, double* xb, double* W_full, double* W_last, hipStream_t st);
+// One workgroup: the stacked operands of V <= kDense64JointMaxPairs pairs (landmark lm [v], reading rj [v] of xy, or reading
+// v when rj is NULL) from `state`: cols [3 + 2 V], Hc [2 V][3 + 2 V] (zero outside the pose columns and the pair's own two),
+// R [2 V][2 V] = r_meas I, nu [2 V] with the bearing wrapped.  The landmarks distinct and inside the state (not checked).
+void launch_dense64_joint_operands(const double* state, const double* xy, const int* lm, const int* rj, int V, double r_meas,
+                                   int* cols, double* Hc, double* R, double* nu, hipStream_t st);
+
 // ---- the reference's motion model and the top of its measurement() on the handle's state (ekf_dense64_model.hip).
 // One thread: Fr [3][3] = eye + A, Qr [3][3] = q_pose I, upd [3] of prediction() (:67-96) for the heading state[0] and the
 // twist (dtheta, dx); |dtheta| < straight_eps takes the straight branch.  Fr, Qr, upd: where propagate_block's operands go.

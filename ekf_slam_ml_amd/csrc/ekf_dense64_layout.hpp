@@ -17,6 +17,9 @@ constexpr int kDense64PendingMaxRows = 64;           // rows of K and T that wai
 constexpr int kDense64ReadMax = 65536;               // entries of one block readout
 constexpr int kDense64ScanMaxBeams = 1024;           // beams of one laser scan
 constexpr int kDense64ScanMaxClusters = 128;         // clusters of one scan, and the most circles a call returns
+constexpr int kDense64JointMaxReadings = 128;        // readings of one joint association (= kDense64ScanMaxClusters)
+constexpr int kDense64JointMaxPairs = 30;            // pairs of one stacked correction: m = 2 V <= 64 and s = 3 + 2 V <= 64
+constexpr int kDense64JointInitGroup = 32;           // new landmarks of one initialisation: r = 2 n <= 64
 
 namespace d64 {
 constexpr size_t kF = sizeof(double), kI = sizeof(int), kM = kDense64MaxM, kR = kDense64MaxR, kS = kDense64MaxS;
@@ -71,6 +74,17 @@ inline ScanLayout scan_layout() {
     const size_t nb = kDense64ScanMaxBeams, nc = kDense64ScanMaxClusters, head = kF * nb, centres = head + 2 * kI,
                  radii = centres + kF * 2 * nc, all = radii + kF * nc;
     return {0, head, centres, radii, all, all + kF * 4 * nc, all - head};
+}
+// the joint association: the readings [128][2] as they went up | the per-reading records of k_djt_argmin [128] (32 bytes each)
+// | what comes down in one copy: head (ints: n_match, n_new, n_pairs, 0) | the final records [128] | the stacked xb [128][2] |
+// and what stays on the device: the pairs' landmarks and readings (ints) [128] each | W = sigma0 I at r = 64 | W at the
+// r < 64 of the last initialisation group.  Every region on a 16-byte boundary.
+struct JointLayout { size_t xy, pre, head, rec, xb, pair_lm, pair_j, W_full, W_last, bytes, record_bytes; };
+inline JointLayout joint_layout() {
+    const size_t nj = kDense64JointMaxReadings, rb = 32, pre = 2 * kF * nj, head = pre + rb * nj, rec = head + 4 * kI,
+                 xb = rec + rb * nj, pair_lm = xb + 2 * kF * nj, pair_j = pair_lm + kI * nj, W_full = pair_j + kI * nj,
+                 W_last = W_full + kF * kR * kR;
+    return {0, pre, head, rec, xb, pair_lm, pair_j, W_full, W_last, W_last + kF * kR * kR, pair_lm - head};
 }
 }  // namespace d64
 }  // namespace ekf

@@ -84,6 +84,12 @@ struct LmMeasureView { double *pose, *xy; };
 inline LmMeasureView view(void* b, const L::LmMeasureLayout& l) { return {f64(b, l.pose), f64(b, l.xy)}; }
 struct ScanView { double* ranges; int* head; double *centres, *radii, *all; };
 inline ScanView view(void* b, const L::ScanLayout& l) { return {f64(b, l.ranges), i32(b, l.head), f64(b, l.centres), f64(b, l.radii), f64(b, l.all)}; }
+struct JointView { double* xy; ekf::Dense64LmRecord* pre; int* head; ekf::Dense64LmRecord* rec; double* xb; int *pair_lm, *pair_j; double *W_full, *W_last; };
+inline JointView view(void* b, const L::JointLayout& l) {
+    return {f64(b, l.xy), reinterpret_cast<ekf::Dense64LmRecord*>(f64(b, l.pre)), i32(b, l.head),
+            reinterpret_cast<ekf::Dense64LmRecord*>(f64(b, l.rec)), f64(b, l.xb), i32(b, l.pair_lm), i32(b, l.pair_j),
+            f64(b, l.W_full), f64(b, l.W_last)};
+}
 
 // The end of a timed entry point: e1 behind the launches, the launch error, the copies back to the host (a null dst is
 // skipped), ONE synchronisation, the time between the handle's events.
@@ -124,6 +130,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf pend;       // PendLayout (ekf_dense64_correct_sparse_deferred)
     ekfrt::DeviceBuf lm_rec;     // ekf::Dense64LmRecord, the decision record of one reading (the landmark front end)
     ekfrt::DeviceBuf scan;       // ScanLayout (ekf_dense64_fit_scan, ekf_dense64_associate_scan)
+    ekfrt::DeviceBuf joint;      // JointLayout (ekf_dense64_associate_joint, ekf_dense64_joint_operands)
     ekfrt::DeviceBuf pairs;      // Dense64PairsPlan (ekf_dense64_score_landmark_pairs), grows with n_lm
     ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)

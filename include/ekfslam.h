@@ -753,6 +753,85 @@ ekf_status ekf_dense64_associate_scan(ekf_dense64_handle h, const ekf_params* pa
                                       int* assoc_out /* [max_readings] nullable */,
                                       double* best_out /* [max_readings] nullable */, double* elapsed_ms);
 
+/* A whole scan associated JOINTLY: the textbook alternative to the reading-by-reading rule above, and a new capability
+ * beside it, not a faster form of it.  All J readings are scored against the state the scan was taken at (as the reference's
+ * measurement() captures the pose once per call, :109-111), ONE assignment is made, and the matched and new readings are
+ * corrected in stacked updates of dimension 2 V.  ekf_dense64_associate_landmarks pays two synchronisations, a scoring launch
+ * over the map and (eager) a pass over Sigma PER READING; this call pays one decision synchronisation per scan and one pass
+ * per 30 readings.  The results differ from the sequential rule's wherever a reading's correction would have moved a later
+ * reading's scores; with J = 1 the two calls coincide bit for bit (state, Sigma, pending rows, assoc_out, best_out).
+ * ekf_dense64_score_readings: read-only.  Candidate (j, i) is reading j against landmark first_lm + i; nis_out and flag_out
+ *   [J][count] (nullable, not both NULL) are bit for bit what ekf_dense64_score_landmarks returns for reading j alone: the
+ *   same model source, the same scoring kernel, read-through with rows pending.  The readings go up once in one copy, they
+ *   are cut into launches of at most 32768 / count readings (a launch stays within EKF_DENSE64_SCORE_SPARSE_MAX_ROWS), and
+ *   the outputs come down behind ONE synchronisation.  1 <= J <= EKF_DENSE64_JOINT_MAX_READINGS, 1 <= count <= 32768,
+ *   first_lm >= 0, 3 + 2 (first_lm + count) <= live; otherwise EKF_ERR_INVALID before the device is looked at.
+ * ekf_dense64_joint_operands: a read-only hook, the stacked operands the joint correction would use for V pairs (landmark
+ *   lm_idx[v], reading v), built from the CURRENT state: cols = {0, 1, 2, 3 + 2 i0, 4 + 2 i0, 3 + 2 i1, ..}; Hc [2V][3 + 2V]
+ *   is zero except that rows 2v and 2v + 1 hold the reference's Hj (:158-166) at the local columns 0 .. 2 and 3 + 2v, 4 + 2v;
+ *   nu [2V] has its bearing wrapped (:183); R = r_meas I is implied and not returned.  At V = 1 these are the operands of
+ *   ekf_dense64_score_landmarks with the bearing wrapped.  1 <= V <= EKF_DENSE64_JOINT_MAX_PAIRS, the landmarks distinct
+ *   and inside the live dimension, the outputs nullable but not all NULL; otherwise EKF_ERR_INVALID.
+ * ekf_dense64_associate_joint, THE JOINT RULE:
+ *   1 SCORE: all J readings against landmarks 0 .. *known - 1 at the state on entry, as ekf_dense64_score_readings does.
+ *   2 PER READING: best = gate_new, win = known, the lexicographic (score, index) minimum with NaNs skipped, as THE RULE
+ *     above.  MATCH when win < known and best < gate_update; NEW when win == known; otherwise DROP.
+ *   3 RESOLVE: of the MATCH readings that claim one landmark the smallest (best, j) keeps it and the others become DROP.
+ *     The NEW readings take the slots known, known + 1, .. in ascending j while slot < n_max; beyond that they become DROP.
+ *     TWO READINGS CLASSED NEW IN ONE CALL GIVE TWO LANDMARKS, also when they see the same object: nothing is scored
+ *     against a landmark that does not exist yet.  ekf_dense64_score_landmark_pairs / ekf_dense64_merge_landmarks is the
+ *     repair.  The records, the counts and the new landmarks' positions (initialize_landmark, :200-214, at the pose on
+ *     entry) come down in one copy behind the FIRST synchronisation; best_out[j] is filled from it.
+ *   4 LIVE: checked once, 3 + 2 (known + n_new) <= live.  EKF_DENSE64_LM_GROW_LIVE grows it by one ekf_dense64_set_live;
+ *     without the flag the call returns EKF_ERR_INVALID and nothing at all has been written.
+ *   5 INIT: the new landmarks in groups of at most 32, each ONE pass through ekf_dense64_init_block's path with first =
+ *     3 + 2 slot, r = 2 n, s = 0, W = sigma0_landmark I and the stacked positions -- bit for bit n calls with r = 2; carry
+ *     and pending rows as that call defines.  *known grows by the number initialised.
+ *   6 CORRECT: the pairs are the MATCH and NEW readings with their landmarks in ascending j (MATCH only with gate_update
+ *     <= 0, as in the sequential call), cut greedily into groups of at most EKF_DENSE64_JOINT_MAX_PAIRS.  Per group the
+ *     operands of ekf_dense64_joint_operands are built from the THEN-CURRENT state, ekf_dense64_correct_sparse (or
+ *     _deferred with EKF_DENSE64_LM_DEFERRED) runs through its internal path at m = 2 V, s = 3 + 2 V, and the heading is
+ *     normalised and stored.  Each group has the correction's own synchronisation.
+ *   assoc_out[j] (nullable): the landmark corrected; -1 for a dropped reading, one that lost a conflict, one that
+ *   initialised a landmark without correcting it, or one of a refused group; -2 for a reading of a group that was not
+ *   reached.  best_out[j] (nullable) as above.  n_groups_out (nullable): the number of groups the pairs were cut into.
+ *   TWIN CONTRACT: the state, Sigma, the pending rows and *known afterwards are bit for bit those of a twin handle on which
+ *   the host calls ekf_dense64_score_landmarks per reading, applies the rule, calls ekf_dense64_init_block per group, then
+ *   per group ekf_dense64_joint_operands followed by ekf_dense64_correct_sparse[_deferred] with what it returned and
+ *   R = r_meas I, and sets the heading.
+ *   FAILURES, checked before the device is looked at, in this order: NULL handle; NULL known or meas_xy; J outside [1,
+ *   EKF_DENSE64_JOINT_MAX_READINGS]; then the checks of ekf_dense64_associate_landmarks unchanged (n_max, *known, the live
+ *   dimension, flag bits); n_max > 32768 -> EKF_ERR_INVALID, nothing changes.  A singular or non-finite S of a group
+ *   returns EKF_ERR_STATE with that group's correction undone as the sparse calls define; earlier groups and the
+ *   initialisations stand, *known is what it was after the initialisations.
+ *   No floating-point atomics and no in-kernel waits; every reduction resolves ties to the lower index, so the same inputs
+ *   give the same bits on every run.  Memory: 78 KB for the call's own buffer, the scoring buffer reserved once per call for
+ *   min(J, 32768 / n_max) n_max candidates, the pending panels with EKF_DENSE64_LM_DEFERRED.
+ * ekf_dense64_associate_scan_joint: ekf_dense64_fit_scan(max_out = max_readings) followed by the same path on the centres,
+ *   exactly as ekf_dense64_associate_scan wraps the sequential loop; its checks first, in that call's order.
+ * elapsed_ms (nullable) = HIP-event time of the launches, summed over the call's synchronisations. */
+#define EKF_DENSE64_JOINT_MAX_READINGS 128   /* = EKF_DENSE64_SCAN_MAX_CIRCLES */
+#define EKF_DENSE64_JOINT_MAX_PAIRS     30   /* m = 2V <= 64 and s = 3 + 2V <= 64 */
+ekf_status ekf_dense64_score_readings(ekf_dense64_handle h, const ekf_params* params, int J,
+                                      const double* meas_xy /* [J][2] */, int first_lm, int count,
+                                      double* nis_out /* [J][count] nullable */, int* flag_out /* [J][count] nullable */,
+                                      double* elapsed_ms);
+ekf_status ekf_dense64_joint_operands(ekf_dense64_handle h, const ekf_params* params, int V,
+                                      const int* lm_idx /* [V] */, const double* meas_xy /* [V][2] */,
+                                      int* cols_out /* [3 + 2V] nullable */, double* Hc_out /* [2V][3 + 2V] nullable */,
+                                      double* nu_out /* [2V] bearing wrapped, nullable */, double* elapsed_ms);
+ekf_status ekf_dense64_associate_joint(ekf_dense64_handle h, const ekf_params* params, int J,
+                                       const double* meas_xy /* [J][2] */, int n_max, int* known /* IN/OUT */,
+                                       unsigned flags, int* assoc_out /* [J] nullable */,
+                                       double* best_out /* [J] nullable */, int* n_groups_out /* nullable */,
+                                       double* elapsed_ms);
+ekf_status ekf_dense64_associate_scan_joint(ekf_dense64_handle h, const ekf_params* params,
+                                            const double* ranges /* [n_beams] */, int n_beams, int max_readings,
+                                            int n_max, int* known /* IN/OUT */, unsigned flags,
+                                            int* count_out, double* centres_out /* [max_readings][2] nullable */,
+                                            int* assoc_out /* [max_readings] nullable */,
+                                            double* best_out /* [max_readings] nullable */, double* elapsed_ms);
+
 /* The other two methods of rigid2d::EKF_SLAM on the handle's own state: prediction() (ekf_slam.cpp:55-106) and measurement()
  * (:108-197).  After ekf_dense64_associate_landmarks the heading lives on the device only -- it is corrected there and
  * nothing is read back -- so a caller of the model-free ekf_dense64_propagate_block would fetch state[0], evaluate four
