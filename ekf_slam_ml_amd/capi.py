@@ -56,6 +56,7 @@ SYMBOLS = [
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
+    "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -82,6 +83,13 @@ class Params(C.Structure):
     """ekf_params (include/ekfslam.h); defaults are the reference's hard-coded constants."""
     _fields_ = [("sigma0_landmark", C.c_double), ("q_pose", C.c_double), ("r_meas", C.c_double),
                 ("gate_new", C.c_double), ("gate_update", C.c_double), ("straight_eps", C.c_double)]
+
+
+class HealthReport(C.Structure):
+    """ekf_dense64_health_report (include/ekfslam.h)"""
+    _fields_ = [("n_nonfinite", C.c_longlong), ("n_asym", C.c_longlong), ("n_diag_bad", C.c_longlong),
+                ("n_minor", C.c_longlong), ("max_asym", C.c_double), ("min_diag", C.c_double),
+                ("asym_i", C.c_int), ("asym_j", C.c_int), ("min_diag_i", C.c_int), ("reserved", C.c_int)]
 
 
 class KnownLogC(C.Structure):
@@ -241,6 +249,9 @@ def load():
         "ekf_dense64_score_landmark_pairs": [h, C.c_int, C.c_double, C.c_double, _ip, _dp, C.POINTER(C.c_longlong),
                                              C.POINTER(C.c_longlong), _dp],
         "ekf_dense64_merge_landmarks": [h, C.POINTER(Params), C.c_int, C.c_int, C.c_double, _ip, C.c_int, _ip, _dp, _dp],
+        "ekf_dense64_health_launch_info": [h, _ip, _ip],
+        "ekf_dense64_health": [h, C.POINTER(HealthReport), _dp],
+        "ekf_dense64_symmetrize": [h, C.POINTER(C.c_longlong), _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
@@ -1026,6 +1037,40 @@ class DensePropagator64(_DensePropagatorBase):
                                                      C.byref(k), flags, C.byref(moved), C.byref(d2), C.byref(ms)))
         return k.value, moved.value, d2.value, ms.value
 
+    def _open(self):
+        if not getattr(self, "_h", None):
+            raise ValueError("the handle is closed")
+
+    def health(self):
+        """Is Sigma[:live, :live] still a covariance?  One read-only pass on the device (ekf_dense64_health_report,
+        include/ekfslam.h): n_nonfinite (NaN or Inf entries), n_asym (pairs i < j whose two entries differ in bits),
+        max_asym / asym_i / asym_j (the largest |Sigma[i][j] - Sigma[j][i]| on its bit pattern, so a NaN wins, and the
+        lowest (i, j) that attains it; 0.0, -1, -1 with no pair), min_diag / min_diag_i (the smallest diagonal entry that
+        is not a NaN, lowest index on equal values; +inf, -1 with none), n_diag_bad (diagonal entries NaN or <= 0),
+        n_minor (pairs with Sigma[i][j] Sigma[j][i] > Sigma[i][i] Sigma[j][j]) and ms.  Flushes the pending rows first."""
+        self._open()
+        rep, ms = HealthReport(), C.c_double()
+        _check(self._lib.ekf_dense64_health(self._h, C.byref(rep), C.byref(ms)))
+        out = {name: getattr(rep, name) for name, _ in HealthReport._fields_ if name != "reserved"}
+        out["ms"] = ms.value
+        return out
+
+    def symmetrize(self):
+        """Sigma[i][j] = Sigma[j][i] = 0.5 * (Sigma[i][j] + Sigma[j][i]) for every pair i < j < live whose two entries
+        differ in bits, in place on the device; equal pairs and the diagonal are not written.  Flushes the pending rows
+        first.  Returns {changed: the pairs written, max_asym: as health()'s before the call, ms}"""
+        self._open()
+        changed, most, ms = C.c_longlong(), C.c_double(), C.c_double()
+        _check(self._lib.ekf_dense64_symmetrize(self._h, C.byref(changed), C.byref(most), C.byref(ms)))
+        return {"changed": changed.value, "max_asym": most.value, "ms": ms.value}
+
+    def health_launch_info(self):
+        """{tile, threads}: the side of health()'s and symmetrize()'s tiles in states and their workgroup size (test hook)"""
+        self._open()
+        tile, th = C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_health_launch_info(self._h, C.byref(tile), C.byref(th)))
+        return {"tile": tile.value, "threads": th.value}
+
     def _correct_sparse(self, entry, cols, Hc, R, nu):
         cols = self._index_lists(cols, 1)
         s = cols.shape[0]
@@ -1532,6 +1577,14 @@ class DenseEKFSLAM:
         flags = (self.handle.LM_DEFERRED if self.deferred else 0) | (self.handle.LM_GROW_LIVE if self.grow_live else 0)
         self._known, moved, d2, _ = self.handle.merge_landmarks(a, b, r_merge, self._known, flags, self.params)
         return moved, d2
+
+    def health(self):
+        """DensePropagator64.health() of the live corner: is the covariance still one?"""
+        return self.handle.health()
+
+    def symmetrize(self):
+        """DensePropagator64.symmetrize(): both halves of the live corner equal again, at the caller's cadence"""
+        return self.handle.symmetrize()
 
     @property
     def state(self):

@@ -4,7 +4,8 @@
 // scoring for a Jacobian given by its non-zero columns (ekf_dense64_sparse.hip), the (re)initialisation of a block of states
 // and the block readout (ekf_dense64_init.hip), the exchange of two blocks (ekf_dense64_swap.hip), the landmark front end
 // (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), the
-// scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
+// scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), the health check of the live corner and its
+// exact symmetrisation (ekf_dense64_health.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 // The structured calls run at the handle's LIVE dimension (ekf_dense64_set_live, N by default): every launch of theirs is
@@ -38,7 +39,7 @@ ekf_status ekf_dense64_s::created() {
 
 void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
     for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p})
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p, health.p})
         if (p) (void)hipFree(p);
     scan_up.release();
 }
@@ -730,6 +731,68 @@ ekf_status ekf_dense64_coupling(ekf_dense64_handle d, int Na, long long* nonzero
     EKFC(finish_timed(d, elapsed_ms, {{out, d->corr_out, sizeof(out)}}));
     *nonzero = (long long)out[0];
     if (max_abs) std::memcpy(max_abs, &out[1], sizeof(double));
+    return EKF_OK;
+}
+
+// ---- the health of the live corner and its symmetrisation (ekf_dense64_health.hip) ----------------------------------------
+ekf_status ekf_dense64_health_launch_info(ekf_dense64_handle d, int* tile, int* threads) {
+    if (!d || !tile || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_health_launch_info: null argument");
+    *tile = ekf::kDense64HealthTile;
+    *threads = ekf::kDense64HealthThreads;
+    return EKF_OK;
+}
+
+namespace {
+// the workspace for the live dimension and its result words set to zero; before e0
+ekf_status health_reserve(ekf_dense64_s* d, const char* fn, ekf::Dense64HealthPlan* pl) {
+    *pl = ekf::dense64_health_plan(d->live);
+    EKFC(d->health.reserve(pl->bytes, d->stream, false, fn, "the health pass's workspace"));
+    HIPC(hipMemsetAsync(d->health.as<char>() + pl->off_words, 0, sizeof(unsigned long long) * ekf::kDense64HealthWords, d->stream));
+    return EKF_OK;
+}
+}  // namespace
+
+// The result words are zeroed, the pending rows applied, three launches; the words come back behind the one synchronisation.
+ekf_status ekf_dense64_health(ekf_dense64_handle d, ekf_dense64_health_report* out, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_health";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null report");
+    HIPC(hipSetDevice(d->device));
+    ekf::Dense64HealthPlan pl;
+    EKFC(health_reserve(d, fn, &pl));
+    unsigned long long w[ekf::kDense64HealthWords] = {};
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_health(pl, d->S, d->ld, d->health.p, d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{w, d->health.as<char>() + pl.off_words, sizeof(w)}}));
+    const bool pair = w[ekf::kDense64HealthMaxLoc] != ~0ull;
+    *out = ekf_dense64_health_report{};
+    out->n_nonfinite = (long long)w[ekf::kDense64HealthNonfinite];
+    out->n_asym = (long long)w[ekf::kDense64HealthAsym];
+    out->n_diag_bad = (long long)w[ekf::kDense64HealthDiagBad];
+    out->n_minor = (long long)w[ekf::kDense64HealthMinor];
+    std::memcpy(&out->max_asym, &w[ekf::kDense64HealthMaxBits], sizeof(double));
+    std::memcpy(&out->min_diag, &w[ekf::kDense64HealthMinDiag], sizeof(double));
+    out->asym_i = pair ? (int)(w[ekf::kDense64HealthMaxLoc] >> 32) : -1;
+    out->asym_j = pair ? (int)(w[ekf::kDense64HealthMaxLoc] & 0xffffffffull) : -1;
+    out->min_diag_i = (int)(long long)w[ekf::kDense64HealthMinDiagIdx];
+    return EKF_OK;
+}
+
+// The result words are zeroed, the pending rows applied, one launch in place.
+ekf_status ekf_dense64_symmetrize(ekf_dense64_handle d, long long* n_changed, double* max_asym, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_symmetrize";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    HIPC(hipSetDevice(d->device));
+    ekf::Dense64HealthPlan pl;
+    EKFC(health_reserve(d, fn, &pl));
+    unsigned long long w[ekf::kDense64HealthWords] = {};
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_symmetrize(pl, d->S, d->ld, d->health.p, d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{w, d->health.as<char>() + pl.off_words, sizeof(w)}}));
+    if (n_changed) *n_changed = (long long)w[ekf::kDense64HealthAsym];
+    if (max_asym) std::memcpy(max_asym, &w[ekf::kDense64HealthMaxBits], sizeof(double));
     return EKF_OK;
 }
 

@@ -258,4 +258,35 @@ void launch_dense64_pairs(const Dense64PairsPlan& p, const double* Sigma, const 
 // innovation of the reading 0 of x[lo] - x[hi], the exact negative of the score's nu (S and nis keep their bits).
 void launch_dense64_pair_terms(const double* state, int lo, int hi, double r_merge, int* cols, double* Hc, double* R,
                                double* nu, hipStream_t st);
+
+// ---- the health of the live corner and its exact symmetrisation (ekf_dense64_health.hip; the definitions of every figure
+// are include/ekfslam.h's, ekf_dense64_health_report).  A workgroup per tile pair (A <= B) of kDense64HealthTile states a
+// side: Sigma[A rows, B cols] along rows from memory, Sigma[B rows, A cols] along rows through an LDS transpose.
+constexpr int kDense64HealthTile = 64;
+constexpr int kDense64HealthThreads = 256;
+// the result words of a call, 64-bit each, zero before the launch
+enum {
+    kDense64HealthNonfinite = 0,   // count (health)
+    kDense64HealthAsym,            // count of pairs that differ in bits (health; symmetrize: the pairs written)
+    kDense64HealthMinor,           // count (health)
+    kDense64HealthDiagBad,         // count (health)
+    kDense64HealthMaxBits,         // the bits of the largest |Sigma[i][j] - Sigma[j][i]| (both)
+    kDense64HealthMaxLoc,          // i << 32 | j of it, all ones without a pair (health)
+    kDense64HealthMinDiag,         // the bits of the smallest diagonal entry, +Inf without one (health)
+    kDense64HealthMinDiagIdx,      // its index as a signed 64-bit number, -1 without one (health)
+    kDense64HealthWords
+};
+// the workspace of a call, byte offsets: words | diag [tiles * 64] | one (max, loc) record per tile pair | one (value,
+// index) record per 256 diagonal entries
+struct Dense64HealthPlan {
+    int Na, tiles, diag_groups;
+    size_t pairs, off_words, off_diag, off_rec_max, off_rec_loc, off_drec_val, off_drec_idx, bytes;
+};
+Dense64HealthPlan dense64_health_plan(int Na);
+// Three launches (the diagonal, the tile pairs, the fold); Sigma[0:Na, 0:Na] is read once (the diagonal twice), nothing of
+// it is written.  Nothing at a row or column index >= Na is read (Na <= the dimension: the launcher does not check).
+void launch_dense64_health(const Dense64HealthPlan& p, const double* Sigma, int ld, void* ws, hipStream_t st);
+// One launch, in place: reads the corner once, writes the two entries of every pair i < j < Na that differ in bits.  Only
+// the first kDense64HealthWords words of the workspace are used: [Asym] and [MaxBits].
+void launch_dense64_symmetrize(const Dense64HealthPlan& p, double* Sigma, int ld, void* ws, hipStream_t st);
 }  // namespace ekf

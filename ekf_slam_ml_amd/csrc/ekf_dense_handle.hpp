@@ -132,6 +132,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf scan;       // ScanLayout (ekf_dense64_fit_scan, ekf_dense64_associate_scan)
     ekfrt::DeviceBuf joint;      // JointLayout (ekf_dense64_associate_joint, ekf_dense64_joint_operands)
     ekfrt::DeviceBuf pairs;      // Dense64PairsPlan (ekf_dense64_score_landmark_pairs), grows with n_lm
+    ekfrt::DeviceBuf health;     // Dense64HealthPlan (ekf_dense64_health, ekf_dense64_symmetrize), grows with live
     ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads

@@ -1106,6 +1106,68 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle h, const ekf_params* p
                                        int* known, int flags /* EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE */,
                                        int* moved_from, double* d2_out, double* elapsed_ms);
 
+/* Is Sigma still a covariance, and the exact repair of its symmetry.  Every call above keeps the contract "Sigma is never
+ * symmetrised" (T = H Sigma is taken from rows, U = Sigma H^T from columns), so rounding lets Sigma[i][j] and Sigma[j][i]
+ * drift apart over a long run.  ekf_dense64_health measures that, and what else stops a matrix from being a covariance,
+ * without Sigma leaving the device; ekf_dense64_symmetrize makes the two halves equal again, at the caller's own cadence.
+ * Both are opt-in: no other entry point calls them or launches anything different because they exist.
+ * Both are structured calls: they run on the live corner Sigma[0:Na, 0:Na], Na = live (N by default), and nothing at a row
+ * or column index >= Na is read or written (the tiles' loads and stores are masked element by element).  Both need Sigma
+ * in memory, so they FLUSH THE PENDING ROWS FIRST, after their own argument checks, as ekf_dense64_coupling does.  Neither
+ * touches the state vector.  A bad argument returns EKF_ERR_INVALID before the device is looked at and changes nothing, the
+ * pending rows included.
+ * ekf_dense64_health: read-only on Sigma, one pass over the corner (8 Na^2 bytes).  DEFINITIONS, all over i, j < Na, every
+ * operation in IEEE binary64, round to nearest even, each rounded on its own (fl), subnormals kept:
+ *   n_nonfinite   entries Sigma[i][j] that are a NaN or +-Inf (the diagonal included)
+ *   n_asym        pairs i < j whose two entries differ in BITS (so -0.0 against +0.0 counts, and two NaNs of different
+ *                 payload; two NaNs of the same bits do not)
+ *   max_asym, asym_i, asym_j
+ *                 with d = fl(Sigma[i][j] - Sigma[j][i]), one plain subtraction per pair i < j: the maximum of |d| taken on
+ *                 the 64-bit pattern of |d| (sign bit cleared, compared as an unsigned integer: the order of the values for
+ *                 everything that is not a NaN, every NaN above +Inf, NaNs among themselves by payload); max_asym is the
+ *                 double of that pattern, so it is a NaN if any d is.  (asym_i, asym_j) is the lexicographically lowest
+ *                 (i, j), i < j, that attains the maximum.  With no pair (Na = 1): 0.0 and -1, -1.  A symmetric corner with
+ *                 Na >= 2 gives 0.0 at (0, 1).
+ *   min_diag, min_diag_i
+ *                 the smallest Sigma[i][i] by value among the diagonal entries that are not a NaN; on equal values (-0.0
+ *                 equals +0.0) the lowest index wins and min_diag has that entry's bits.  All NaN: +Inf and -1.
+ *   n_diag_bad    diagonal entries that are a NaN or <= 0 (-0.0 and +0.0 are <= 0)
+ *   n_minor       pairs i < j with fl(Sigma[i][j] * Sigma[j][i]) > fl(Sigma[i][i] * Sigma[j][j]): a negative 2 x 2 principal
+ *                 minor, a necessary condition of positive semi-definiteness that costs no further traffic.  Each product
+ *                 is rounded once (no fused operation); a comparison that involves a NaN is false and is not counted.
+ * A NULL handle (checked first) or a NULL report returns EKF_ERR_INVALID.
+ * ekf_dense64_symmetrize: for every pair i < j < Na whose two entries differ in bits, both are set to
+ *   v = fl(0.5 * fl(Sigma[i][j] + Sigma[j][i]))      one addition, one halving
+ * (the halving is exact unless v is subnormal; a sum that overflows gives +-Inf; a NaN operand gives a NaN with that
+ * operand's payload as the hardware's addition hands it on).  A pair whose entries hold the same bits is NOT WRITTEN, so NaN
+ * payloads of equal pairs survive; the diagonal is never written.  Afterwards Sigma[i][j] and Sigma[j][i] hold the same bits
+ * for all i, j < Na; a second call writes nothing and returns *n_changed = 0; a symmetric corner is only read.
+ *   *n_changed (nullable)  the pairs written = n_asym of a health call made just before
+ *   *max_asym  (nullable)  as defined above, on the values before the call
+ * 8 Na^2 bytes are read and at most 8 Na^2 written, in place: one workgroup owns both tiles of a tile pair, so there is no
+ * staging buffer of size Na^2.  A NULL handle returns EKF_ERR_INVALID.
+ * Both calls: a workgroup per tile pair (A <= B) of the corner; Sigma[A rows, B cols] is read (and written) along rows,
+ * Sigma[B rows, A cols] along rows too, through a transpose in LDS -- no walk down a column of Sigma on either side.
+ * Integer counters, an integer maximum of bit patterns, locations that are pure functions of the data (per-tile records and
+ * a fold): no floating-point atomics, a run repeats bit for bit.  The workspace (16 bytes per tile pair and 8 per state,
+ * about 0.3 MB at Na = 10003) is allocated by the first call and grows with Na; a failure there returns EKF_ERR_NOMEM and
+ * leaves the handle as it was.  ekf_dense64_health_launch_info reports the tile side in states and the workgroup size.
+ * Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the launches, the flush included. */
+typedef struct ekf_dense64_health_report {
+    long long n_nonfinite;
+    long long n_asym;
+    long long n_diag_bad;
+    long long n_minor;
+    double max_asym;
+    double min_diag;
+    int asym_i, asym_j;
+    int min_diag_i;
+    int reserved;   /* 0 */
+} ekf_dense64_health_report;
+ekf_status ekf_dense64_health_launch_info(ekf_dense64_handle h, int* tile, int* threads);
+ekf_status ekf_dense64_health(ekf_dense64_handle h, ekf_dense64_health_report* out, double* elapsed_ms);
+ekf_status ekf_dense64_symmetrize(ekf_dense64_handle h, long long* n_changed, double* max_asym, double* elapsed_ms);
+
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
  * ekf_dense64_get_sigma_block: out[a][c] = Sigma[rows[a]][cols[c]], nr x nc row-major; one gather launch into a buffer
