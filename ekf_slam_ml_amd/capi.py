@@ -57,6 +57,7 @@ SYMBOLS = [
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
+    "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -90,6 +91,12 @@ class HealthReport(C.Structure):
     _fields_ = [("n_nonfinite", C.c_longlong), ("n_asym", C.c_longlong), ("n_diag_bad", C.c_longlong),
                 ("n_minor", C.c_longlong), ("max_asym", C.c_double), ("min_diag", C.c_double),
                 ("asym_i", C.c_int), ("asym_j", C.c_int), ("min_diag_i", C.c_int), ("reserved", C.c_int)]
+
+
+class FactorReport(C.Structure):
+    """ekf_dense64_factor_report (include/ekfslam.h)"""
+    _fields_ = [("ok", C.c_int), ("fail_index", C.c_int), ("min_pivot_i", C.c_int), ("Na", C.c_int),
+                ("fail_pivot", C.c_double), ("min_pivot", C.c_double), ("max_pivot", C.c_double), ("logdet", C.c_double)]
 
 
 class KnownLogC(C.Structure):
@@ -252,6 +259,10 @@ def load():
         "ekf_dense64_health_launch_info": [h, _ip, _ip],
         "ekf_dense64_health": [h, C.POINTER(HealthReport), _dp],
         "ekf_dense64_symmetrize": [h, C.POINTER(C.c_longlong), _dp, _dp],
+        "ekf_dense64_factor_launch_info": [h, _ip, _ip],
+        "ekf_dense64_factor": [h, C.POINTER(FactorReport), _dp],
+        "ekf_dense64_get_factor": [h, _dp],
+        "ekf_dense64_whiten": [h, C.c_int, _dp, _dp, _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
@@ -1071,6 +1082,54 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_health_launch_info(self._h, C.byref(tile), C.byref(th)))
         return {"tile": tile.value, "threads": th.value}
 
+    WHITEN_MAX_RHS = 64   # EKF_DENSE64_WHITEN_MAX_RHS
+
+    def factor(self):
+        """The Cholesky factor L of Sigma[:live, :live] (its lower triangle: Sigma[i][j], j <= i), taken on the device into
+        a snapshot buffer of the handle's own; Sigma and the state are only read.  Flushes the pending rows first.  Returns
+        ekf_dense64_factor_report (include/ekfslam.h) as a dict: ok (1: Sigma is positive definite), fail_index / fail_pivot
+        (the first column whose pivot was not finite and > 0), min_pivot / max_pivot / min_pivot_i (of L[j][j]^2 over the
+        columns factored), Na, logdet (log det Sigma summed on the host; NaN unless ok) and ms."""
+        self._open()
+        rep, ms = FactorReport(), C.c_double()
+        _check(self._lib.ekf_dense64_factor(self._h, C.byref(rep), C.byref(ms)))
+        out = {name: getattr(rep, name) for name, _ in FactorReport._fields_}
+        out["ms"] = ms.value
+        self._factor_na = rep.Na
+        return out
+
+    def get_factor(self):
+        """L of the last factor(), Na x Na (the live dimension it was taken at) with an exactly zero strict upper triangle:
+        the snapshot as taken, whatever has happened to Sigma or the live dimension since.  EkfError (EKF_ERR_STATE) before
+        the first factor() and after one that ended with ok == 0."""
+        self._open()
+        Na = getattr(self, "_factor_na", None) or 1   # (before the first factor the library refuses and writes nothing)
+        out = np.empty((Na, Na), dtype=np.float64)
+        _check(self._lib.ekf_dense64_get_factor(self._h, _d(out)))
+        return out
+
+    def whiten(self, B, want_Y=True):
+        """Y[r] = L^-1 B[r] by forward substitution against the last factor() and d2[r] = |Y[r]|^2 for the rows of B
+        (nrhs x live, or one vector), up to WHITEN_MAX_RHS at once; with B = state - truth d2 is the NEES of the whole map.
+        Does not read Sigma and does not flush the pending rows.  Returns {Y (None unless want_Y), d2, ms}."""
+        self._open()
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        if B.ndim == 1:
+            B = B[None, :]
+        if B.ndim != 2 or not 1 <= B.shape[0] <= self.WHITEN_MAX_RHS or B.shape[1] != self.live:
+            raise ValueError(f"B must be nrhs x live with 1 <= nrhs <= {self.WHITEN_MAX_RHS}")
+        Y = np.empty_like(B) if want_Y else None
+        d2, ms = np.empty(B.shape[0]), C.c_double()
+        _check(self._lib.ekf_dense64_whiten(self._h, B.shape[0], _d(B), _d(Y) if want_Y else None, _d(d2), C.byref(ms)))
+        return {"Y": Y, "d2": d2, "ms": ms.value}
+
+    def factor_launch_info(self):
+        """{block, threads}: the block side of factor() in states and the workgroup size (test hook)"""
+        self._open()
+        block, th = C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_factor_launch_info(self._h, C.byref(block), C.byref(th)))
+        return {"block": block.value, "threads": th.value}
+
     def _correct_sparse(self, entry, cols, Hc, R, nu):
         cols = self._index_lists(cols, 1)
         s = cols.shape[0]
@@ -1585,6 +1644,23 @@ class DenseEKFSLAM:
     def symmetrize(self):
         """DensePropagator64.symmetrize(): both halves of the live corner equal again, at the caller's cadence"""
         return self.handle.symmetrize()
+
+    def factor(self):
+        """DensePropagator64.factor() of the live corner: definiteness and log det Sigma"""
+        return self.handle.factor()
+
+    def map_nees(self, truth):
+        """(state - truth)^T Sigma^-1 (state - truth) over the live dimension against the last factor(): the NEES of the
+        whole map, live degrees of freedom.  truth: the live states [theta, x, y, m1x, ...]; the heading difference is
+        wrapped by the library's normalize_angles rule."""
+        d = self.handle
+        live = d.live
+        truth = np.ascontiguousarray(truth, dtype=np.float64).reshape(-1)
+        if truth.shape != (live,):
+            raise ValueError("truth must hold the live states")
+        e = d.state_block(0, live) - truth
+        e[0] = normalize_angles(e[:1])[0]
+        return float(d.whiten(e, want_Y=False)["d2"][0])
 
     @property
     def state(self):

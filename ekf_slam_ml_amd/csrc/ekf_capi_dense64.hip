@@ -5,7 +5,8 @@
 // and the block readout (ekf_dense64_init.hip), the exchange of two blocks (ekf_dense64_swap.hip), the landmark front end
 // (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), the
 // scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), the health check of the live corner and its
-// exact symmetrisation (ekf_dense64_health.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
+// exact symmetrisation (ekf_dense64_health.hip), its Cholesky factor with the substitution against it
+// (ekf_dense64_factor.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 // The structured calls run at the handle's LIVE dimension (ekf_dense64_set_live, N by default): every launch of theirs is
@@ -39,7 +40,7 @@ ekf_status ekf_dense64_s::created() {
 
 void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
     for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p, health.p})
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p, health.p, factor.p, factor_ws.p, whiten.p})
         if (p) (void)hipFree(p);
     scan_up.release();
 }
@@ -793,6 +794,109 @@ ekf_status ekf_dense64_symmetrize(ekf_dense64_handle d, long long* n_changed, do
     EKFC(finish_timed(d, elapsed_ms, {{w, d->health.as<char>() + pl.off_words, sizeof(w)}}));
     if (n_changed) *n_changed = (long long)w[ekf::kDense64HealthAsym];
     if (max_asym) std::memcpy(max_asym, &w[ekf::kDense64HealthMaxBits], sizeof(double));
+    return EKF_OK;
+}
+
+// ---- the Cholesky factor of the live corner and the substitution against it (ekf_dense64_factor.hip) ----------------------
+ekf_status ekf_dense64_factor_launch_info(ekf_dense64_handle d, int* block, int* threads) {
+    if (!d || !block || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_factor_launch_info: null argument");
+    *block = ekf::kDense64FactorNB;
+    *threads = ekf::kDense64FactorThreads;
+    return EKF_OK;
+}
+
+// The buffers are reserved and the verdict word zeroed, the pending rows applied, the chain of launches; the records and the
+// diagonal of L come back behind the one synchronisation, and the host folds them in ascending order.
+ekf_status ekf_dense64_factor(ekf_dense64_handle d, ekf_dense64_factor_report* out, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_factor";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null report");
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->live);
+    EKFC(d->factor_ws.reserve(pl.bytes, d->stream, false, fn, "the factor's records"));
+    EKFC(d->factor.reserve(pl.factor_bytes, d->stream, true, fn, "the factor's snapshot"));
+    char* ws = d->factor_ws.as<char>();
+    HIPC(hipMemsetAsync(ws + pl.off_verdict, 0, sizeof(int), d->stream));
+    d->factor_ok = 0;   // the snapshot is being overwritten
+    d->factor_na = pl.Na;
+    std::vector<ekf::Dense64FactorRecord> rec(pl.blocks);
+    std::vector<double> diag(pl.Na);
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_factor(pl, d->S, d->ld, d->factor.as<double>(), ws, d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{rec.data(), ws + pl.off_rec, sizeof(ekf::Dense64FactorRecord) * rec.size()},
+                                      {diag.data(), ws + pl.off_diag, sizeof(double) * diag.size()}}));
+    *out = ekf_dense64_factor_report{};
+    out->ok = 1, out->fail_index = -1, out->min_pivot_i = -1, out->Na = pl.Na;
+    out->min_pivot = HUGE_VAL, out->max_pivot = 0.0;
+    for (const ekf::Dense64FactorRecord& r : rec) {   // ascending: the records behind a failed block were never written
+        if (r.min_i >= 0 && r.min_pivot < out->min_pivot) out->min_pivot = r.min_pivot, out->min_pivot_i = r.min_i;
+        if (r.max_pivot > out->max_pivot) out->max_pivot = r.max_pivot;
+        if (r.fail_index >= 0) {
+            out->ok = 0, out->fail_index = r.fail_index, out->fail_pivot = r.fail_pivot;
+            break;
+        }
+    }
+    if (out->ok) {
+        double sum = 0.0;
+        for (int j = 0; j < pl.Na; j++) sum += std::log(diag[j]);
+        out->logdet = 2.0 * sum;
+    } else {
+        out->logdet = std::numeric_limits<double>::quiet_NaN();
+    }
+    d->factor_ok = out->ok;
+    return EKF_OK;
+}
+
+namespace {
+ekf_status factor_usable(ekf_dense64_s* d, const char* fn, bool same_live) {
+    if (!d->factor_ok)
+        return fail(EKF_ERR_STATE, std::string(fn) + ": there is no complete factor (no ekf_dense64_factor yet, or the last one ended with ok == 0)");
+    if (same_live && d->factor_na != d->live)
+        return fail(EKF_ERR_STATE, std::string(fn) + ": the factor was taken at another live dimension");
+    return EKF_OK;
+}
+}  // namespace
+
+ekf_status ekf_dense64_get_factor(ekf_dense64_handle d, double* L_out) {
+    const char* fn = "ekf_dense64_get_factor";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!L_out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null output");
+    EKFC(factor_usable(d, fn, false));
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->factor_na);
+    const size_t Na = pl.Na;
+    HIPC(hipStreamSynchronize(d->stream));
+    HIPC(hipMemcpy2D(L_out, sizeof(double) * Na, d->factor.p, sizeof(double) * pl.ldf, sizeof(double) * Na, Na, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < Na; i++)   // whatever the snapshot holds above the diagonal
+        for (size_t j = i + 1; j < Na; j++) L_out[i * Na + j] = 0.0;
+    return EKF_OK;
+}
+
+// The working copy is zeroed and B goes up; one launch per block column and the norms; d2 and Y come back.
+ekf_status ekf_dense64_whiten(ekf_dense64_handle d, int nrhs, const double* B, double* Y_out, double* d2_out, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_whiten";
+    constexpr int kMaxRhs = ekf::kDense64WhitenMaxRhs;
+    static_assert(kMaxRhs == EKF_DENSE64_WHITEN_MAX_RHS, "the header's limit");
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!B) return fail(EKF_ERR_INVALID, std::string(fn) + ": null B");
+    if (nrhs < 1 || nrhs > kMaxRhs) return fail(EKF_ERR_INVALID, std::string(fn) + ": 1 <= nrhs <= EKF_DENSE64_WHITEN_MAX_RHS");
+    if (!Y_out && !d2_out) return fail(EKF_ERR_INVALID, std::string(fn) + ": Y_out and d2_out are both NULL");
+    EKFC(factor_usable(d, fn, true));
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->factor_na);
+    const size_t Na = pl.Na, panel = sizeof(double) * kMaxRhs * (size_t)pl.rows, pitch = sizeof(double) * pl.rows;
+    EKFC(d->whiten.reserve(2 * panel + sizeof(double) * kMaxRhs, d->stream, false, fn, "the right-hand sides"));
+    double* rhs = d->whiten.as<double>();
+    double* d2 = rhs + 2 * (size_t)kMaxRhs * pl.rows;
+    HIPC(hipMemsetAsync(rhs, 0, panel, d->stream));
+    HIPC(hipMemcpy2DAsync(rhs, pitch, B, sizeof(double) * Na, sizeof(double) * Na, nrhs, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_whiten(pl, d->factor.as<double>(), rhs, d2, d->stream);
+    EKFC(finish_timed(d, elapsed_ms, {{d2_out, d2, sizeof(double) * nrhs}}));
+    if (Y_out)
+        HIPC(hipMemcpy2D(Y_out, sizeof(double) * Na, rhs + (size_t)kMaxRhs * pl.rows, pitch, sizeof(double) * Na, nrhs,
+                         hipMemcpyDeviceToHost));
     return EKF_OK;
 }
 

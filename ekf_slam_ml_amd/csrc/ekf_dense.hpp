@@ -289,4 +289,39 @@ void launch_dense64_health(const Dense64HealthPlan& p, const double* Sigma, int 
 // One launch, in place: reads the corner once, writes the two entries of every pair i < j < Na that differ in bits.  Only
 // the first kDense64HealthWords words of the workspace are used: [Asym] and [MaxBits].
 void launch_dense64_symmetrize(const Dense64HealthPlan& p, double* Sigma, int ld, void* ws, hipStream_t st);
+
+// ---- the Cholesky factor of the live corner and the forward substitution against it (ekf_dense64_factor.hip; the
+// definitions are include/ekfslam.h's, ekf_dense64_factor_report).  A blocked right-looking factorisation, block side
+// kDense64FactorNB, in a snapshot buffer of the handle's own: `rows` = Na rounded up to the block side, row stride
+// ldf = rows + NB doubles, zero where the corner is not (so no tile of the snapshot is ragged), the lower triangle holds L,
+// the last NB columns hold the NEGATED panel of the block column in flight -- the A operand of the trailing update, which
+// is gemm_tile<double, BT> with C = Qadd = the trailing tile: A22 + (-L21) L21^T.
+constexpr int kDense64FactorNB = 64;
+constexpr int kDense64FactorThreads = 256;
+constexpr int kDense64WhitenMaxRhs = 64;
+// what the diagonal-block kernel leaves per block column; the host folds them in ascending block order
+struct Dense64FactorRecord {
+    double min_pivot, max_pivot;   // over the columns of the block that were factored; +Inf / 0.0 if none
+    double fail_pivot;             // the pivot that ended the factorisation (bits), 0.0 without one
+    int min_i;                     // column of min_pivot (lowest on ties), -1 if none
+    int fail_index;                // the column whose pivot was not (finite and > 0), -1 without one
+};
+// the workspace of a call, byte offsets: the verdict word (0 until a pivot fails) | one record per block column | the
+// diagonal of L [rows]
+struct Dense64FactorPlan {
+    int Na, blocks, rows, ldf;
+    size_t factor_bytes, off_verdict, off_rec, off_diag, bytes;
+};
+Dense64FactorPlan dense64_factor_plan(int Na);
+// 1 + 3 launches per block column (the last one: 1): the copy of the corner's lower triangle (masked element by element:
+// nothing of Sigma at an index >= Na or above the diagonal is read, nothing of it is written), then per block column the
+// diagonal-block factor (one workgroup), the panel solve by substitution (one workgroup per NB rows below) and the trailing
+// update (one workgroup per NB x NB tile of the trailing lower triangle).  Every kernel behind the first reads the verdict
+// word before its first store and does nothing when a pivot has failed.  The verdict word zero before the launch.
+void launch_dense64_factor(const Dense64FactorPlan& p, const double* Sigma, int ld, double* factor, void* ws, hipStream_t st);
+// Y = L^-1 B: rhs [2][kDense64WhitenMaxRhs][p.rows] -- first the working copy, row r = right-hand side r, zero beyond Na and
+// in the rows not in use, then Y in the same shape (every entry written).  One launch per block column (every workgroup
+// solves the diagonal block for all right-hand sides, the first one stores it into Y, the others take it out of their NB
+// rows of the working copy), then d2 [kDense64WhitenMaxRhs] = the squared norms, a fixed fold.
+void launch_dense64_whiten(const Dense64FactorPlan& p, const double* factor, double* rhs, double* d2, hipStream_t st);
 }  // namespace ekf

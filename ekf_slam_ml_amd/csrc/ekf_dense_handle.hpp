@@ -133,11 +133,16 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf joint;      // JointLayout (ekf_dense64_associate_joint, ekf_dense64_joint_operands)
     ekfrt::DeviceBuf pairs;      // Dense64PairsPlan (ekf_dense64_score_landmark_pairs), grows with n_lm
     ekfrt::DeviceBuf health;     // Dense64HealthPlan (ekf_dense64_health, ekf_dense64_symmetrize), grows with live
+    ekfrt::DeviceBuf factor;     // the snapshot of ekf_dense64_factor: L of the live corner, Dense64FactorPlan::factor_bytes
+    ekfrt::DeviceBuf factor_ws;  // Dense64FactorPlan: the verdict word, the per-block records, the diagonal of L
+    ekfrt::DeviceBuf whiten;     // ekf_dense64_whiten: the working copy of B and Y, then d2
     ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads
     std::vector<int> host_stamp; // [N] the duplicate check of the index lists
     int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
+    int factor_na = 0;           // the live dimension the snapshot was taken at, 0 before the first factor
+    int factor_ok = 0;           // the snapshot is a complete factor (the last ekf_dense64_factor ended with ok == 1)
     int carry = 0;               // ekf_dense64_set_carry: propagate_block, init_block, swap_blocks, get_sigma_block do not flush
     // the live dimension (ekf_dense64_set_live): what the structured calls take for N; the plans change with it, not per call
     int live = 0;                          // 1 .. N, N unless set

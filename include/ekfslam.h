@@ -1168,6 +1168,68 @@ ekf_status ekf_dense64_health_launch_info(ekf_dense64_handle h, int* tile, int* 
 ekf_status ekf_dense64_health(ekf_dense64_handle h, ekf_dense64_health_report* out, double* elapsed_ms);
 ekf_status ekf_dense64_symmetrize(ekf_dense64_handle h, long long* n_changed, double* max_asym, double* elapsed_ms);
 
+/* The Cholesky factor of Sigma on the device: is Sigma positive definite (the sufficient test that n_minor above is not),
+ * log det Sigma (the entropy of the map; its change across a correction is the information gain), and through the forward
+ * substitution of ekf_dense64_whiten the Mahalanobis distance e^T Sigma^-1 e of the WHOLE map (its NEES against ground
+ * truth, Na degrees of freedom).  Opt-in: no other entry point calls these or launches anything different because they
+ * exist.
+ * ekf_dense64_factor is a structured call on the live corner Sigma[0:Na, 0:Na], Na = live.  THE LOWER TRIANGLE ONLY IS READ:
+ * Sigma[i][j] with j <= i < Na, along rows (masked element by element); nothing above the diagonal and nothing at an index
+ * >= Na.  The matrix factored is the symmetric matrix with that lower triangle; a caller who wants both halves to count
+ * calls ekf_dense64_symmetrize first.  Read-only on Sigma and on the state; it FLUSHES THE PENDING ROWS FIRST, after its
+ * argument checks, inside the timed region, as ekf_dense64_health does.  A NULL handle (checked first) or a NULL report
+ * returns EKF_ERR_INVALID and changes nothing, the pending rows included.
+ * DEFINITION, IEEE binary64, columns j ascending:
+ *   d_j     = Sigma[j][j] - sum_{k<j} L[j][k]^2             the pivot
+ *   L[j][j] = sqrt(d_j)
+ *   L[i][j] = (Sigma[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j]        i > j
+ * The square root and the division are the correctly rounded ones, and every quotient is a division by L[j][j] in a forward
+ * substitution: there is no inverse of a diagonal block and no multiplication by a reciprocal, so the componentwise bound
+ * |Sigma - L L^T|_ij <= gamma_{Na+1} (|L| |L|^T)_ij, gamma_n = n u / (1 - n u), u = 2^-53, holds.  The association of each
+ * sum is the implementation's (block columns of 64 states, chains of fused multiply-adds on the matrix cores inside a
+ * block update) and depends on (Na, block side) alone; no atomics: a run repeats bit for bit.
+ * THE STOP RULE: the first column j whose d_j is not (finite and > 0) ends the factorisation: ok = 0, fail_index = j,
+ * fail_pivot = d_j (its bits: +0.0 and -0.0 fail, a NaN keeps its payload), logdet = NaN, min_pivot / max_pivot cover the
+ * columns before j.  The call still returns EKF_OK: an indefinite Sigma is a finding, not an error.  The verdict is a pure
+ * function of the data -- the lowest failing column -- and a device word that every later launch reads before its first
+ * store, so nothing is computed from NaNs.
+ * logdet is summed ON THE HOST from the diagonal of L, which comes down with the report: 2.0 * (((log l_0) + log l_1) + ...),
+ * ascending, plain binary64 with the C library's log.
+ * THE FACTOR IS A SNAPSHOT in a buffer of its own, allocated by the first call and growing with Na: 8 (Na + 63)(Na + 127)
+ * bytes at most (Na rounded up to the block side, one block column of workspace beside it), 812.8 MB at Na = 10003.  A
+ * failure to allocate returns EKF_ERR_NOMEM and leaves the handle and any earlier snapshot as they were.  Later calls that
+ * change Sigma (or the live dimension) neither touch nor invalidate the snapshot: ekf_dense64_get_factor and
+ * ekf_dense64_whiten use it as taken.  Before the first factor, and after a factor that ended with ok == 0, both return
+ * EKF_ERR_STATE.
+ * ekf_dense64_get_factor: L as Na x Na row-major, Na = the dimension the factor was taken at; the strict upper triangle is
+ * exactly +0.0.
+ * ekf_dense64_whiten: Y[r] = L^-1 B[r] by forward substitution (ascending, divisions by L[j][j]) for 1 <= nrhs <=
+ * EKF_DENSE64_WHITEN_MAX_RHS right-hand sides at once, d2[r] = sum_i Y[r][i]^2 (a fixed fold).  A right-hand side gives the
+ * same bits alone and at any position of a batch.  With B[r] = state - truth (the caller wraps the heading), d2 is the NEES
+ * of the whole map.  EKF_ERR_INVALID before the device is looked at: a NULL handle or B, nrhs out of range, Y_out and d2_out
+ * both NULL.  EKF_ERR_STATE: no complete factor, or the snapshot's Na differs from the live dimension.  Read-only on
+ * everything but its own operand buffers; it does not read Sigma, so it does NOT flush the pending rows.
+ * ekf_dense64_factor_launch_info reports the block side in states (a divisor of 128, >= 16) and the workgroup size.
+ * Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the launches, for the factor the flush
+ * included. */
+typedef struct ekf_dense64_factor_report {
+    int    ok;            /* 1: every pivot was finite and > 0, the factor is complete; 0: stopped at fail_index */
+    int    fail_index;    /* -1, or the first column j whose pivot was not (finite and > 0) */
+    int    min_pivot_i;   /* index of the smallest pivot among the columns factored (lowest index on ties); -1 if none */
+    int    Na;            /* the live dimension the factor was taken at */
+    double fail_pivot;    /* that pivot's value (bits), 0.0 when ok */
+    double min_pivot;     /* smallest / largest d_j = L[j][j]^2 as computed BEFORE the square root, over the */
+    double max_pivot;     /*   columns factored; +Inf / 0.0 if none */
+    double logdet;        /* ok: 2 * sum_j log(L[j][j]); else NaN */
+} ekf_dense64_factor_report;
+ekf_status ekf_dense64_factor_launch_info(ekf_dense64_handle h, int* block, int* threads);
+ekf_status ekf_dense64_factor(ekf_dense64_handle h, ekf_dense64_factor_report* out, double* elapsed_ms);
+ekf_status ekf_dense64_get_factor(ekf_dense64_handle h, double* L_out /* Na x Na row-major */);
+#define EKF_DENSE64_WHITEN_MAX_RHS 64
+ekf_status ekf_dense64_whiten(ekf_dense64_handle h, int nrhs, const double* B /* [nrhs][Na] */,
+                              double* Y_out /* [nrhs][Na], nullable */, double* d2_out /* [nrhs], nullable */,
+                              double* elapsed_ms);
+
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
  * ekf_dense64_get_sigma_block: out[a][c] = Sigma[rows[a]][cols[c]], nr x nc row-major; one gather launch into a buffer
