@@ -48,6 +48,7 @@ SYMBOLS = [
     "ekf_dense64_set_state", "ekf_dense64_get_state", "ekf_dense64_correct", "ekf_dense64_score", "ekf_dense64_propagate_block",
     "ekf_dense64_correct_sparse", "ekf_dense64_score_sparse",
     "ekf_dense64_correct_sparse_deferred", "ekf_dense64_flush", "ekf_dense64_pending",
+    "ekf_dense64_correct_sparse_joseph", "ekf_dense64_joseph_launch_info",
     "ekf_dense64_score_landmarks", "ekf_dense64_associate_landmarks",
     "ekf_dense64_fit_scan", "ekf_dense64_associate_scan",
     "ekf_dense64_score_readings", "ekf_dense64_joint_operands", "ekf_dense64_associate_joint",
@@ -232,6 +233,9 @@ def load():
         "ekf_dense64_correct_sparse": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
         "ekf_dense64_score_sparse": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, _dp, _dp, _dp, _ip, _dp],
         "ekf_dense64_correct_sparse_deferred": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp],
+        "ekf_dense64_correct_sparse_joseph": [h, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_longlong),
+                                              _dp],
+        "ekf_dense64_joseph_launch_info": [h, _ip, _ip, _ip],
         "ekf_dense64_flush": [h, _dp],
         "ekf_dense64_pending": [h, _ip],
         "ekf_dense64_score_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _ip, _ip,
@@ -816,6 +820,8 @@ class DensePropagator64(_DensePropagatorBase):
     READ_MAX = 65536   # EKF_DENSE64_READ_MAX
     PENDING_MAX_ROWS = 64   # EKF_DENSE64_PENDING_MAX_ROWS
     LM_DEFERRED, LM_GROW_LIVE = 1, 2   # EKF_DENSE64_LM_DEFERRED, EKF_DENSE64_LM_GROW_LIVE
+    LM_JOSEPH = 8   # EKF_DENSE64_LM_JOSEPH (4 stays an unknown bit)
+    JOSEPH_MAX_M = 32   # EKF_DENSE64_JOSEPH_MAX_M
     SCAN_MAX_BEAMS, SCAN_MAX_CIRCLES = 1024, 128   # EKF_DENSE64_SCAN_MAX_BEAMS, EKF_DENSE64_SCAN_MAX_CIRCLES
     JOINT_MAX_READINGS, JOINT_MAX_PAIRS = 128, 30   # EKF_DENSE64_JOINT_MAX_READINGS, EKF_DENSE64_JOINT_MAX_PAIRS
 
@@ -947,6 +953,39 @@ class DensePropagator64(_DensePropagatorBase):
         first.  A singular or non-finite S raises EkfError (EKF_ERR_STATE) and leaves state, Sigma and the pending rows."""
         return self._correct_sparse("ekf_dense64_correct_sparse_deferred", cols, Hc, R, nu)
 
+    def correct_sparse_joseph(self, cols, Hc, R, nu=None, gain_w=None):
+        """correct_sparse() in the Joseph form Sigma <- (I - K H) Sigma (I - K H)^T + K R K^T, run as Sigma - K T - D K^T
+        with D = U - K S: positive semi-definite up to rounding whatever the prior against R, and valid for any gain.
+        gain_w: None, or N weights in [0, 1] giving K = diag(w) U S^-1 (the partial update); a state with w = 0 is a
+        consider state -- its estimate and its own block of Sigma keep their bits, its cross-covariances are updated, and
+        tiles whose rows and columns are all considered are not touched.  m <= JOSEPH_MAX_M; eager only (flushes the
+        pending rows first).  Returns (nis or None, tiles_skipped, elapsed_ms); a singular or non-finite S raises EkfError
+        (EKF_ERR_STATE) and leaves state and Sigma as they were."""
+        cols, Hc, R, nu, m, s = self._sparse_operands(cols, Hc, R, nu, self.JOSEPH_MAX_M)
+        pw = None
+        if gain_w is not None:
+            gain_w = np.ascontiguousarray(gain_w, dtype=np.float64)
+            if gain_w.shape != (self.N,):
+                raise ValueError("gain_w must have length N")
+            if not (np.isfinite(gain_w).all() and (gain_w >= 0.0).all() and (gain_w <= 1.0).all()):
+                raise ValueError("every gain weight must be finite and in [0, 1]")
+            pw = gain_w.ctypes.data_as(_dp)
+        nis = C.c_double() if nu is not None else None
+        skipped, ms = C.c_longlong(), C.c_double()
+        _check(self._lib.ekf_dense64_correct_sparse_joseph(
+            self._h, m, s, cols.ctypes.data_as(_ip), Hc.ctypes.data_as(_dp), R.ctypes.data_as(_dp),
+            nu.ctypes.data_as(_dp) if nu is not None else None, pw, C.byref(nis) if nu is not None else None,
+            C.byref(skipped), C.byref(ms)))
+        return (nis.value if nis is not None else None), skipped.value, ms.value
+
+    def joseph_launch_info(self):
+        """{tile_rows, tile_cols, threads}: the tile of correct_sparse_joseph()'s pass over Sigma in states and its
+        workgroup size (test hook)"""
+        self._open()
+        tr, tc, th = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_joseph_launch_info(self._h, C.byref(tr), C.byref(tc), C.byref(th)))
+        return {"tile_rows": tr.value, "tile_cols": tc.value, "threads": th.value}
+
     def flush(self):
         """apply the pending rows to Sigma (one rank-`pending` update); a no-op with nothing pending.  Returns elapsed_ms"""
         ms = C.c_double()
@@ -1032,7 +1071,7 @@ class DensePropagator64(_DensePropagatorBase):
         """Fuse landmarks a and b (either order) of the `known` ones and remove the higher: correct_sparse() -- with
         LM_DEFERRED in flags correct_sparse_deferred() -- on landmark_pairs()' operands for (min, max), built on the
         device; then swap_blocks(max, last) unless max is the last, init_block(last, W = sigma0 I) and known - 1; with
-        LM_GROW_LIVE also live = 3 + 2 known.  Bit for bit that sequence spelled.  Returns (known, moved_from: the old index
+        LM_GROW_LIVE also live = 3 + 2 known, with LM_JOSEPH correct_sparse_joseph().  Bit for bit that sequence spelled.  Returns (known, moved_from: the old index
         of the landmark that now sits in slot max, or -1; d2: the correction's nis; elapsed_ms).  A singular S raises
         EkfError (EKF_ERR_STATE) and leaves everything as it was."""
         a, b, known, flags = int(a), int(b), int(known), int(flags)
@@ -1041,8 +1080,9 @@ class DensePropagator64(_DensePropagatorBase):
         if a == b or not (0 <= a < known and 0 <= b < known):
             raise ValueError("a and b must be two different landmarks in [0, known)")
         r_merge = self._r_merge(r_merge)
-        if flags & ~(self.LM_DEFERRED | self.LM_GROW_LIVE):
-            raise ValueError("flags: LM_DEFERRED | LM_GROW_LIVE")
+        if flags & ~(self.LM_DEFERRED | self.LM_GROW_LIVE | self.LM_JOSEPH) or \
+                (flags & self.LM_JOSEPH and flags & self.LM_DEFERRED):
+            raise ValueError("flags: LM_DEFERRED | LM_GROW_LIVE | LM_JOSEPH, the last not with the first")
         k, moved, d2, ms = C.c_int(known), C.c_int(-1), C.c_double(), C.c_double()
         _check(self._lib.ekf_dense64_merge_landmarks(self._h, C.byref(params) if params is not None else None, a, b, r_merge,
                                                      C.byref(k), flags, C.byref(moved), C.byref(d2), C.byref(ms)))
@@ -1130,21 +1170,27 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_factor_launch_info(self._h, C.byref(block), C.byref(th)))
         return {"block": block.value, "threads": th.value}
 
-    def _correct_sparse(self, entry, cols, Hc, R, nu):
+    def _sparse_operands(self, cols, Hc, R, nu, max_m):
+        """the shape and range checks of a sparse correction -> (cols int32, Hc, R, nu or None, m, s), contiguous"""
         cols = self._index_lists(cols, 1)
         s = cols.shape[0]
         Hc = np.ascontiguousarray(Hc, dtype=np.float64)
-        if Hc.ndim != 2 or Hc.shape[1] != s or not 1 <= Hc.shape[0] <= min(self.N, self.MAX_M):
-            raise ValueError(f"Hc must be m x s with 1 <= m <= min(N, {self.MAX_M})")
+        if Hc.ndim != 2 or Hc.shape[1] != s or not 1 <= Hc.shape[0] <= min(self.N, max_m):
+            raise ValueError(f"Hc must be m x s with 1 <= m <= min(N, {max_m})")
         m = Hc.shape[0]
         R = np.ascontiguousarray(R, dtype=np.float64)
         if R.shape != (m, m):
             raise ValueError("R must be m x m")
-        nis, pnu, pnis = None, None, None
         if nu is not None:
             nu = np.ascontiguousarray(nu, dtype=np.float64)
             if nu.shape != (m,):
                 raise ValueError("nu must have length m")
+        return cols, Hc, R, nu, m, s
+
+    def _correct_sparse(self, entry, cols, Hc, R, nu):
+        cols, Hc, R, nu, m, s = self._sparse_operands(cols, Hc, R, nu, self.MAX_M)
+        nis, pnu, pnis = None, None, None
+        if nu is not None:
             nis = C.c_double()
             pnu, pnis = nu.ctypes.data_as(_dp), C.byref(nis)
         ms = C.c_double()
@@ -1214,11 +1260,18 @@ class DensePropagator64(_DensePropagatorBase):
             return nis, S, flags, ms.value, (cols, Hc, nu)
         return nis, S, flags, ms.value
 
-    def associate_landmarks(self, readings, known, n_max, deferred=False, grow_live=False, params=None):
+    def _lm_flags(self, deferred, grow_live=False, joseph=False):
+        if deferred and joseph:
+            raise ValueError("joseph is an eager form: not with deferred")
+        return (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0) | \
+               (self.LM_JOSEPH if joseph else 0)
+
+    def associate_landmarks(self, readings, known, n_max, deferred=False, grow_live=False, params=None, joseph=False):
         """data_association (ekf_slam.cpp:278-402) for the readings (J, 2) in order, on the handle's own state: per reading
         the known landmarks are scored, the reference's rule is applied on the device, a new landmark is initialised
         (init_block's path, s = 0, W = sigma0 I), the winner is corrected (correct_sparse, or correct_sparse_deferred with
-        deferred=True) and the heading wrapped.  grow_live: a new landmark first grows the live dimension when it has to.
+        deferred=True, correct_sparse_joseph with joseph=True) and the heading wrapped.  grow_live: a new landmark first
+        grows the live dimension when it has to.
         Returns (known, assoc (J,) int32: landmark corrected / -1 dropped, best (J,), elapsed_ms).  A refused call or a
         singular S raises EkfError; the exception carries .known, .assoc and .best as they stood."""
         z = np.ascontiguousarray(readings, dtype=np.float64)
@@ -1227,7 +1280,7 @@ class DensePropagator64(_DensePropagatorBase):
         J = z.shape[0]
         k = C.c_int(int(known))
         assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
-        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        flags = self._lm_flags(deferred, grow_live, joseph)
         ms = C.c_double()
         try:
             _check(self._lib.ekf_dense64_associate_landmarks(
@@ -1391,12 +1444,14 @@ class DensePropagator64(_DensePropagatorBase):
             Fr.ctypes.data_as(_dp) if want_terms else None, upd.ctypes.data_as(_dp) if want_terms else None, C.byref(ms)))
         return (ms.value, Fr, upd) if want_terms else ms.value
 
-    def measure_landmarks(self, sensor_xy, visible, initialised, deferred=False, want_terms=False, params=None):
+    def measure_landmarks(self, sensor_xy, visible, initialised, deferred=False, want_terms=False, params=None,
+                          joseph=False):
         """measurement() (ekf_slam.cpp:108-197) on the handle's own state: sensor_xy (n_lm, 2) holds a reading per
         landmark, visible (n_lm,) says which are corrected, initialised is the reference's landmark_init_flag.  The pose
         is captured once per call on the device and every correction of the call uses it; with initialised false ALL
         n_lm landmarks are first placed from their readings (Sigma untouched).  Then per visible landmark, ascending:
-        correct_sparse (correct_sparse_deferred with deferred=True) on device-built operands and the heading wrap.
+        correct_sparse (correct_sparse_deferred with deferred=True, correct_sparse_joseph with joseph=True) on
+        device-built operands and the heading wrap.
         Returns (initialised, corrected, elapsed_ms), and with want_terms also (Hc (V, 2, 5), nu (V, 2) wrapped).  A
         singular S raises EkfError (EKF_ERR_STATE); the exception carries .initialised and .corrected as they stood."""
         z = np.ascontiguousarray(sensor_xy, dtype=np.float64)
@@ -1412,10 +1467,11 @@ class DensePropagator64(_DensePropagatorBase):
         Hc = np.empty((V, 2, 5), dtype=np.float64) if want_terms else None
         nu = np.empty((V, 2), dtype=np.float64) if want_terms else None
         flag, done, ms = C.c_int(1 if initialised else 0), C.c_int(0), C.c_double()
+        flags = self._lm_flags(deferred, joseph=joseph)
         try:
             _check(self._lib.ekf_dense64_measure_landmarks(
                 self._h, C.byref(params) if params is not None else None, n_lm, z.ctypes.data_as(_dp),
-                vis.ctypes.data_as(_bp), C.byref(flag), self.LM_DEFERRED if deferred else 0, C.byref(done),
+                vis.ctypes.data_as(_bp), C.byref(flag), flags, C.byref(done),
                 Hc.ctypes.data_as(_dp) if want_terms else None, nu.ctypes.data_as(_dp) if want_terms else None,
                 C.byref(ms)))
         except EkfError as e:
@@ -1548,16 +1604,20 @@ class DenseEKFSLAM:
     into the library, the state never leaving the device.  n landmarks in a handle with room for `capacity` (default n).
     deferred: the corrections go through the pending rows; carry: prediction() and a new landmark leave them pending;
     grow_live: the live dimension starts at the pose and data_association() grows it as the map is discovered
-    (measurement() places all n landmarks, so it raises it to 3 + 2 n).  `handle` is the DensePropagator64 underneath."""
+    (measurement() places all n landmarks, so it raises it to 3 + 2 n); joseph: the corrections of measurement(),
+    data_association() and merge() run in the Joseph form (eager only).  `handle` is the DensePropagator64 underneath."""
 
     PRIOR = 100.0   # the reference's landmark prior (ekf_slam.cpp:32)
 
-    def __init__(self, n, capacity=None, deferred=False, carry=False, grow_live=False, params=None, device=-1):
+    def __init__(self, n, capacity=None, deferred=False, carry=False, grow_live=False, params=None, device=-1,
+                 joseph=False):
         self.n = int(n)
         cap = self.n if capacity is None else int(capacity)
         if self.n < 1 or cap < self.n:
             raise ValueError("n >= 1 and capacity >= n")
-        self.deferred, self.grow_live, self.params = bool(deferred), bool(grow_live), params
+        if deferred and joseph:
+            raise ValueError("joseph is an eager form: not with deferred")
+        self.deferred, self.grow_live, self.params, self.joseph = bool(deferred), bool(grow_live), params, bool(joseph)
         self.handle = d = DensePropagator64(3 + 2 * cap, device)
         # the constructor's prior (:27-46): Sigma zero (as created) except 100 I on the landmarks; the state zero
         for first in range(3, d.N, d.MAX_R):
@@ -1581,7 +1641,7 @@ class DenseEKFSLAM:
             d.live = 3 + 2 * self.n
         try:
             self._init_flag, done, _ = d.measure_landmarks(sensor_xy, visible, self._init_flag, self.deferred,
-                                                           params=self.params)
+                                                           params=self.params, joseph=self.joseph)
         except EkfError as e:
             self._init_flag = e.initialised
             raise
@@ -1592,7 +1652,7 @@ class DenseEKFSLAM:
         landmark each reading corrected, -1 for a dropped one"""
         try:
             self._known, assoc, _, _ = self.handle.associate_landmarks(meas_xy, self._known, self.n, self.deferred,
-                                                                       self.grow_live, self.params)
+                                                                       self.grow_live, self.params, self.joseph)
         except EkfError as e:
             self._known = e.known
             raise
@@ -1633,7 +1693,7 @@ class DenseEKFSLAM:
     def merge(self, a, b, r_merge):
         """fuse the known landmarks a and b and remove the higher (merge_landmarks on the object's paths); the last known
         landmark moves into its slot.  Returns (moved_from, d2)"""
-        flags = (self.handle.LM_DEFERRED if self.deferred else 0) | (self.handle.LM_GROW_LIVE if self.grow_live else 0)
+        flags = self.handle._lm_flags(self.deferred, self.grow_live, self.joseph)
         self._known, moved, d2, _ = self.handle.merge_landmarks(a, b, r_merge, self._known, flags, self.params)
         return moved, d2
 

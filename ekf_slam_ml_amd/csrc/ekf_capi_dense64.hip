@@ -6,7 +6,8 @@
 // (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), the
 // scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), the health check of the live corner and its
 // exact symmetrisation (ekf_dense64_health.hip), its Cholesky factor with the substitution against it
-// (ekf_dense64_factor.hip), and the deferred form of the sparse update: pending rows of K and T that the sparse calls
+// (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), and
+// the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
 // The structured calls run at the handle's LIVE dimension (ekf_dense64_set_live, N by default): every launch of theirs is
@@ -32,6 +33,7 @@ ekf_status ekf_dense64_s::created() {
     HIPC(ekf::dense64_block_prepare());
     HIPC(hipMalloc((void**)&blk_in, L::blk_in_layout().bytes));
     HIPC(ekf::dense64_sparse_prepare());
+    HIPC(ekf::dense64_joseph_prepare());
     HIPC(ekf::dense64_init_prepare());
     HIPC(hipMalloc((void**)&ini_in, L::ini_in_layout().bytes));
     HIPC(hipMalloc((void**)&rd_buf, L::rd_buf_layout().bytes));
@@ -85,14 +87,21 @@ ekf_status pend_reserve(ekf_dense64_s* d, const char* fn) {
     return d->pend.reserve(L::pend_layout(d->ld).bytes, d->stream, true, fn, "the pending panels");
 }
 
-// the launches of one correction on operands that sit in the operand buffer; behind e0
-void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool have_nu) {
+// the launches of one correction on operands that sit in the operand buffer; behind e0.  joseph_w (eager only): the Joseph
+// form, with the weights that sit in the workspace (dense64_joseph_ws) or all 1
+enum class Joseph { kNo, kUnweighted, kWeighted };
+void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool have_nu, Joseph joseph = Joseph::kNo) {
     const CorrSparseView in = view(d->corr_in, L::corr_sparse_layout(d->ld));
     const CorrOutView out = view(d->corr_out, L::corr_out_layout());
     const double* dnu = have_nu ? in.nu : nullptr;
     if (!deferred || d->pend_rows + m > kMaxP) d->flush_pending();   // deferred: only when there is no room for m more rows
     const PendView p = d->panels();
-    if (deferred)
+    if (joseph != Joseph::kNo)
+        ekf::launch_dense64_correct_sparse_joseph(
+            d->pl_live, d->S, d->x, d->workspace(), in.cols, in.Hc, in.R, dnu,
+            joseph == Joseph::kWeighted ? ekf::dense64_joseph_ws(d->pl_live, d->workspace()).w : nullptr, m, s, out.nis,
+            out.verdict, d->stream);
+    else if (deferred)
         ekf::launch_dense64_correct_deferred(d->pl_live, d->S, d->x, d->workspace(), p.K, p.T, d->pend_rows, in.cols, in.Hc,
                                              in.R, dnu, m, s, out.nis, out.verdict, d->stream);
     else
@@ -133,6 +142,54 @@ ekf_status dense64_correct_sparse(ekf_dense64_s* d, bool deferred, int m, int s,
     HIPC(hipEventRecord(d->e0, d->stream));
     correct_sparse_launch(d, deferred, m, s, nu != nullptr);
     return correct_sparse_finish(d, fn.c_str(), deferred, m, nis_out, elapsed_ms);
+}
+
+// The Joseph form: ekf_dense64_correct_sparse's checks with the cap on m at 32, then the weights' host scan (which also
+// counts the tiles the pass will skip); the weights go up with the operands, the pending rows are applied inside the timed
+// region, and the verdict and nis come back as they do there.
+constexpr int kJosephMaxM = ekf::kDense64JosephMaxM;
+static_assert(kJosephMaxM == EKF_DENSE64_JOSEPH_MAX_M, "ekfslam.h and ekf_dense.hpp");
+
+ekf_status dense64_correct_sparse_joseph(ekf_dense64_s* d, int m, int s, const int* cols, const double* Hc, const double* R,
+                                         const double* nu, const double* gain_w, double* nis_out, long long* tiles_skipped,
+                                         double* elapsed_ms) {
+    const std::string fn = "ekf_dense64_correct_sparse_joseph";
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!cols || !Hc || !R || m < 1 || m > kJosephMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live || (nis_out && !nu))
+        return fail(EKF_ERR_INVALID, fn + ": bad argument (1 <= m <= 32)");
+    if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
+        return fail(EKF_ERR_INVALID, fn + ": cols must hold distinct indices in [0, N), below the live dimension");
+    const int Na = d->live, tr = ekf::kDense64JosephTileRows, tc = ekf::kDense64JosephTileCols;
+    long long skipped = 0;
+    if (gain_w) {
+        for (int i = 0; i < Na; i++)
+            if (!(gain_w[i] >= 0.0 && gain_w[i] <= 1.0))   // (a NaN fails both comparisons)
+                return fail(EKF_ERR_INVALID, fn + ": every gain weight below the live dimension must be finite and in [0, 1]");
+        auto idle = [&](int side) {   // groups of `side` states without a w != 0
+            long long n = 0;
+            for (int i0 = 0; i0 < Na; i0 += side) {
+                bool any = false;
+                for (int i = i0; i < std::min(Na, i0 + side) && !any; i++) any = gain_w[i] != 0.0;
+                n += any ? 0 : 1;
+            }
+            return n;
+        };
+        skipped = idle(tr) * idle(tc);
+    }
+    HIPC(hipSetDevice(d->device));
+    const CorrSparseView in = view(d->corr_in, L::corr_sparse_layout(d->ld));
+    HIPC(hipMemcpyAsync(in.Hc, Hc, sizeof(double) * m * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(in.cols, cols, sizeof(int) * s, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(in.R, R, sizeof(double) * m * m, hipMemcpyHostToDevice, d->stream));
+    if (nu) HIPC(hipMemcpyAsync(in.nu, nu, sizeof(double) * m, hipMemcpyHostToDevice, d->stream));
+    if (gain_w)
+        HIPC(hipMemcpyAsync(ekf::dense64_joseph_ws(d->pl_live, d->workspace()).w, gain_w, sizeof(double) * Na,
+                            hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    correct_sparse_launch(d, false, m, s, nu != nullptr, gain_w ? Joseph::kWeighted : Joseph::kUnweighted);
+    EKFC(correct_sparse_finish(d, fn.c_str(), false, m, nis_out, elapsed_ms));
+    if (tiles_skipped) *tiles_skipped = skipped;
+    return EKF_OK;
 }
 
 // Sparse scoring of J candidates: the operands go up into one buffer (SpsLayout), one launch, the outputs come straight back
@@ -220,15 +277,24 @@ ekf_status scan_fit(ekf_dense64_s* d, const char* fn, const double* ranges, int 
 
 // ---- data_association (:278-402), shared by ekf_dense64_associate_landmarks and ekf_dense64_associate_scan -----------------
 // the argument checks both calls make, in their documented order, behind their own
-ekf_status associate_checks(ekf_dense64_s* d, const std::string& fn, int n_max, const int* known, unsigned flags) {
+// the flags of the landmark front end: `allowed` is what the call knows; the Joseph form is eager only
+ekf_status lm_flags_ok(const std::string& fn, unsigned flags, unsigned allowed) {
+    if (flags & ~allowed) return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    if ((flags & EKF_DENSE64_LM_JOSEPH) && (flags & EKF_DENSE64_LM_DEFERRED))
+        return fail(EKF_ERR_INVALID, fn + ": EKF_DENSE64_LM_JOSEPH is an eager form and does not combine with "
+                                          "EKF_DENSE64_LM_DEFERRED");
+    return EKF_OK;
+}
+Joseph lm_joseph(unsigned flags) { return (flags & EKF_DENSE64_LM_JOSEPH) ? Joseph::kUnweighted : Joseph::kNo; }
+
+ekf_status associate_checks(ekf_dense64_s* d, const std::string& fn, int n_max, const int* known, unsigned flags,
+                            unsigned allowed = EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE) {
     if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
         return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
     if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
     if (3 + 2 * *known > d->live)
         return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
-    if (flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
-        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
-    return EKF_OK;
+    return lm_flags_ok(fn, flags, allowed);
 }
 
 // what the loop below needs in memory
@@ -293,7 +359,7 @@ ekf_status associate_readings(ekf_dense64_s* d, const char* fnc, const ekf::Para
         // the winner's operands from the current state, that is after an initialisation; the innovation wrapped (:183)
         ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, rec.win, 1, 1, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu,
                                      d->stream);
-        correct_sparse_launch(d, deferred, 2, 5, true);
+        correct_sparse_launch(d, deferred, 2, 5, true, lm_joseph(flags));
         ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
         if (assoc_out) assoc_out[j] = -1;
         // (a refused correction's launches ran and were timed)
@@ -556,6 +622,20 @@ ekf_status ekf_dense64_correct_sparse(ekf_dense64_handle d, int m, int s, const 
 ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
                                                const double* R, const double* nu, double* nis_out, double* elapsed_ms) {
     return dense64_correct_sparse(d, true, m, s, cols, Hc, R, nu, nis_out, elapsed_ms);
+}
+
+ekf_status ekf_dense64_correct_sparse_joseph(ekf_dense64_handle d, int m, int s, const int* cols, const double* Hc,
+                                             const double* R, const double* nu, const double* gain_w, double* nis_out,
+                                             long long* tiles_skipped, double* elapsed_ms) {
+    return dense64_correct_sparse_joseph(d, m, s, cols, Hc, R, nu, gain_w, nis_out, tiles_skipped, elapsed_ms);
+}
+ekf_status ekf_dense64_joseph_launch_info(ekf_dense64_handle d, int* tile_rows, int* tile_cols, int* threads) {
+    if (!d || !tile_rows || !tile_cols || !threads)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_joseph_launch_info: null argument");
+    *tile_rows = ekf::kDense64JosephTileRows;
+    *tile_cols = ekf::kDense64JosephTileCols;
+    *threads = ekf::kDense64JosephThreads;
+    return EKF_OK;
 }
 
 ekf_status ekf_dense64_flush(ekf_dense64_handle d, double* elapsed_ms) {
@@ -949,8 +1029,7 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     if (a == b || a < 0 || b < 0 || a >= *known || b >= *known)
         return fail(EKF_ERR_INVALID, fn + ": a and b must be two different landmarks in [0, *known)");
     if (!(r_merge >= 0.0) || !std::isfinite(r_merge)) return fail(EKF_ERR_INVALID, fn + ": r_merge must be finite and >= 0");
-    if ((unsigned)flags & ~(EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE))
-        return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    EKFC(lm_flags_ok(fn, (unsigned)flags, EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE | EKF_DENSE64_LM_JOSEPH));
     const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
     const ekf::Params p = landmark_params(params);
     const int lo = std::min(a, b), hi = std::max(a, b), last = *known - 1;
@@ -963,7 +1042,7 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
     HIPC(hipEventRecord(d->e0, d->stream));
     ekf::launch_dense64_pair_terms(d->x, lo, hi, r_merge, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
-    correct_sparse_launch(d, deferred, 2, 4, true);
+    correct_sparse_launch(d, deferred, 2, 4, true, lm_joseph((unsigned)flags));
     EKFC(leg(correct_sparse_finish(d, fnc, deferred, 2, d2_out, pms)));   // singular: nothing was written, *known stands
     // the removal of hi ("Removing a landmark")
     const double W[4] = {p.sigma0_landmark, 0.0, 0.0, p.sigma0_landmark};
@@ -1013,7 +1092,8 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
     if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (J < 1) return fail(EKF_ERR_INVALID, fn + ": J must be at least 1");
-    EKFC(associate_checks(d, fn, n_max, known, flags));
+    EKFC(associate_checks(d, fn, n_max, known, flags,
+                          EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE | EKF_DENSE64_LM_JOSEPH));
     const ekf::Params p = landmark_params(params);
     if (elapsed_ms) *elapsed_ms = 0.0;
     for (int j = 0; j < J; j++) {
@@ -1236,7 +1316,7 @@ ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle d, const ekf_params*
     if (!sensor_xy || !visible || !initialised) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (n_lm < 1 || 3 + 2 * (long long)n_lm > d->live)
         return fail(EKF_ERR_INVALID, fn + ": the n_lm >= 1 landmarks must lie inside the live dimension");
-    if (flags & ~EKF_DENSE64_LM_DEFERRED) return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
+    EKFC(lm_flags_ok(fn, flags, EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_JOSEPH));
     const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0, init = *initialised == 0;
     const ekf::Params p = landmark_params(params);
     if (elapsed_ms) *elapsed_ms = 0.0;
@@ -1264,7 +1344,7 @@ ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle d, const ekf_params*
         // the pose of the snapshot, the landmark from the current state (get_tube_x(i)); the innovation wrapped (:183)
         ekf::launch_dense64_lm_terms(d->x, mv.pose, sensor_xy[2 * i], sensor_xy[2 * i + 1], i, 1, 1, p.r_meas, cin.cols,
                                      cin.Hc, cin.R, cin.nu, d->stream);
-        correct_sparse_launch(d, deferred, 2, 5, true);
+        correct_sparse_launch(d, deferred, 2, 5, true, lm_joseph(flags));
         ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187
         // (a refused correction's launches ran and were timed)
         const ekf_status st = leg(correct_sparse_finish(

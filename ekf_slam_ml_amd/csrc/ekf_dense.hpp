@@ -104,6 +104,11 @@ void launch_dense64_correct_tail(const Dense64CorrectPlan& pl, double* Sigma, do
 void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
                                    const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
                                    double* nis, int* verdict, hipStream_t st);
+// The first two of those launches alone (the eager gather, the scoring kernel with J = 1), with the summed S [m][m] written
+// to S_out as well (nullable): what a caller with a gain and an update of its own needs (ekf_dense64_joseph.hip).
+void launch_dense64_sparse_panels(const Dense64CorrectPlan& pl, const double* Sigma, double* ws, const int* cols,
+                                  const double* Hc, const double* R, const double* nu, int m, int s, double* nis,
+                                  double* S_out, int* verdict, hipStream_t st);
 // Launch 5 of launch_dense64_correct (k_dc_gain) on U^T and S^-1 in ws, K^T written to Kt [m][ld] instead of ws.
 void launch_dense64_gain(const Dense64CorrectPlan& pl, const double* ws, double* Kt, double* state, const double* nu, int m,
                          const int* verdict, hipStream_t s);
@@ -117,6 +122,25 @@ void launch_dense64_correct_deferred(const Dense64CorrectPlan& pl, const double*
 // Launch 6 of launch_dense64_correct (k_dc_update) at rank p on the pending panels; zero: a device word that holds 0.
 void launch_dense64_flush(const Dense64CorrectPlan& pl, double* Sigma, const double* Kp, const double* Tq, int p,
                           const int* zero, hipStream_t s);
+
+// ---- the Joseph form of the sparse correction with per-state gain weights (ekf_dense64_joseph.hip; the definition is
+// include/ekfslam.h's, ekf_dense64_correct_sparse_joseph): Sigma <- Sigma - K T - D K^T with K = diag(w) U S^-1 and
+// D = U - K S, one read-modify-write pass of rank 2 m over tiles of kDense64JosephTileRows x kDense64JosephTileCols.
+constexpr int kDense64JosephMaxM = 32;        // two stacked panels of m rows fit the 64-row panel stride
+constexpr int kDense64JosephTileRows = 16;    // a wave's unit: one row block ...
+constexpr int kDense64JosephTileCols = 128;   // ... of a workgroup's column strip
+constexpr int kDense64JosephThreads = 256;
+hipError_t dense64_joseph_prepare();   // raises the dynamic-LDS limit of the update (64 KiB at m = 32)
+// Where the call keeps what is its own inside the workspace of the plan (the partial panels of the dense correction, which
+// no sparse call uses): the weights [ld] and S [32 * 32] as doubles, then one byte per state (w != 0), per row block and
+// per column strip (bit 0: some w != 0 among its live states, bit 1: some w == 0).
+struct Dense64JosephWs { double *w, *S; unsigned char *state_on, *block, *strip; };
+Dense64JosephWs dense64_joseph_ws(const Dense64CorrectPlan& pl, double* ws);
+// The four launches: launch_dense64_sparse_panels, k_dj_gain, k_dj_update.  w: the weights on the device (the region of
+// dense64_joseph_ws) or NULL for all 1; everything else as launch_dense64_correct_sparse, 1 <= m <= 32.
+void launch_dense64_correct_sparse_joseph(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
+                                          const int* cols, const double* Hc, const double* R, const double* nu,
+                                          const double* w, int m, int s, double* nis, int* verdict, hipStream_t st);
 
 // ---- fp64 (re)initialisation of a block of states (ekf_dense64_init.hip) on the same Sigma and state: the block
 // b = [first, first + r) becomes a function of the s listed states with Jacobian G (r x s): F = identity with F[b, b] = 0

@@ -390,14 +390,14 @@ void launch_score(const double* Sigma, PEND pend, const int* cols, const double*
 // The gather and the scoring with J = 1 (S^-1 into ws, the verdict word, nis) in front of either form's gain.
 template <class PEND>
 void launch_panels(const Dense64CorrectPlan& pl, const double* Sigma, PEND pend, double* Tout, double* ws, const int* cols,
-                   const double* Hc, const double* R, const double* nu, int m, int s, double* nis, int* verdict,
-                   hipStream_t st) {
+                   const double* Hc, const double* R, const double* nu, int m, int s, double* nis, double* S_out,
+                   int* verdict, hipStream_t st) {
     // the panels are written up to N rounded up to 128 (zeros from N on): ld itself when N spans the handle, and with a live
     // dimension below it every strip the gain and the update of that width read
     const int n_strips = (pl.N + 127) / 128 * 2;
     hipLaunchKernelGGL(k_dsp_gather<PEND>, dim3(2 * n_strips), dim3(kThreads), gather_lds(m, s, pend.p), st, Sigma, cols,
                        Hc, Tout, ws + pl.off_Ut, pl.N, pl.ld, m, s, n_strips, pend);
-    launch_score(Sigma, pend, cols, Hc, R, 1, nu, 1, m, s, pl.ld, nu ? nis : nullptr, nullptr, verdict, ws + pl.off_Sinv,
+    launch_score(Sigma, pend, cols, Hc, R, 1, nu, 1, m, s, pl.ld, nu ? nis : nullptr, S_out, verdict, ws + pl.off_Sinv,
                  st);
 }
 
@@ -420,14 +420,21 @@ void launch_dense64_score_sparse(const double* Sigma, const double* Kp, const do
 void launch_dense64_correct_sparse(const Dense64CorrectPlan& pl, double* Sigma, double* state, double* ws,
                                    const int* cols, const double* Hc, const double* R, const double* nu, int m, int s,
                                    double* nis, int* verdict, hipStream_t st) {
-    launch_panels(pl, Sigma, Eager{}, ws + pl.off_T, ws, cols, Hc, R, nu, m, s, nis, verdict, st);
+    launch_panels(pl, Sigma, Eager{}, ws + pl.off_T, ws, cols, Hc, R, nu, m, s, nis, nullptr, verdict, st);
     launch_dense64_correct_tail(pl, Sigma, state, ws, nu, m, verdict, st);
+}
+
+void launch_dense64_sparse_panels(const Dense64CorrectPlan& pl, const double* Sigma, double* ws, const int* cols,
+                                  const double* Hc, const double* R, const double* nu, int m, int s, double* nis,
+                                  double* S_out, int* verdict, hipStream_t st) {
+    launch_panels(pl, Sigma, Eager{}, ws + pl.off_T, ws, cols, Hc, R, nu, m, s, nis, S_out, verdict, st);
 }
 
 void launch_dense64_correct_deferred(const Dense64CorrectPlan& pl, const double* Sigma, double* state, double* ws,
                                      double* Kp, double* Tq, int p, const int* cols, const double* Hc, const double* R,
                                      const double* nu, int m, int s, double* nis, int* verdict, hipStream_t st) {
-    launch_panels(pl, Sigma, Pending{Kp, Tq, p}, Tq + (size_t)p * pl.ld, ws, cols, Hc, R, nu, m, s, nis, verdict, st);
+    launch_panels(pl, Sigma, Pending{Kp, Tq, p}, Tq + (size_t)p * pl.ld, ws, cols, Hc, R, nu, m, s, nis, nullptr, verdict,
+                  st);
     launch_dense64_gain(pl, ws, Kp + (size_t)p * pl.ld, state, nu, m, verdict, st);
 }
 

@@ -623,6 +623,56 @@ ekf_status ekf_dense64_correct_sparse_deferred(ekf_dense64_handle h, int m, int 
 ekf_status ekf_dense64_flush(ekf_dense64_handle h, double* elapsed_ms);    /* no-op, 0 ms, with nothing pending */
 ekf_status ekf_dense64_pending(ekf_dense64_handle h, int* rows);           /* rows of K / T waiting, 0 .. 64 */
 
+/* The Joseph form of ekf_dense64_correct_sparse, with per-state gain weights.  The short form Sigma <- Sigma - K T is the
+ * covariance of the updated state for the exact optimal gain only, and it cancels when a prior variance is large against
+ * R.  The Joseph form
+ *   Sigma <- (I - K H) Sigma (I - K H)^T + K R K^T  =  Sigma - K T - U K^T + K S K^T      (U = Sigma H^T, S = T H^T + R)
+ * is a sum of congruences: it stays positive semi-definite up to rounding and it holds for ANY gain.  With D = U - K S, the
+ * residual of the gain equation (zero up to rounding for the optimal gain), it is Sigma <- Sigma - K T - D K^T: one
+ * read-modify-write pass of rank 2 m over Sigma.  "Any gain" is used for the PARTIAL UPDATE (Schmidt-Kalman): per-state
+ * weights w in [0, 1] give K = diag(w) U S^-1; a state with w = 0 is a CONSIDER state, whose estimate and own covariance
+ * block stay untouched while its cross-covariances stay consistent.
+ * cols, Hc, R, nu, nis_out, the verdict rule and the order of the argument checks are ekf_dense64_correct_sparse's; only the
+ * cap on m differs, 1 <= m <= EKF_DENSE64_JOSEPH_MAX_M (the two stacked panels of m rows fit the 64-row panel stride).
+ * SAME T, U, S, S^-1, nis: they are the bits ekf_dense64_correct_sparse computes for the same arguments on the same Sigma
+ *   (the same gather, sum and elimination code is launched).
+ * THE GAIN: K[i][k] = +0.0 when w_i == 0, otherwise fl(w_i * G[i][k]), with G = U S^-1 summed as the short form's gain
+ *   kernel sums it (l ascending, a product and an addition per term).  Rows i >= Na are zero.
+ * THE STATE: state[i] += sum_k K[i][k] nu[k] in that kernel's fold (eight partial sums over k = g, g + 8, .., then g
+ *   ascending).  A state with w_i == 0 is NOT WRITTEN.
+ * THE RESIDUAL: D[i][k] = U[i][k] - sum_l K[i][l] S[l][k]: the accumulator starts at U[i][k] and takes one fused
+ *   multiply-add per l, ascending.  S is the summed S, the matrix S_out of ekf_dense64_score_sparse returns.
+ * THE COVARIANCE: Sigma[i][j] <- Sigma[i][j] - sum_k K[i][k] T[k][j] - sum_k D[i][k] K[j][k] for i, j < Na.  All 2 m
+ *   products are folded into ONE accumulator that starts at Sigma[i][j]; the K T terms come first, then the D K^T terms.
+ *   The association inside a group of terms is the implementation's (chains of v_mfma_f64_16x16x4_f64, four terms each); it
+ *   depends on (m, tile shape) alone.  There are no atomics on floating-point data, and a run repeats bit for bit.
+ * THE CONSIDER RULE (a definition, not only an optimisation): an entry Sigma[i][j] with w_i == 0 and w_j == 0 enters no
+ *   result and is not written -- a NaN, an Inf or a -0.0 there keeps its bits.  An entry with w_i == 0 takes the D K^T terms
+ *   only, with D[i] = U[i]; an entry with w_j == 0 takes the K T terms only.
+ * TILES: the pass works on tiles of tile_rows x tile_cols entries (ekf_dense64_joseph_launch_info; aligned at 0).  A tile
+ *   whose rows and columns are all considered is not touched, so the cost follows the active states even while they are
+ *   still correlated with the rest (ekf_dense64_set_live needs a decoupled tail for that).  *tiles_skipped (nullable) is the
+ *   number of untouched tiles, a pure function of (Na, w, tile shape): (row groups without a w != 0) * (column groups
+ *   without one); 0 with gain_w == NULL.
+ * gain_w: N doubles (the handle's N), NULL = all 1.  Every value among the first Na must be finite and in [0, 1], else the
+ *   call returns EKF_ERR_INVALID before the device is looked at (a host scan, after the checks above); values at indices
+ *   >= Na are ignored.
+ * EAGER ONLY: the call needs Sigma in memory, so it FLUSHES THE PENDING ROWS FIRST, after its argument checks (a refused
+ *   call leaves them in place) and inside the timed region, as ekf_dense64_health does.
+ * LIVE: a structured call on the live corner.  Nothing at a row or column >= Na is read or written; accesses are masked
+ *   element by element.
+ * A singular or non-finite S returns EKF_ERR_STATE; Sigma and the state stay exactly as they were, except that the flush, if
+ *   any, has happened.  The writing launches read the verdict word before their first store.
+ * Four launches (gather, scoring with J = 1, gain, update), synchronous, on the handle's stream; it uses the operand buffer
+ * and the workspace of ekf_dense64_correct and allocates nothing.  elapsed_ms (nullable) = HIP-event time of the launches. */
+#define EKF_DENSE64_JOSEPH_MAX_M 32
+ekf_status ekf_dense64_correct_sparse_joseph(ekf_dense64_handle h, int m, int s, const int* cols, const double* Hc,
+                                             const double* R, const double* nu,
+                                             const double* gain_w /* N doubles (the handle's N), NULL = all 1 */,
+                                             double* nis_out, long long* tiles_skipped /* nullable */,
+                                             double* elapsed_ms);
+ekf_status ekf_dense64_joseph_launch_info(ekf_dense64_handle h, int* tile_rows, int* tile_cols, int* threads);
+
 /* The landmark front end: the reference's data_association() (ekf_slam.cpp:278-402) on the handle's own state.  The sparse
  * calls above are model-free, so a caller that spells the reference's loop with them reads the state back,
  * builds one Jacobian per known landmark on the host, sends them up, takes the scores down, decides, and builds the
@@ -694,6 +744,11 @@ ekf_status ekf_dense64_score_landmarks(ekf_dense64_handle h, const ekf_params* p
                                        double* elapsed_ms);
 #define EKF_DENSE64_LM_DEFERRED  1u  /* corrections through the deferred path (pending rows), else correct_sparse */
 #define EKF_DENSE64_LM_GROW_LIVE 2u  /* a new landmark first grows the live dimension to 3 + 2 (known + 1) if it is smaller */
+/* EKF_DENSE64_LM_JOSEPH (ekf_dense64_measure_landmarks, ekf_dense64_associate_landmarks, ekf_dense64_merge_landmarks; every
+ * other call refuses it as an unknown bit): the call's corrections go through ekf_dense64_correct_sparse_joseph's internal
+ * path with gain_w = NULL instead of ekf_dense64_correct_sparse's.  An eager form: together with EKF_DENSE64_LM_DEFERRED the
+ * call returns EKF_ERR_INVALID where it checks its flag bits.  Without the flag every launch and every bit is as before. */
+#define EKF_DENSE64_LM_JOSEPH    8u  /* corrections in the Joseph form (eager only); 4u stays an unknown bit */
 ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle h, const ekf_params* params, int J,
                                            const double* meas_xy /* [J][2] */, int n_max, int* known /* IN/OUT */,
                                            unsigned flags,
