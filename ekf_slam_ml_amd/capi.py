@@ -59,6 +59,7 @@ SYMBOLS = [
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
+    "ekf_dense64_frame_launch_info", "ekf_dense64_map_congruence", "ekf_dense64_reframe_landmarks",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -267,6 +268,9 @@ def load():
         "ekf_dense64_factor": [h, C.POINTER(FactorReport), _dp],
         "ekf_dense64_get_factor": [h, _dp],
         "ekf_dense64_whiten": [h, C.c_int, _dp, _dp, _dp, _dp],
+        "ekf_dense64_frame_launch_info": [h, _ip, _ip, _ip],
+        "ekf_dense64_map_congruence": [h, _dp, _dp, _dp],
+        "ekf_dense64_reframe_landmarks": [h, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
@@ -1170,6 +1174,57 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_factor_launch_info(self._h, C.byref(block), C.byref(th)))
         return {"block": block.value, "threads": th.value}
 
+    FRAME_FIXED, FRAME_ROBOT = 0, 1   # EKF_DENSE64_FRAME_FIXED, EKF_DENSE64_FRAME_ROBOT
+
+    def map_congruence(self, G, C=None):
+        """Sigma[:live, :live] <- J Sigma J^T in place for J = blockdiag(1, G, ..., G) + [C | 0] (ekf_dense64_map_congruence,
+        include/ekfslam.h): G 2 x 2 on the robot position and every landmark (the pairs (1, 2), (3, 4), ...), C live x 3 on
+        the pose columns or None (the rank-6 part is skipped; with G = I in bits Sigma is not passed over).  live must be
+        3 + 2 n.  Flushes the pending rows first; the state is not touched; Sigma is never symmetrised.  Returns elapsed_ms"""
+        self._open()
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if G.shape != (2, 2):
+            raise ValueError("G must be 2 x 2")
+        if C is not None:
+            C = np.ascontiguousarray(C, dtype=np.float64)
+            if C.shape != (self.live, 3):
+                raise ValueError("C must be live x 3")
+        ms = np.zeros(1)   # (the parameter C hides ctypes here)
+        _check(self._lib.ekf_dense64_map_congruence(self._h, _d(G), _d(C) if C is not None else None, _d(ms)))
+        return float(ms[0])
+
+    def reframe(self, mode, dtheta=0.0, tx=0.0, ty=0.0, want_terms=False):
+        """State and Sigma of the live corner into another frame (ekf_dense64_reframe_landmarks).  FRAME_FIXED: theta +=
+        dtheta (not wrapped), q <- R(dtheta) q + (tx, ty) for the robot position and every landmark.  FRAME_ROBOT: the map in
+        the robot's own frame, the old origin becomes the "pose" (dtheta, tx, ty ignored); its own inverse up to rounding,
+        and until it is called again the state is not what predict_landmarks() assumes.  Returns elapsed_ms, or with
+        want_terms (True, or a float64 vector of at least 4 + 3 live entries to fill) (G (2, 2), C (live, 3) or None for FRAME_FIXED, elapsed_ms): map_congruence(G, C) gives the same Sigma
+        bit for bit."""
+        self._open()
+        mode = int(mode)
+        terms = None
+        if isinstance(want_terms, np.ndarray):   # the caller's own buffer: the library writes 4 + 3 live doubles into it
+            terms = want_terms
+            if terms.dtype != np.float64 or terms.ndim != 1 or not terms.flags.c_contiguous or terms.shape[0] < 4 + 3 * self.live:
+                raise ValueError("terms must be a contiguous float64 vector of at least 4 + 3 live entries")
+        elif want_terms:
+            terms = np.empty(4 + 3 * self.live, dtype=np.float64)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_reframe_landmarks(self._h, mode, float(dtheta), float(tx), float(ty),
+                                                       _d(terms) if terms is not None else None, C.byref(ms)))
+        if terms is None:
+            return ms.value
+        terms = terms[:4 + 3 * self.live]
+        return terms[:4].reshape(2, 2).copy(), (terms[4:].reshape(-1, 3).copy() if mode == self.FRAME_ROBOT else None), ms.value
+
+    def frame_launch_info(self):
+        """{tile_rows, tile_cols, threads}: the tile of map_congruence()'s pass in states (origins at 3 + a tile_rows,
+        3 + b tile_cols) and its workgroup size (test hook)"""
+        self._open()
+        tr, tc, th = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_frame_launch_info(self._h, C.byref(tr), C.byref(tc), C.byref(th)))
+        return {"tile_rows": tr.value, "tile_cols": tc.value, "threads": th.value}
+
     def _sparse_operands(self, cols, Hc, R, nu, max_m):
         """the shape and range checks of a sparse correction -> (cols int32, Hc, R, nu or None, m, s), contiguous"""
         cols = self._index_lists(cols, 1)
@@ -1708,6 +1763,33 @@ class DenseEKFSLAM:
     def factor(self):
         """DensePropagator64.factor() of the live corner: definiteness and log det Sigma"""
         return self.handle.factor()
+
+    def _framed(self, call):
+        """run a frame change on the states the map has: all n landmarks after measurement(), the known ones of
+        data_association() otherwise.  Below the live dimension the rest must be decoupled from them."""
+        d = self.handle
+        live = d.live
+        W = 3 + 2 * (self.n if self._init_flag else self._known)
+        if W > live:
+            raise ValueError("the map reaches beyond the live dimension")
+        if W < live:
+            if d.coupling(W)[0] != 0:
+                raise ValueError(f"states beyond {W} are coupled to the map: a frame change of the first {W} alone is not exact")
+            d.live = W
+        try:
+            return call()
+        finally:
+            if W < live:
+                d.live = live
+
+    def reframe(self, dtheta, tx, ty):
+        """the map and its covariance in the frame reached by the rigid transform q -> R(dtheta) q + (tx, ty)
+        (DensePropagator64.reframe, FRAME_FIXED): what map_nees() needs when the truth comes in a world frame"""
+        return self._framed(lambda: self.handle.reframe(DensePropagator64.FRAME_FIXED, dtheta, tx, ty))
+
+    def robot_frame(self):
+        """the map in the robot's own frame (FRAME_ROBOT); call it again before filtering on"""
+        return self._framed(lambda: self.handle.reframe(DensePropagator64.FRAME_ROBOT))
 
     def map_nees(self, truth):
         """(state - truth)^T Sigma^-1 (state - truth) over the live dimension against the last factor(): the NEES of the

@@ -6,7 +6,8 @@
 // (ekf_dense64_landmarks.hip), the reference's prediction() and measurement() on that state (ekf_dense64_model.hip), the
 // scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), the health check of the live corner and its
 // exact symmetrisation (ekf_dense64_health.hip), its Cholesky factor with the substitution against it
-// (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), and
+// (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), the
+// map re-expressed in another frame (ekf_dense64_frame.hip), and
 // the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
@@ -42,7 +43,7 @@ ekf_status ekf_dense64_s::created() {
 
 void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
     for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p, health.p, factor.p, factor_ws.p, whiten.p})
+                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p, health.p, factor.p, factor_ws.p, whiten.p, frame.p})
         if (p) (void)hipFree(p);
     scan_up.release();
 }
@@ -978,6 +979,72 @@ ekf_status ekf_dense64_whiten(ekf_dense64_handle d, int nrhs, const double* B, d
         HIPC(hipMemcpy2D(Y_out, sizeof(double) * Na, rhs + (size_t)kMaxRhs * pl.rows, pitch, sizeof(double) * Na, nrhs,
                          hipMemcpyDeviceToHost));
     return EKF_OK;
+}
+
+// ---- the map in another frame (ekf_dense64_frame.hip) ---------------------------------------------------------------------
+ekf_status ekf_dense64_frame_launch_info(ekf_dense64_handle d, int* tile_rows, int* tile_cols, int* threads) {
+    if (!d || !tile_rows || !tile_cols || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_frame_launch_info: null argument");
+    *tile_rows = ekf::kDense64FrameTileRows;
+    *tile_cols = ekf::kDense64FrameTileCols;
+    *threads = ekf::kDense64FrameThreads;
+    return EKF_OK;
+}
+
+namespace {
+static_assert(ekf::kDense64FrameFixed == EKF_DENSE64_FRAME_FIXED && ekf::kDense64FrameRobot == EKF_DENSE64_FRAME_ROBOT,
+              "the header's modes");
+// the live dimension a frame change runs at (odd, >= 3) and the workspace for it; before e0, nothing changed on a refusal
+ekf_status frame_reserve(ekf_dense64_s* d, const char* fn, ekf::Dense64FramePlan* pl) {
+    if (d->live < 3 || d->live % 2 == 0)
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": the live dimension must be 3 + 2 n (a pose and whole landmarks)");
+    HIPC(hipSetDevice(d->device));
+    *pl = ekf::dense64_frame_plan(d->live, d->ld);
+    return d->frame.reserve(sizeof(double) * pl->doubles, d->stream, false, fn, "the frame change's workspace");
+}
+// G = I in bits (+1, +0, +0, +1): with no C the congruence is the identity map and Sigma is not passed over
+bool is_identity(const double* G) {
+    const double I[4] = {1.0, 0.0, 0.0, 1.0};
+    return std::memcmp(G, I, sizeof(I)) == 0;
+}
+}  // namespace
+
+// G and C go up into the terms region, the pending rows are applied, three launches.
+ekf_status ekf_dense64_map_congruence(ekf_dense64_handle d, const double* G, const double* C, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_map_congruence";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!G) return fail(EKF_ERR_INVALID, std::string(fn) + ": null G");
+    ekf::Dense64FramePlan pl;
+    EKFC(frame_reserve(d, fn, &pl));
+    double* ws = d->frame.as<double>();
+    HIPC(hipMemcpyAsync(ws + pl.off_terms, G, sizeof(double) * 4, hipMemcpyHostToDevice, d->stream));
+    if (C) HIPC(hipMemcpyAsync(ws + pl.off_terms + 4, C, sizeof(double) * 3 * (size_t)pl.Na, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    if (C || !is_identity(G)) ekf::launch_dense64_frame_congruence(pl, d->S, ws, C != nullptr, d->stream);
+    return finish_timed(d, elapsed_ms);
+}
+
+// One launch for the terms and the new state, the congruence on those terms, the new state copied over the old one.
+ekf_status ekf_dense64_reframe_landmarks(ekf_dense64_handle d, int mode, double dtheta, double tx, double ty, double* terms_out,
+                                         double* elapsed_ms) {
+    const char* fn = "ekf_dense64_reframe_landmarks";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (mode != EKF_DENSE64_FRAME_FIXED && mode != EKF_DENSE64_FRAME_ROBOT)
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": mode is EKF_DENSE64_FRAME_FIXED or EKF_DENSE64_FRAME_ROBOT");
+    const bool robot = mode == EKF_DENSE64_FRAME_ROBOT;
+    if (!robot && !(std::isfinite(dtheta) && std::isfinite(tx) && std::isfinite(ty)))
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": dtheta, tx and ty must be finite");
+    ekf::Dense64FramePlan pl;
+    EKFC(frame_reserve(d, fn, &pl));
+    double* ws = d->frame.as<double>();
+    const double c = robot ? 0.0 : std::cos(dtheta), s = robot ? 0.0 : std::sin(dtheta);
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();
+    ekf::launch_dense64_frame_state(pl, mode, d->x, ws, dtheta, c, s, tx, ty, d->stream);
+    ekf::launch_dense64_frame_congruence(pl, d->S, ws, robot, d->stream);
+    HIPC(hipMemcpyAsync(d->x, ws + pl.off_state, sizeof(double) * pl.Na, hipMemcpyDeviceToDevice, d->stream));
+    if (terms_out && !robot) std::fill(terms_out + 4, terms_out + 4 + 3 * (size_t)pl.Na, 0.0);   // (no C was used)
+    return finish_timed(d, elapsed_ms, {{terms_out, ws + pl.off_terms, sizeof(double) * (robot ? 4 + 3 * (size_t)pl.Na : 4)}});
 }
 
 // ---- duplicate landmarks: the all-pairs scan (ekf_dense64_pairs.hip) and the merge, a layer over the calls above ----------

@@ -348,4 +348,28 @@ void launch_dense64_factor(const Dense64FactorPlan& p, const double* Sigma, int 
 // solves the diagonal block for all right-hand sides, the first one stores it into Y, the others take it out of their NB
 // rows of the working copy), then d2 [kDense64WhitenMaxRhs] = the squared norms, a fixed fold.
 void launch_dense64_whiten(const Dense64FactorPlan& p, const double* factor, double* rhs, double* d2, hipStream_t st);
+
+// ---- the map in another frame (ekf_dense64_frame.hip; the definition is include/ekfslam.h's, ekf_dense64_map_congruence):
+// Sigma <- J Sigma J^T on the live corner for J = blockdiag(1, G, ..., G) + [C | 0], in place, one pass over tiles of
+// kDense64FrameTileRows x kDense64FrameTileCols whose origins sit on odd indices (3 + ...), and the state that goes with it.
+constexpr int kDense64FrameTileRows = 64;
+constexpr int kDense64FrameTileCols = 128;
+constexpr int kDense64FrameThreads = 256;
+constexpr int kDense64FrameFixed = 0, kDense64FrameRobot = 1;   // EKF_DENSE64_FRAME_FIXED, EKF_DENSE64_FRAME_ROBOT
+// the workspace of a call, offsets in doubles: terms = G [4] | C [Na][3] (room for ld rows) | the new state [ld] | the old
+// pose rows [3][ld] | the old pose columns, transposed [3][ld] | the panels A | C^T | (D Sigma_c)^T, [9][ld]
+struct Dense64FramePlan {
+    int Na, ld, pairs;   // pairs: index 0 and the (Na - 1) / 2 pairs (1, 2), (3, 4), ...
+    size_t off_terms, off_state, off_rows, off_cols, off_panels, doubles;
+};
+Dense64FramePlan dense64_frame_plan(int Na, int ld);   // Na odd, >= 3 (the caller checks)
+// One launch: terms and the new state (Na entries) into the workspace from the state as it is; the state is not written.
+// FIXED: G = [c, -s, s, c] from the arguments, C is not written.  ROBOT: cos and sin of state[0] on the device; the
+// arguments behind `ws` are ignored.
+void launch_dense64_frame_state(const Dense64FramePlan& p, int mode, const double* state, double* ws, double dtheta, double c,
+                                double s, double tx, double ty, hipStream_t st);
+// Three launches on the terms that sit in the workspace (has_C: C is read, otherwise the rank-6 part is skipped): the
+// snapshot and the panels, the pass over Sigma[3:Na, 3:Na], the new pose rows and columns.  Nothing at an index >= Na is
+// read or written.
+void launch_dense64_frame_congruence(const Dense64FramePlan& p, double* Sigma, double* ws, bool has_C, hipStream_t st);
 }  // namespace ekf

@@ -1285,6 +1285,77 @@ ekf_status ekf_dense64_whiten(ekf_dense64_handle h, int nrhs, const double* B /*
                               double* Y_out /* [nrhs][Na], nullable */, double* d2_out /* [nrhs], nullable */,
                               double* elapsed_ms);
 
+/* The map in another frame.  A SLAM map is defined up to the frame it was started in; these calls change that frame on the
+ * device: Sigma <- J Sigma J^T in place, one streaming pass over the live corner (16 Na^2 bytes, what a correction moves),
+ * instead of ekf_dense64_get_sigma, a host product and ekf_dense64_set.  Opt-in: no other entry point calls these or
+ * launches anything different because they exist.
+ * The Jacobian of a frame change on (theta, x, y, l1x, l1y, ...) is J = D + [C | 0]: D = blockdiag(1, G, G, ..., G) with the
+ * 2 x 2 block G (row-major G[4]) on the robot position and on every landmark, and C, Na x 3 row-major, on the pose columns.
+ * THE PAIRS ARE (1, 2), (3, 4), ...: ODD-ALIGNED, INDEX 0 STANDS ALONE.
+ * ekf_dense64_map_congruence is a structured call on the live corner Sigma[0:Na, 0:Na], Na = live.  NA MUST BE ODD AND >= 3
+ * (Na = 3 + 2 n), otherwise EKF_ERR_INVALID.  Nothing at a row or column index >= Na is read or written (loads and stores
+ * are masked element by element).  It needs Sigma in memory, so it FLUSHES THE PENDING ROWS FIRST, carry or not, after its
+ * argument checks and inside the timed region, as ekf_dense64_health does.  IT DOES NOT TOUCH THE STATE VECTOR.  A NULL
+ * handle (checked first), a NULL G or a bad live dimension returns EKF_ERR_INVALID and changes nothing, the pending rows
+ * included.  C is nullable.
+ * DEFINITION, every operation in IEEE binary64, round to nearest even, each rounded on its own (fl) unless it is written as
+ * a fused multiply-add fma(a, b, c) = fl(a b + c); Sigma below is the corner ON ENTRY (after the flush):
+ *   1. P = D Sigma D^T, per 2 x 2 block B = Sigma[i..i+1][j..j+1] of two pairs:
+ *        Y = G B     Y[r][c] = fma(G[r][1], B[1][c], fl(G[r][0] * B[0][c]))
+ *        Z = Y G^T   Z[r][c] = fma(Y[r][1], G[c][1], fl(Y[r][0] * G[c][0]))          P[i+r][j+c] = Z[r][c]
+ *      Row 0 and column 0 get the one-sided product: P[0][j+c] = fma(Sigma[0][j+1], G[c][1], fl(Sigma[0][j] * G[c][0])),
+ *      P[i+r][0] = fma(G[r][1], Sigma[i+1][0], fl(G[r][0] * Sigma[i][0])), P[0][0] = Sigma[0][0].
+ *   2. With Sigma_p the OLD pose rows (3 x Na), Sigma_c the OLD pose columns (Na x 3), Sigma_pp the old 3 x 3 corner:
+ *        A  = Sigma_p D^T + Sigma_pp C^T (3 x Na): the first term as the one-sided product of step 1 (column 0: Sigma[k][0]),
+ *             then a = fma(Sigma_pp[k][l], C[j][l], a) for l = 0, 1, 2 in ascending order
+ *        Bc = D Sigma_c (Na x 3): the one-sided product from the left (row 0: Sigma[0][k])
+ *   3. Sigma'[i][j] = P[i][j] + sum_{k<3} C[i][k] A[k][j] + sum_{k<3} Bc[i][k] C[j][k]: six fused multiply-adds into an
+ *      accumulator that starts at P[i][j], the C A terms first, k ascending:
+ *        acc = fma(C[i][k], A[k][j], acc), k = 0, 1, 2;  acc = fma(Bc[i][k], C[j][k], acc), k = 0, 1, 2
+ *   4. C = NULL: the rank-6 part (steps 2 and 3) is SKIPPED, not multiplied by zeros, so Sigma' = P and NaN payloads in P
+ *      survive.  C = NULL and G = I IN BITS (+1.0, +0.0, +0.0, +1.0): the map is the identity and Sigma is not passed over
+ *      at all (the pending rows are still flushed), so every entry keeps its bits, NaN payloads and -0.0 included; step 1
+ *      alone would turn a -0.0 beside a positive entry into +0.0 and spread a NaN over its block.
+ * SIGMA IS NEVER SYMMETRISED: Sigma'[i][j] uses Sigma[i][j], never Sigma[j][i].  Sixteen bounds the rounded operations an
+ * entry sees (4 products and 4 fused steps of step 1, 4 + 3 of step 2, 6 of step 3), so
+ *   |Sigma' - J Sigma J^T|_ij <= gamma_16 ((|D| + |[C | 0]|) |Sigma| (|D| + |[C | 0]|)^T)_ij,  gamma_k = k u / (1 - k u), u = 2^-53.
+ * (The tests hold the tighter form with |J| = |D + [C | 0]| entry by entry, which differs on the 3 x 3 pose block alone.)
+ * On integer operands small enough for every intermediate to stay below 2^53 the result is exact in any order.
+ * THE LAUNCHES.  A small launch (a thread per pair) snapshots the three pose rows and the three pose columns -- the only
+ * walk down a column, 3 Na entries -- into the workspace and builds A, C^T and Bc^T as nine rows in the handle's [k][ld]
+ * panel layout (two 6-row panels that share C^T).  The hot kernel makes one pass over Sigma[3:Na, 3:Na]: loads and stores
+ * along rows, a 2 x 2 block is one lane's business, so the pass is in place with no staging copy of Sigma; tiles of
+ * tile_rows x tile_cols states whose ORIGINS SIT ON ODD INDICES (3 + a tile_rows, 3 + b tile_cols), so no block straddles
+ * two workgroups; the panel of a tile's columns sits in registers, the one of its rows comes through the scalar cache.  A
+ * sibling launch writes the new pose rows and columns from the snapshot alone.  NO ATOMICS: A RUN REPEATS BIT FOR BIT, and
+ * an entry's bits do not depend on N, on ld or on what lies outside the corner.  ekf_dense64_frame_launch_info reports the
+ * tile sides in states and the workgroup size.  The workspace (19 ld + 4 doubles, 1.6 MB at N = 10003) comes from the
+ * handle, allocated on first use; a failure there returns EKF_ERR_NOMEM and leaves the handle as it was.
+ * ekf_dense64_reframe_landmarks transforms the state and Sigma together; the domain rules are those of the congruence, and a
+ * mode other than the two below, or (FIXED) a dtheta, tx or ty that is not finite, returns EKF_ERR_INVALID.
+ *   EKF_DENSE64_FRAME_FIXED: a known rigid transform.  theta' = theta + dtheta, NOT WRAPPED (as the reference's
+ *     prediction()); q' = R(dtheta) q + t for the robot position and every landmark: x' = fl(fma(-s, y, fl(c x)) + tx),
+ *     y' = fl(fma(c, y, fl(s x)) + ty).  G = R(dtheta) = [c, -s, s, c], C is absent.  c and s are taken ONCE ON THE HOST with
+ *     the C library's cos and sin; the device applies them to the state in a small kernel.
+ *   EKF_DENSE64_FRAME_ROBOT: the inverse pose composition -- the map in the robot's own frame, the old origin becomes the
+ *     "pose"; dtheta, tx, ty are ignored.  With M = R(-theta), M' = dM/dtheta: theta' = -theta, p' = -M p,
+ *     l_i' = M (l_i - p).  G = M; C: theta row [-2, 0, 0], position rows [-M' p | -2 M], landmark i [M' (l_i - p) | -M].
+ *     G and C are built ON THE DEVICE from the handle's own state (the device's cos and sin): the pose never leaves the
+ *     device.  The call is its own inverse up to rounding.  AFTERWARDS THE STATE IS
+ *     NOT THE PARAMETERISATION ekf_dense64_predict_landmarks ASSUMES (the "pose" is the old origin seen from the robot):
+ *     call it again before filtering on.
+ *   terms_out (nullable, [4 + 3 Na] doubles): G [4] then C [Na][3] as they were used (FIXED: C comes back as zeros).  THE
+ *   COVARIANCE RESULT IS, BIT FOR BIT, ekf_dense64_map_congruence WITH THOSE OPERANDS (FIXED: with C = NULL).
+ * Out of scope: a transform with a covariance of its own, joining two handles, carrying the pending rows through the call.
+ * Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the launches, the flush included. */
+#define EKF_DENSE64_FRAME_FIXED 0
+#define EKF_DENSE64_FRAME_ROBOT 1
+ekf_status ekf_dense64_frame_launch_info(ekf_dense64_handle h, int* tile_rows, int* tile_cols, int* threads);
+ekf_status ekf_dense64_map_congruence(ekf_dense64_handle h, const double* G /* [4] */, const double* C /* [Na][3], nullable */,
+                                      double* elapsed_ms);
+ekf_status ekf_dense64_reframe_landmarks(ekf_dense64_handle h, int mode, double dtheta, double tx, double ty,
+                                         double* terms_out /* [4 + 3 Na], nullable */, double* elapsed_ms);
+
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
  * ekf_dense64_get_sigma_block: out[a][c] = Sigma[rows[a]][cols[c]], nr x nc row-major; one gather launch into a buffer
