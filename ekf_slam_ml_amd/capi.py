@@ -32,7 +32,7 @@ SYMBOLS = [
     "ekf_last_error", "ekf_default_params", "ekf_leading_dimension", "ekf_device_count",
     "ekf_create", "ekf_destroy", "ekf_clone", "ekf_predict", "ekf_measure_known", "ekf_associate",
     "ekf_maha_scores", "ekf_get_pose", "ekf_get_landmarks", "ekf_dim", "ekf_get_state", "ekf_set_state",
-    "ekf_get_cov", "ekf_set_cov", "ekf_get_init_flag", "ekf_set_init_flag", "ekf_sync", "ekf_set_tuning", "ekf_set_active_set", "ekf_batch_set_active_set", "ekf_batch_get_touched",
+    "ekf_get_cov", "ekf_set_cov", "ekf_get_init_flag", "ekf_set_init_flag", "ekf_sync", "ekf_device_bytes", "ekf_set_tuning", "ekf_set_active_set", "ekf_batch_set_active_set", "ekf_batch_get_touched",
     "ekf_batch_create", "ekf_batch_destroy", "ekf_batch_reset", "ekf_batch_device_bytes",
     "ekf_batch_upload_known_log", "ekf_batch_run_known", "ekf_batch_upload_unknown_log", "ekf_batch_run_unknown",
     "ekf_batch_get_known_counts", "ekf_batch_get_decisions", "ekf_batch_get_state", "ekf_batch_get_cov",
@@ -182,6 +182,7 @@ def load():
         "ekf_get_init_flag": [h, _ip],
         "ekf_set_init_flag": [h, C.c_int],
         "ekf_sync": [h],
+        "ekf_device_bytes": [h, C.POINTER(C.c_size_t)],
         "ekf_set_active_set": [h, C.c_int],
         "ekf_batch_set_active_set": [h, C.c_int],
         "ekf_batch_get_touched": [h, _ip],
@@ -435,6 +436,11 @@ class EKF_SLAM:
 
     def sync(self):
         _check(self._lib.ekf_sync(self._h))
+
+    def device_bytes(self):
+        b = C.c_size_t()
+        _check(self._lib.ekf_device_bytes(self._h, C.byref(b)))
+        return b.value
 
     def set_active_set(self, enable=True):
         """Stream only the rows of the touched set in the eager correction (exact; opt-in)."""

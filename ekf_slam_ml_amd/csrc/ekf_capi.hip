@@ -505,12 +505,10 @@ ekf_status ekf_phase_trace(ekf_handle h, int enable, long long* out) {
     const size_t cnt = (size_t)2 * ekf::kTraceSlots;
     if (out && P.phase_trace) EKFC(P.download(out, P.phase_trace, sizeof(long long) * cnt));
     if (enable && !P.phase_trace) {
-        EKFC(P.dalloc(&P.phase_trace, cnt));
-        HIPC(hipMemsetAsync(P.phase_trace, 0, sizeof(long long) * cnt, P.stream));
+        EKFC(P.dalloc(&P.phase_trace, cnt, Fill::kZero));
     } else if (!enable && P.phase_trace) {
         HIPC(hipStreamSynchronize(P.stream));
-        HIPC(hipFree(P.phase_trace));
-        P.phase_trace = nullptr;
+        P.mem.free(&P.phase_trace);
     }
     return EKF_OK;
 }
@@ -542,6 +540,12 @@ ekf_status ekf_get_profile(ekf_handle h, double ms[2], long long launches[2]) {
     EKFC(P.use());
     EKFC(P.prof_drain());
     for (int c = 0; c < 2; c++) { ms[c] = P.prof_ms[c]; launches[c] = P.prof_launches[c]; }
+    return EKF_OK;
+}
+
+ekf_status ekf_device_bytes(ekf_handle h, size_t* bytes) {
+    if (!h || !bytes) return fail(EKF_ERR_INVALID, "null argument");
+    *bytes = h->pool.mem.bytes();
     return EKF_OK;
 }
 

@@ -67,7 +67,7 @@ ekf_status ekf_batch_reset(ekf_batch_handle hb) {
 
 ekf_status ekf_batch_device_bytes(ekf_batch_handle hb, size_t* bytes) {
     if (!hb || !bytes) return fail(EKF_ERR_INVALID, "null argument");
-    *bytes = hb->pool.dev_bytes + hb->pool.log_bytes + hb->pool.ulog_bytes;
+    *bytes = hb->pool.mem.bytes();
     return EKF_OK;
 }
 
@@ -118,11 +118,9 @@ ekf_status ekf_batch_upload_known_log(ekf_batch_handle hb, const ekf_known_log* 
         }
     EKFC(free_log(P));
     const size_t n_tw = (size_t)T * B * 2, n_lm = (size_t)T * B * vmax, n_z = n_lm * 2, n_in = (size_t)B * 2 * n;
-    HIPC(hipMalloc((void**)&P.log_twist, sizeof(double) * (n_tw ? n_tw : 1)));
-    HIPC(hipMalloc((void**)&P.log_lm, sizeof(int) * (n_lm ? n_lm : 1)));
-    HIPC(hipMalloc((void**)&P.log_z, sizeof(double) * (n_z ? n_z : 1)));
-    HIPC(hipMalloc((void**)&P.log_init, sizeof(double) * (n_in ? n_in : 1)));
-    P.log_bytes = sizeof(double) * (n_tw + n_z + n_in) + sizeof(int) * n_lm;
+    EKFC(P.mem.replace_group({target(&P.log_twist, n_tw ? n_tw : 1), target(&P.log_lm, n_lm ? n_lm : 1),
+                              target(&P.log_z, n_z ? n_z : 1), target(&P.log_init, n_in ? n_in : 1)},
+                             "ekf_batch_upload_known_log", "the log"));
     HIPC(hipMemcpy(P.log_twist, log->twist, sizeof(double) * n_tw, hipMemcpyHostToDevice));
     if (n_lm) HIPC(hipMemcpy(P.log_lm, log->lm_idx, sizeof(int) * n_lm, hipMemcpyHostToDevice));
     if (n_z) HIPC(hipMemcpy(P.log_z, log->z_xy, sizeof(double) * n_z, hipMemcpyHostToDevice));
@@ -333,12 +331,10 @@ ekf_status ekf_batch_upload_unknown_log(ekf_batch_handle hb, const ekf_unknown_l
             return fail(EKF_ERR_INVALID, "unknown log: count must lie in 0..jmax");
     EKFC(free_ulog(P));
     const size_t n_tw = (size_t)T * B * 2, n_ct = (size_t)T * B, n_me = n_ct * jmax * 2, n_as = n_ct * jmax;
-    HIPC(hipMalloc((void**)&P.ulog_twist, sizeof(double) * n_tw));
-    HIPC(hipMalloc((void**)&P.ulog_count, sizeof(int) * n_ct));
-    HIPC(hipMalloc((void**)&P.ulog_meas, sizeof(double) * (n_me ? n_me : 1)));
-    HIPC(hipMalloc((void**)&P.ulog_assoc, sizeof(int) * (n_as ? n_as : 1)));
-    if (!P.corr_counter) HIPC(hipMalloc((void**)&P.corr_counter, sizeof(unsigned long long)));
-    P.ulog_bytes = sizeof(double) * (n_tw + n_me) + sizeof(int) * (n_ct + n_as);
+    EKFC(P.mem.replace_group({target(&P.ulog_twist, n_tw), target(&P.ulog_count, n_ct), target(&P.ulog_meas, n_me ? n_me : 1),
+                              target(&P.ulog_assoc, n_as ? n_as : 1)},
+                             "ekf_batch_upload_unknown_log", "the log"));
+    if (!P.corr_counter) EKFC(P.dalloc(&P.corr_counter, 1));
     HIPC(hipMemcpy(P.ulog_twist, log->twist, sizeof(double) * n_tw, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(P.ulog_count, log->count, sizeof(int) * n_ct, hipMemcpyHostToDevice));
     if (n_me) HIPC(hipMemcpy(P.ulog_meas, log->meas_xy, sizeof(double) * n_me, hipMemcpyHostToDevice));
@@ -589,15 +585,15 @@ ekf_status ekf_batch_set_known_counts(ekf_batch_handle hb, const int* counts) {
     EKFC(P.use());
     for (int b = 0; b < P.pv.B; b++)
         if (counts[b] < 0 || counts[b] > P.pv.n) return fail(EKF_ERR_INVALID, "known count must lie in 0..n");
+    ScopedMem tmp(P.stream);
     int* dev = nullptr;
-    HIPC(hipMalloc((void**)&dev, sizeof(int) * P.pv.B));
+    EKFC(tmp.alloc(&dev, (size_t)P.pv.B, Fill::kNone, "ekf_batch_set_known_counts", "the counts"));
     ekf_status st = P.upload(dev, counts, sizeof(int) * P.pv.B);
     if (st == EKF_OK) {
         ekf::launch_assoc_begin(P.pv, dev, 0, P.stream);
         st = checked_launch();
     }
     hipError_t e = hipStreamSynchronize(P.stream);
-    (void)hipFree(dev);
     if (st == EKF_OK && e != hipSuccess) st = fail(EKF_ERR_HIP, hipGetErrorString(e));
     if (st != EKF_OK) return st;
     // landmarks below a caller-declared count may carry any covariance: no discovered-prefix structure below it

@@ -17,8 +17,7 @@ ekf_status dense_destroy(H* d) {
     if (!d) return EKF_OK;
     if (d->device >= 0) (void)hipSetDevice(d->device);
     if (d->stream) (void)hipStreamSynchronize(d->stream);
-    for (auto* p : {d->F, d->S, d->T, d->Q})
-        if (p) (void)hipFree(p);
+    d->mem.free_all();
     d->destroying();
     for (hipEvent_t e : {d->e0, d->e1})
         if (e) (void)hipEventDestroy(e);
@@ -31,30 +30,19 @@ template <class H>
 ekf_status dense_create(const char* name, int N, int device, H** out) {
     if (!out || N <= 0) return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
     *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(EKF_ERR_NO_DEVICE, "no HIP device visible: libekfslam_hip has no CPU path");
-    if (device < 0) HIPC(hipGetDevice(&device));
-    if (device >= count) return fail(EKF_ERR_INVALID, "device index out of range");
-    hipDeviceProp_t prop;
-    HIPC(hipGetDeviceProperties(&prop, device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(EKF_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+    EKFC(select_device(&device, true));
     H* d = new (std::nothrow) H();
     if (!d) return fail(EKF_ERR_NOMEM, "host allocation failed");
     d->device = device;
     d->N = N;
     d->ld = round_up(N, ekf::kDenseTile);
-    const size_t bytes = sizeof(*d->F) * (size_t)d->ld * d->ld;
     ekf_status st = EKF_OK;
     auto body = [&]() -> ekf_status {
         HIPC(hipSetDevice(device));
         HIPC(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+        d->mem.stream = d->stream;
         HIPC(ekf::dense_gemm_prepare<elem_t<H>>());
-        for (auto** p : {&d->F, &d->S, &d->T, &d->Q}) {
-            HIPC(hipMalloc((void**)p, bytes));
-            HIPC(hipMemsetAsync(*p, 0, bytes, d->stream));
-        }
+        for (auto** p : {&d->F, &d->S, &d->T, &d->Q}) EKFC(d->mem.alloc(p, (size_t)d->ld * d->ld, Fill::kZero, name, "the matrices"));
         EKFC(d->created());
         HIPC(hipEventCreate(&d->e0));
         HIPC(hipEventCreate(&d->e1));

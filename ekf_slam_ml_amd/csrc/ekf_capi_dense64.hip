@@ -21,32 +21,21 @@ using namespace ekfrt;
 
 ekf_status ekf_dense64_s::created() {
     HIPC(ekf::dense64_correct_prepare());
-    const size_t in = L::corr_in_layout(ld).bytes;
-    HIPC(hipMalloc((void**)&x, sizeof(double) * ld));
-    HIPC(hipMemsetAsync(x, 0, sizeof(double) * ld, stream));
-    HIPC(hipMalloc((void**)&corr_in, in));
-    HIPC(hipMemsetAsync(corr_in, 0, in, stream));
-    HIPC(hipMalloc((void**)&corr_out, L::corr_out_layout().bytes));
-    live = N;
-    pl_full = pl_live = ekf::dense64_correct_plan(N, ld);
-    const size_t ws = pl_full.ws_doubles;
-    if (ws > (size_t)ld * ld) HIPC(hipMalloc((void**)&ws_own, sizeof(double) * ws));
     HIPC(ekf::dense64_block_prepare());
-    HIPC(hipMalloc((void**)&blk_in, L::blk_in_layout().bytes));
     HIPC(ekf::dense64_sparse_prepare());
     HIPC(ekf::dense64_joseph_prepare());
     HIPC(ekf::dense64_init_prepare());
-    HIPC(hipMalloc((void**)&ini_in, L::ini_in_layout().bytes));
-    HIPC(hipMalloc((void**)&rd_buf, L::rd_buf_layout().bytes));
+    live = N;
+    pl_full = pl_live = ekf::dense64_correct_plan(N, ld);
+    const char *fn = "ekf_dense64_create", *what = "the operand buffers";
+    EKFC(mem.replace_group({target_bytes(&x, sizeof(double) * ld, Fill::kZero), target_bytes(&corr_in, L::corr_in_layout(ld).bytes, Fill::kZero),
+                            target_bytes(&corr_out, L::corr_out_layout().bytes), target_bytes(&blk_in, L::blk_in_layout().bytes),
+                            target_bytes(&ini_in, L::ini_in_layout().bytes), target_bytes(&rd_buf, L::rd_buf_layout().bytes)}, fn, what));
+    if (pl_full.ws_doubles > (size_t)ld * ld) EKFC(mem.alloc(&ws_own, pl_full.ws_doubles, Fill::kNone, fn, what));
     return EKF_OK;
 }
 
-void ekf_dense64_s::destroying() {   // every device allocation of the handle beyond F, Sigma, T, Q: the one list
-    for (void* p : {(void*)x, (void*)corr_in, (void*)corr_out, (void*)ws_own, (void*)blk_in, (void*)ini_in, (void*)rd_buf,
-                    sc_small.p, sc_H.p, sc_ws.p, sps.p, pend.p, lm_rec.p, scan.p, joint.p, pairs.p, health.p, factor.p, factor_ws.p, whiten.p, frame.p})
-        if (p) (void)hipFree(p);
-    scan_up.release();
-}
+void ekf_dense64_s::destroying() { scan_up.release(); }
 
 namespace {
 
@@ -85,7 +74,7 @@ bool index_lists_ok(std::vector<int>& stamp, int N, int rows, int s, const int* 
 // The public entry point is checks | pend_reserve | uploads | e0 | correct_sparse_launch | correct_sparse_finish; a caller
 // that builds the operands on the device (the landmark front end) writes them through the same view and runs the last two.
 ekf_status pend_reserve(ekf_dense64_s* d, const char* fn) {
-    return d->pend.reserve(L::pend_layout(d->ld).bytes, d->stream, true, fn, "the pending panels");
+    return d->pend.reserve(d->mem, L::pend_layout(d->ld).bytes, true, fn, "the pending panels");
 }
 
 // the launches of one correction on operands that sit in the operand buffer; behind e0.  joseph_w (eager only): the Joseph
@@ -198,7 +187,7 @@ ekf_status dense64_correct_sparse_joseph(ekf_dense64_s* d, int m, int s, const i
 // The public entry point is checks | sps_layout | sps_reserve | uploads | e0 | score_sparse_launch | copies back; a caller
 // that builds the operands on the device (the landmark front end) writes them through the same view and launches the same.
 ekf_status sps_reserve(ekf_dense64_s* d, size_t need, const char* fn) {
-    return d->sps.reserve(need, d->stream, false, fn, "the candidates' buffer");
+    return d->sps.reserve(d->mem, need, false, fn, "the candidates' buffer");
 }
 // the one launch on operands that sit in the buffer: eager, or read-through as rows are pending
 void score_sparse_launch(ekf_dense64_s* d, const SpsView& v, int J, int m, int s, bool r_shared, bool have_nu,
@@ -255,7 +244,7 @@ ekf_status scan_fit(ekf_dense64_s* d, const char* fn, const double* ranges, int 
         for (Staging& sg : d->scan_up.slot) EKFC(sg.reserve(sizeof(double) * kScanBeams));
         d->scan_rec.assign((l.bytes - l.head) / sizeof(double), 0.0);
     }
-    EKFC(d->scan.reserve(l.bytes, d->stream, true, fn, "the scan buffer"));
+    EKFC(d->scan.reserve(d->mem, l.bytes, true, fn, "the scan buffer"));
     const ScanView v = view(d->scan.p, l);
     Staging& sg = d->scan_up.acquire();
     EKFC(sg.wait());
@@ -300,7 +289,7 @@ ekf_status associate_checks(ekf_dense64_s* d, const std::string& fn, int n_max, 
 
 // what the loop below needs in memory
 ekf_status associate_reserve(ekf_dense64_s* d, const char* fnc, int n_max, bool deferred) {
-    EKFC(d->lm_rec.reserve(sizeof(ekf::Dense64LmRecord), d->stream, false, fnc, "the decision record"));
+    EKFC(d->lm_rec.reserve(d->mem, sizeof(ekf::Dense64LmRecord), false, fnc, "the decision record"));
     if (deferred) EKFC(pend_reserve(d, fnc));
     // the scoring buffer once, for the full map: a map that is being discovered must not pay a hipMalloc and a hipFree
     // (a device synchronisation) per new landmark
@@ -381,7 +370,7 @@ constexpr int kJointInit = ekf::kDense64JointInitGroup;
 int joint_chunk(int J, int count) { return std::min(J, (kSparseRows / 2) / count); }
 
 ekf_status joint_reserve(ekf_dense64_s* d, const char* fnc) {
-    return d->joint.reserve(L::joint_layout().bytes, d->stream, true, fnc, "the joint association's buffer");
+    return d->joint.reserve(d->mem, L::joint_layout().bytes, true, fnc, "the joint association's buffer");
 }
 
 // J readings (in jv.xy) against landmarks [first_lm, first_lm + count), cut into launches of `chunk` readings: per launch
@@ -566,11 +555,11 @@ ekf_status ekf_dense64_score(ekf_dense64_handle d, int J, int m, const double* H
     const bool own_ws = sp.spart_doubles > (size_t)ld * ld;   // else the product buffer, dead between propagations
     if (!d->sc_small.p) {
         const hipError_t e = ekf::dense64_score_prepare();
-        if (e != hipSuccess) return DeviceBuf::refuse(e, fn, what);
+        if (e != hipSuccess) return Ledger::refuse(e, fn, what);
     }
-    EKFC(d->sc_small.reserve(L::sc_small_layout().bytes, d->stream, false, fn, what));
-    EKFC(d->sc_H.reserve(sizeof(double) * sp.h_doubles, d->stream, true, fn, what));
-    if (own_ws) EKFC(d->sc_ws.reserve(sizeof(double) * sp.spart_doubles, d->stream, false, fn, what));
+    EKFC(d->sc_small.reserve(d->mem, L::sc_small_layout().bytes, false, fn, what));
+    EKFC(d->sc_H.reserve(d->mem, sizeof(double) * sp.h_doubles, true, fn, what));
+    if (own_ws) EKFC(d->sc_ws.reserve(d->mem, sizeof(double) * sp.spart_doubles, false, fn, what));
     const size_t mm = (size_t)m * m, w = sizeof(double) * N;
     const int per = sp.cpg * m;   // rows of a full group
     double* Hs = d->sc_H.as<double>();
@@ -828,7 +817,7 @@ namespace {
 // the workspace for the live dimension and its result words set to zero; before e0
 ekf_status health_reserve(ekf_dense64_s* d, const char* fn, ekf::Dense64HealthPlan* pl) {
     *pl = ekf::dense64_health_plan(d->live);
-    EKFC(d->health.reserve(pl->bytes, d->stream, false, fn, "the health pass's workspace"));
+    EKFC(d->health.reserve(d->mem, pl->bytes, false, fn, "the health pass's workspace"));
     HIPC(hipMemsetAsync(d->health.as<char>() + pl->off_words, 0, sizeof(unsigned long long) * ekf::kDense64HealthWords, d->stream));
     return EKF_OK;
 }
@@ -894,8 +883,8 @@ ekf_status ekf_dense64_factor(ekf_dense64_handle d, ekf_dense64_factor_report* o
     if (!out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null report");
     HIPC(hipSetDevice(d->device));
     const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->live);
-    EKFC(d->factor_ws.reserve(pl.bytes, d->stream, false, fn, "the factor's records"));
-    EKFC(d->factor.reserve(pl.factor_bytes, d->stream, true, fn, "the factor's snapshot"));
+    EKFC(d->factor_ws.reserve(d->mem, pl.bytes, false, fn, "the factor's records"));
+    EKFC(d->factor.reserve(d->mem, pl.factor_bytes, true, fn, "the factor's snapshot"));
     char* ws = d->factor_ws.as<char>();
     HIPC(hipMemsetAsync(ws + pl.off_verdict, 0, sizeof(int), d->stream));
     d->factor_ok = 0;   // the snapshot is being overwritten
@@ -967,7 +956,7 @@ ekf_status ekf_dense64_whiten(ekf_dense64_handle d, int nrhs, const double* B, d
     HIPC(hipSetDevice(d->device));
     const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->factor_na);
     const size_t Na = pl.Na, panel = sizeof(double) * kMaxRhs * (size_t)pl.rows, pitch = sizeof(double) * pl.rows;
-    EKFC(d->whiten.reserve(2 * panel + sizeof(double) * kMaxRhs, d->stream, false, fn, "the right-hand sides"));
+    EKFC(d->whiten.reserve(d->mem, 2 * panel + sizeof(double) * kMaxRhs, false, fn, "the right-hand sides"));
     double* rhs = d->whiten.as<double>();
     double* d2 = rhs + 2 * (size_t)kMaxRhs * pl.rows;
     HIPC(hipMemsetAsync(rhs, 0, panel, d->stream));
@@ -999,7 +988,7 @@ ekf_status frame_reserve(ekf_dense64_s* d, const char* fn, ekf::Dense64FramePlan
         return fail(EKF_ERR_INVALID, std::string(fn) + ": the live dimension must be 3 + 2 n (a pose and whole landmarks)");
     HIPC(hipSetDevice(d->device));
     *pl = ekf::dense64_frame_plan(d->live, d->ld);
-    return d->frame.reserve(sizeof(double) * pl->doubles, d->stream, false, fn, "the frame change's workspace");
+    return d->frame.reserve(d->mem, sizeof(double) * pl->doubles, false, fn, "the frame change's workspace");
 }
 // G = I in bits (+1, +0, +0, +1): with no C the congruence is the identity map and Sigma is not passed over
 bool is_identity(const double* G) {
@@ -1068,7 +1057,7 @@ ekf_status ekf_dense64_score_landmark_pairs(ekf_dense64_handle d, int n_lm, doub
         return fail(EKF_ERR_INVALID, std::string(fn) + ": r_merge must be finite and >= 0, gate not a NaN");
     HIPC(hipSetDevice(d->device));
     const ekf::Dense64PairsPlan pl = ekf::dense64_pairs_plan(n_lm);
-    EKFC(d->pairs.reserve(pl.bytes, d->stream, false, fn, "the pair scan's workspace"));
+    EKFC(d->pairs.reserve(d->mem, pl.bytes, false, fn, "the pair scan's workspace"));
     char* ws = d->pairs.as<char>();
     unsigned long long counts[2] = {0, 0};
     HIPC(hipMemsetAsync(ws + pl.off_count, 0, sizeof(counts), d->stream));

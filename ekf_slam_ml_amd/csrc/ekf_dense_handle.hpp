@@ -1,53 +1,24 @@
 // ekf_dense_handle.hpp -- the two dense handles behind include/ekfslam.h, shared by ekf_capi_dense.hip (the fp32 entry
 // points and the templates over the element type) and ekf_capi_dense64.hip (everything only the fp64 handle has).  The
 // templates reach what is particular to a handle through four hooks -- created, destroying, sigma_needed, sigma_replaced --
-// which are empty for fp32.  Also here: DeviceBuf, the one way a buffer is allocated after creation, the typed views of the
+// which are empty for fp32.  Every device buffer of a handle, at creation or later (DeviceBuf), comes from the handle's
+// ledger (ekf_device_mem.hpp).  Also here: the typed views of the
 // layouts of ekf_dense64_layout.hpp, and the end of a timed entry point.
 #pragma once
 #include "ekf_runtime.hpp"
 
 namespace ekfrt {
 
-// A device buffer that is allocated on first use and grows: nothing happens when it is large enough already; otherwise the
-// new buffer is allocated into a local (and zeroed on the stream), the old one is freed (which synchronises: no call is in
-// flight) and the members change only when everything succeeded.
-struct DeviceBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    template <class T> T* as() const { return static_cast<T*>(p); }
-    static ekf_status refuse(hipError_t e, const char* fn, const char* what) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? EKF_ERR_NOMEM : EKF_ERR_HIP,
-                    std::string(fn) + ": " + hipGetErrorString(e) + " while reserving " + what);
-    }
-    ekf_status reserve(size_t need, hipStream_t stream, bool zero_fill, const char* fn, const char* what) {
-        if (need <= bytes) return EKF_OK;
-        void* fresh = nullptr;
-        hipError_t e = hipMalloc(&fresh, need);
-        if (e == hipSuccess && zero_fill) e = hipMemsetAsync(fresh, 0, need, stream);
-        if (e != hipSuccess) {
-            if (fresh) {
-                (void)hipStreamSynchronize(stream);
-                (void)hipFree(fresh);
-            }
-            return refuse(e, fn, what);
-        }
-        if (p) (void)hipFree(p);
-        p = fresh;
-        bytes = need;
-        return EKF_OK;
-    }
-};
-
 template <class E>
 struct DenseHandle {
     int device = -1, N = 0, ld = 0;
     hipStream_t stream = nullptr;
+    Ledger mem;   // every device allocation of the handle
     E *F = nullptr, *S = nullptr, *T = nullptr, *Q = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // the hooks of the shared templates; a handle with more than Sigma hides them with its own
     ekf_status created() { return EKF_OK; }   // inside create, stream and Sigma exist: the handle's own buffers
-    void destroying() {}                      // inside destroy, the stream is idle: free them
+    void destroying() {}                      // inside destroy, the ledger is empty: what else the handle holds
     void sigma_needed() {}                    // Sigma is about to be read or written in memory, inside the timed region
     void sigma_replaced() {}                  // set() gave a new Sigma
 };

@@ -7,6 +7,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_dense.hpp"
 #include "ekf_sim.hpp"
+#include "ekf_device_mem.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -18,13 +19,6 @@
 #include <vector>
 
 namespace ekfrt {
-
-inline thread_local std::string g_err;
-
-inline ekf_status fail(ekf_status st, const std::string& msg) {
-    g_err = msg;
-    return st;
-}
 
 #define HIPC(expr)                                                                              \
     do {                                                                                        \
@@ -41,6 +35,36 @@ inline ekf_status fail(ekf_status st, const std::string& msg) {
     } while (0)
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// the HIP policy of ekf_device_mem.hpp: the only hipMalloc / hipFree of device memory in the C-ABI translation units
+struct HipMem {
+    using Stream = hipStream_t;
+    static constexpr int kOutOfMemory = hipErrorOutOfMemory;
+    static int alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static int free(void* p) { return hipFree(p); }
+    static int fill(void* p, int byte, size_t bytes, Stream s) { return hipMemsetAsync(p, byte, bytes, s); }
+    static int sync(Stream s) { return hipStreamSynchronize(s); }
+    static void clear_error() { (void)hipGetLastError(); }
+    static const char* error_string(int e) { return hipGetErrorString((hipError_t)e); }
+};
+using Ledger = DeviceLedger<HipMem>;
+using ScopedMem = ScopedLedger<HipMem>;
+
+// the device an entry point runs on: *device < 0 = the current one
+inline ekf_status select_device(int* device, bool require_gfx950) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(EKF_ERR_NO_DEVICE, "no HIP device visible: libekfslam_hip has no CPU path");
+    if (*device < 0) HIPC(hipGetDevice(device));
+    if (*device >= count) return fail(EKF_ERR_INVALID, "device index out of range");
+    if (require_gfx950) {
+        hipDeviceProp_t prop;
+        HIPC(hipGetDeviceProperties(&prop, *device));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return fail(EKF_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+    }
+    return EKF_OK;
+}
 
 // pinned host buffer whose last async use is guarded by an event
 struct Staging {
@@ -94,7 +118,7 @@ struct Pool {
     hipStream_t stream = nullptr;
     ekf::PoolView pv{};
     ekf::Rank2Tuning tuning{0, -1, 0, 1, 1, 1};
-    size_t dev_bytes = 0;
+    Ledger mem;         // every device allocation of the pool; ekf_batch_device_bytes is its sum
     int init_flag = 0;  // landmark_init_flag, ekf_slam.hpp:65
 
     // association / single-filter staging (device)
@@ -115,7 +139,6 @@ struct Pool {
     double* log_z = nullptr;
     double* log_init = nullptr;
     double* log_truth = nullptr;  // [T][B][3], simulated logs only
-    size_t log_bytes = 0;
     std::vector<int> slot_active;  // [T][vmax]
 
     // uploaded unknown-association log
@@ -128,7 +151,6 @@ struct Pool {
     int truth_is_unknown_log = 0;  // which simulated log ekf_batch_mc_stats refers to (the latest)
     unsigned long long* corr_counter = nullptr;
     std::vector<int> ucount_host;  // [T][B]
-    size_t ulog_bytes = 0;
 
     std::vector<hipEvent_t> ev_pool;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
@@ -307,21 +329,17 @@ struct Pool {
     int current_columns = 1;
     bool panel_valid = false, panel_active = false;
     int colp_rows() const { return 3 + 2 * colp_slots; }
-    ekf_status free_panel() {
-        if (colp) HIPC(hipFree(colp));
-        if (lmslot) HIPC(hipFree(lmslot));
-        if (plan_list) HIPC(hipFree(plan_list));
-        if (uvc) HIPC(hipFree(uvc));
-        if (cur) HIPC(hipFree(cur));
-        for (int q = 0; q < 2; q++) if (curv[q]) HIPC(hipFree(curv[q]));
-        for (int q = 0; q < 2; q++) if (apred[q]) HIPC(hipFree(apred[q]));
-        apred[0] = apred[1] = nullptr;
-        colp = nullptr; lmslot = nullptr; plan_list = nullptr; uvc = nullptr; cur = nullptr; curv[0] = curv[1] = nullptr;
+    void free_panel() {   // (the stream is idle)
+        for (double** p : {&colp, &cur, &apred[0], &apred[1]}) mem.free(p);
+        for (int** p : {&plan_list, &curv[0], &curv[1]}) mem.free(p);
+        mem.free(&lmslot);
+        mem.free(&uvc);
         colp_slots = 0;
         panel_valid = panel_active = false;
-        return EKF_OK;
     }
-    ekf_status ensure_panel(bool* fresh) {   // *fresh: the buffers were (re)created -- whatever panel was valid is gone
+    // *fresh: the buffers were (re)created -- whatever panel was valid is gone.  One group: after a failure there is no
+    // panel, never a half-built one
+    ekf_status ensure_panel(bool* fresh) {
         int want = column_panel == 2 ? 1 : pend_cap / 2;
         if (want > 64) want = 64;
         if (want < 1) want = 1;
@@ -329,26 +347,18 @@ struct Pool {
         if (colp && colp_slots == want) return EKF_OK;
         *fresh = true;
         HIPC(hipStreamSynchronize(stream));
-        EKFC(free_panel());
+        free_panel();
+        const size_t B = pv.B, rows = 3 + 2 * want, nv = B * (1 + want);
+        EKFC(mem.replace_group({target(&colp, B * rows * pv.ld, Fill::kZero),                // (pad entries of the rows stay 0)
+                                target(&lmslot, B * (pv.n > 0 ? pv.n : 1), Fill::kOnes),   // -1: no landmark has a slot
+                                target(&plan_list, B * want, Fill::kOnes),
+                                target(&uvc, B * rows * pend_cap),
+                                target(&cur, B * (6 + 4 * want) * pv.ld, Fill::kZero),     // (pad entries of the rows stay 0)
+                                target(&curv[0], nv, Fill::kOnes), target(&curv[1], nv, Fill::kOnes),   // -1: nothing kept
+                                target(&apred[0], B * 2, Fill::kZero), target(&apred[1], B * 2, Fill::kZero)},
+                               "ensure_panel", "the column panel"));
         colp_slots = want;
-        const size_t np = (size_t)pv.B * colp_rows() * pv.ld, nl = (size_t)pv.B * (pv.n > 0 ? pv.n : 1), nq = (size_t)pv.B * want;
-        HIPC(hipMalloc((void**)&colp, np * sizeof(double)));
-        HIPC(hipMalloc((void**)&lmslot, nl * sizeof(short)));
-        HIPC(hipMalloc((void**)&plan_list, nq * sizeof(int)));
-        HIPC(hipMalloc((void**)&uvc, (size_t)pv.B * colp_rows() * pend_cap * sizeof(ekf::double2_t)));
-        const size_t nc = (size_t)pv.B * (6 + 4 * want) * pv.ld, nv = (size_t)pv.B * (1 + want);
-        HIPC(hipMalloc((void**)&cur, nc * sizeof(double)));
-        HIPC(hipMemsetAsync(cur, 0, nc * sizeof(double), stream));        // (pad entries of the rows stay 0)
-        for (int q = 0; q < 2; q++) {
-            HIPC(hipMalloc((void**)&curv[q], nv * sizeof(int)));
-            HIPC(hipMemsetAsync(curv[q], 0xFF, nv * sizeof(int), stream));   // -1: nothing kept
-            HIPC(hipMalloc((void**)&apred[q], (size_t)pv.B * 2 * sizeof(double)));
-            HIPC(hipMemsetAsync(apred[q], 0, (size_t)pv.B * 2 * sizeof(double), stream));
-        }
         curv_sel = 0;
-        HIPC(hipMemsetAsync(colp, 0, np * sizeof(double), stream));       // (pad entries of the rows stay 0)
-        HIPC(hipMemsetAsync(lmslot, 0xFF, nl * sizeof(short), stream));   // -1: no landmark has a slot
-        HIPC(hipMemsetAsync(plan_list, 0xFF, nq * sizeof(int), stream));
         return EKF_OK;
     }
 
@@ -357,18 +367,17 @@ struct Pool {
         EKFC(flush());
         pend_symmetric = symmetric_gather ? 1 : 0;
         HIPC(hipStreamSynchronize(stream));
-        for (double** p : {&Uf, &Vf, &state_alt})
-            if (*p) { HIPC(hipFree(*p)); *p = nullptr; }
-        EKFC(free_panel());
+        free_panel();
         pend_cap = 0;
-        if (max_pending_corrections <= 0) return EKF_OK;
+        if (max_pending_corrections <= 0) {
+            for (double** p : {&Uf, &Vf, &state_alt}) mem.free(p);
+            return EKF_OK;
+        }
         int cap = 2 * max_pending_corrections;
         if (cap > ekf::max_pending()) cap = ekf::max_pending();
         const size_t cnt = (size_t)pv.B * cap * pv.ld;
-        HIPC(hipMalloc((void**)&Uf, cnt * sizeof(double)));
-        HIPC(hipMalloc((void**)&Vf, cnt * sizeof(double)));
-        HIPC(hipMalloc((void**)&state_alt, (size_t)pv.B * pv.ld * sizeof(double)));
-        HIPC(hipMemsetAsync(state_alt, 0, (size_t)pv.B * pv.ld * sizeof(double), stream));
+        EKFC(mem.replace_group({target(&Uf, cnt), target(&Vf, cnt), target(&state_alt, (size_t)pv.B * pv.ld, Fill::kZero)},
+                               "set_update_mode", "the pending factors"));
         pend_cap = cap;
         return EKF_OK;
     }
@@ -483,26 +492,15 @@ struct Pool {
     }
 
     template <class Tp>
-    ekf_status dalloc(Tp** p, size_t count) {
-        HIPC(hipMalloc((void**)p, count * sizeof(Tp)));
-        dev_bytes += count * sizeof(Tp);
-        return EKF_OK;
-    }
+    ekf_status dalloc(Tp** p, size_t count, Fill fill = Fill::kNone) { return mem.alloc(p, count, fill, "Pool", "a pool buffer"); }
 
     ekf_status create(int B, int n, const ekf_params* params, int dev) {
         if (B <= 0 || n < 0) return fail(EKF_ERR_INVALID, "B must be > 0 and n >= 0");
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(EKF_ERR_NO_DEVICE, "no HIP device visible: libekfslam_hip has no CPU path");
-        if (dev < 0) HIPC(hipGetDevice(&dev));
-        if (dev >= count) return fail(EKF_ERR_INVALID, "device index out of range");
-        hipDeviceProp_t prop;
-        HIPC(hipGetDeviceProperties(&prop, dev));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(EKF_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+        EKFC(select_device(&dev, true));
         device = dev;
         EKFC(use());
         HIPC(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        mem.stream = stream;
         ekf_params p;
         ekf_default_params(&p);
         if (params) p = *params;
@@ -530,7 +528,7 @@ struct Pool {
         HIPC(hipHostMalloc((void**)&err_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
         *err_host = 0u;
         pv.err = err_host;   // (unified addressing: the mapped pointer is valid on the device)
-        HIPC(hipMalloc((void**)&pv.queue, 64));   // (the resident streaming kernels' tile queue: one word, zeroed per launch)
+        EKFC(dalloc(&pv.queue, 64 / sizeof(*pv.queue)));   // (the resident streaming kernels' tile queue: one word, zeroed per launch)
         return reset();
     }
 
@@ -551,15 +549,7 @@ struct Pool {
     void destroy() {
         if (device >= 0) (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        if (assoc_block) { pv.assoc = nullptr; assoc_alt = nullptr; assoc_out_dev = nullptr; }   // (parts of the block)
-        void* ptrs[] = {pv.sigma, pv.state, pv.Kg, pv.Gh, pv.snap, pv.rec, pv.assoc, pv.touch_flag, pv.touch_list,
-                        pv.touch_count, scores, meas_dev, assoc_block,
-                        assoc_out_dev, sensor_dev, digest_dev, poses_dev, log_twist, log_lm, log_z, log_init,
-                        Uf, Vf, state_alt, assoc_alt, terms, log_truth, ulog_twist, ulog_count, ulog_meas, ulog_assoc, ulog_truth, corr_counter,
-                        phase_trace, terms2, scores2, blk_cache, cf_U, cf_V, cf_cnt, cf_state, call_in, cf_pred,
-                        colp, lmslot, plan_list, uvc, spec, specw, cur, curv[0], curv[1], apred[0], apred[1], pv.queue};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
+        mem.free_all();
         stage_in.release();
         stage_out.release();
         if (pub_host) (void)hipHostFree(pub_host);
@@ -681,40 +671,50 @@ struct Pool {
         pub_sent = true;
         return EKF_OK;
     }
+    // Everything new first, then the moves and ONE synchronisation, then the commit; the old buffers go last.  A failure
+    // leaves the old buffers, the old pointers and the old jcap in force.
     ekf_status ensure_meas_capacity(int J) {
         if (J <= jcap) return EKF_OK;
-        HIPC(hipStreamSynchronize(stream));
-        if (meas_dev) HIPC(hipFree(meas_dev));
-        meas_dev = nullptr;
         const int cap = J < 64 ? 64 : round_up(J, 64);
-        EKFC(dalloc(&meas_dev, (size_t)cap * 2));
-        if (pv.B == 1) {
-            char* blk = nullptr;
-            EKFC(dalloc(&blk, kAssocDecOff + sizeof(int) * (size_t)cap));
-            HIPC(hipMemsetAsync(blk, 0, kAssocDecOff, stream));
-            // the records move in (the current one first); the old homes are released
+        double* meas = nullptr;
+        char *blk = nullptr, *pub = nullptr;
+        int* dec = nullptr;
+        auto fresh = [&]() -> ekf_status {
+            EKFC(dalloc(&meas, (size_t)cap * 2));
+            if (pv.B > 1) return dalloc(&dec, (size_t)cap);
+            EKFC(dalloc(&blk, kAssocDecOff + sizeof(int) * (size_t)cap, Fill::kZero));
+            HIPC(hipHostMalloc((void**)&pub, kAssocDecOff + sizeof(int) * (size_t)cap,
+                               hipHostMallocMapped | hipHostMallocCoherent));   // (the host spins on it: fine-grained)
+            std::memset(pub, 0, kAssocDecOff);
+            // the records move in (the current one first)
             HIPC(hipMemcpyAsync(blk, pv.assoc, sizeof(ekf::AssocRec), hipMemcpyDeviceToDevice, stream));
             if (assoc_alt) HIPC(hipMemcpyAsync(blk + kAssocRecSlot, assoc_alt, sizeof(ekf::AssocRec), hipMemcpyDeviceToDevice, stream));
-            HIPC(hipStreamSynchronize(stream));
-            if (assoc_block) HIPC(hipFree(assoc_block));
-            else {
-                HIPC(hipFree(pv.assoc));
-                if (assoc_alt) HIPC(hipFree(assoc_alt));
-            }
+            return EKF_OK;
+        };
+        ekf_status st = fresh();
+        const hipError_t e = hipStreamSynchronize(stream);
+        if (st == EKF_OK && e != hipSuccess) st = fail(EKF_ERR_HIP, std::string("ensure_meas_capacity: ") + hipGetErrorString(e));
+        if (st != EKF_OK) {
+            mem.free(&meas); mem.free(&blk); mem.free(&dec);
+            if (pub) (void)hipHostFree(pub);
+            HipMem::clear_error();
+            return st;
+        }
+        mem.free(&meas_dev);
+        meas_dev = meas;
+        if (pv.B == 1) {
+            if (assoc_block) mem.free(&assoc_block);   // (the records were parts of it)
+            else { mem.free(&pv.assoc); mem.free(&assoc_alt); }
+            if (pub_host) (void)hipHostFree(pub_host);
             assoc_block = blk;
-            if (pub_host) HIPC(hipHostFree(pub_host));
-            pub_host = nullptr;
-            HIPC(hipHostMalloc((void**)&pub_host, kAssocDecOff + sizeof(int) * (size_t)cap,
-                               hipHostMallocMapped | hipHostMallocCoherent));   // (the host spins on it: fine-grained)
-            std::memset(pub_host, 0, kAssocDecOff);
+            pub_host = pub;
             pv.assoc = reinterpret_cast<ekf::AssocRec*>(blk);
             assoc_alt = reinterpret_cast<ekf::AssocRec*>(blk + kAssocRecSlot);
-            assoc_out_dev = reinterpret_cast<int*>(blk + kAssocDecOff);
+            dec = reinterpret_cast<int*>(blk + kAssocDecOff);
         } else {
-            if (assoc_out_dev) HIPC(hipFree(assoc_out_dev));
-            assoc_out_dev = nullptr;
-            EKFC(dalloc(&assoc_out_dev, (size_t)cap));
+            mem.free(&assoc_out_dev);
         }
+        assoc_out_dev = dec;
         jcap = cap;
         return EKF_OK;
     }
@@ -736,20 +736,18 @@ inline ekf_status checked_launch() {
 
 inline ekf_status free_log(Pool& P) {
     HIPC(hipStreamSynchronize(P.stream));
-    for (void* p : {(void*)P.log_twist, (void*)P.log_lm, (void*)P.log_z, (void*)P.log_init, (void*)P.log_truth})
-        if (p) HIPC(hipFree(p));
-    P.log_twist = nullptr; P.log_lm = nullptr; P.log_z = nullptr; P.log_init = nullptr; P.log_truth = nullptr;
-    P.T = 0; P.vmax = 0; P.log_bytes = 0;
+    for (double** p : {&P.log_twist, &P.log_z, &P.log_init, &P.log_truth}) P.mem.free(p);
+    P.mem.free(&P.log_lm);
+    P.T = 0; P.vmax = 0;
     return EKF_OK;
 }
 
 inline ekf_status free_ulog(Pool& P) {
     HIPC(hipStreamSynchronize(P.stream));
-    for (void* p : {(void*)P.ulog_twist, (void*)P.ulog_count, (void*)P.ulog_meas, (void*)P.ulog_assoc, (void*)P.ulog_truth})
-        if (p) HIPC(hipFree(p));
-    P.ulog_twist = nullptr; P.ulog_count = nullptr; P.ulog_meas = nullptr; P.ulog_assoc = nullptr; P.ulog_truth = nullptr;
+    for (double** p : {&P.ulog_twist, &P.ulog_meas, &P.ulog_truth}) P.mem.free(p);
+    for (int** p : {&P.ulog_count, &P.ulog_assoc}) P.mem.free(p);
     P.truth_is_unknown_log = 0;
-    P.uT = 0; P.ujmax = 0; P.ulog_bytes = 0;
+    P.uT = 0; P.ujmax = 0;
     P.ucount_host.clear();
     return EKF_OK;
 }

@@ -212,6 +212,8 @@ ekf_status ekf_phase_trace(ekf_handle h, int enable, long long* out);
 ekf_status ekf_test_raise_device_error(ekf_handle h);
 /* Blocks until every kernel queued on the handle's stream has finished. */
 ekf_status ekf_sync(ekf_handle h);
+/* Device bytes the filter holds: the exact sum of its live device allocations (as ekf_batch_device_bytes). */
+ekf_status ekf_device_bytes(ekf_handle h, size_t* bytes);
 /* Measurement hook (off by default): brackets every covariance-streaming launch (class 0: fused correction, rank-2
  * stream, decision + correction) and every Mahalanobis scoring launch (class 1) of this filter with HIP events on
  * its stream.  ekf_get_profile synchronises and returns the summed kernel milliseconds and launch counts per class
@@ -247,7 +249,8 @@ ekf_status ekf_batch_create(int B, int n, const ekf_params* params, int device, 
 ekf_status ekf_batch_destroy(ekf_batch_handle hb);
 /* Re-initialise every filter to the constructor state (ekf_slam.cpp:27-53). */
 ekf_status ekf_batch_reset(ekf_batch_handle hb);
-/* Device bytes the batch holds (covariance pool + state + scratch + uploaded log). */
+/* Device bytes the batch holds (covariance pool + state + scratch + uploaded log): the exact sum of its live device
+ * allocations, the delayed mode's factor store and column panel included. */
 ekf_status ekf_batch_device_bytes(ekf_batch_handle hb, size_t* bytes);
 ekf_status ekf_batch_upload_known_log(ekf_batch_handle hb, const ekf_known_log* log);
 /* Runs steps [t_begin, t_end) of the uploaded log for all filters on the batch's stream and

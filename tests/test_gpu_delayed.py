@@ -485,3 +485,31 @@ def test_column_panel_at_the_million_steps_configuration(hip):
     for a, b in zip(res[2][3], res[1][3]):
         assert np.abs(a - b).max() < 1e-10
     assert np.abs(res[2][4] - res[1][4]).max() / np.abs(res[1][4]).max() < 1e-10
+
+
+def test_column_panel_is_rebuilt_inside_one_handle(hip):
+    """set_update_mode(8) then set_update_mode(16) on the SAME pool: the panel's slot count changes (8 -> 16 plan slots), so
+    its buffers are released and rebuilt as one group between the two runs.  Each run of the log is compared with the eager
+    run of another pool at this file's delayed-against-eager tolerance (1e-11, test_batch_delayed_equals_eager); N = 257,
+    the smallest dimension the panel takes."""
+    B, n, T = 2, 127, 6
+    cfg = synth.SimConfig(n=n, steps=T, filters=B, seed=4227, half_extent=3.0, min_spacing=0.1, max_visible_dis=1e9,
+                          vmax=2, v_cmd=0.8, w_cmd=0.5)
+    log = synth.make_known_log(cfg)
+    eager = hip.BatchEKF(B, n)
+    eager.upload_known_log(log.twist, log.lm_idx, log.z_xy, log.init_xy)
+    eager.run_known()
+    ref = [(eager.state(b), eager.cov(b)) for b in range(B)]
+    eager.close()
+    bt = hip.BatchEKF(B, n)
+    bt.upload_known_log(log.twist, log.lm_idx, log.z_xy, log.init_xy)
+    for k in (8, 16):
+        bt.reset()
+        bt.set_update_mode(k)
+        bt.run_known(0, 3)     # (two runs: the first one's closing flush hands the panel to the second)
+        before = bt.form_counts()["gain_from_panel"]
+        bt.run_known(3, T)
+        assert bt.form_counts()["gain_from_panel"] > before, k   # the rebuilt panel was read
+        for b in range(B):
+            assert_parity(bt.state(b), bt.cov(b), ref[b][0], ref[b][1], 1e-11, f"k={k} filter {b} vs eager")
+    bt.close()
