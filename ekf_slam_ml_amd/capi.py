@@ -56,6 +56,8 @@ SYMBOLS = [
     "ekf_dense64_predict_landmarks", "ekf_dense64_measure_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
+    "ekf_dense64_region_begin", "ekf_dense64_region_end", "ekf_dense64_region_info", "ekf_dense64_region_launch_info",
+    "ekf_dense64_get_padded",
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
@@ -93,6 +95,12 @@ class HealthReport(C.Structure):
     _fields_ = [("n_nonfinite", C.c_longlong), ("n_asym", C.c_longlong), ("n_diag_bad", C.c_longlong),
                 ("n_minor", C.c_longlong), ("max_asym", C.c_double), ("min_diag", C.c_double),
                 ("asym_i", C.c_int), ("asym_j", C.c_int), ("min_diag_i", C.c_int), ("reserved", C.c_int)]
+
+
+class RegionReport(C.Structure):
+    """ekf_dense64_region_report (include/ekfslam.h)"""
+    _fields_ = [("Na", C.c_int), ("Nb", C.c_int), ("corrections", C.c_longlong), ("row_maps", C.c_longlong),
+                ("group_bytes", C.c_longlong)]
 
 
 class FactorReport(C.Structure):
@@ -258,6 +266,11 @@ def load():
         "ekf_dense64_set_live": [h, C.c_int],
         "ekf_dense64_get_live": [h, _ip],
         "ekf_dense64_coupling": [h, C.c_int, C.POINTER(C.c_longlong), _dp, _dp],
+        "ekf_dense64_get_padded": [h, _dp, _dp],
+        "ekf_dense64_region_begin": [h, C.c_int, _dp],
+        "ekf_dense64_region_end": [h, C.POINTER(RegionReport), _dp],
+        "ekf_dense64_region_info": [h, _ip, _ip] + [C.POINTER(C.c_longlong)] * 3,
+        "ekf_dense64_region_launch_info": [h, C.c_int] + [_ip] * 7 + [C.POINTER(C.c_longlong)],
         "ekf_dense64_pairs_launch_info": [h, _ip, _ip],
         "ekf_dense64_score_landmark_pairs": [h, C.c_int, C.c_double, C.c_double, _ip, _dp, C.POINTER(C.c_longlong),
                                              C.POINTER(C.c_longlong), _dp],
@@ -1044,6 +1057,55 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_coupling(self._h, int(Na), C.byref(count), C.byref(most), C.byref(ms)))
         return count.value, most.value, ms.value
 
+    def region_begin(self, Na):
+        """opens a local region A = [0, Na), 3 <= Na < N: until region_end() the structured calls run at live = Na, bit for
+        bit as with live = Na, and the handle accumulates what the rest of the map owes -- exact for a COUPLED tail
+        (include/ekfslam.h, ekf_dense64_region_begin).  Any call outside a region's terms ends it first.  Returns
+        elapsed_ms"""
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_region_begin(self._h, int(Na), C.byref(ms)))
+        return ms.value
+
+    def region_end(self):
+        """the global update: x_b, Sigma_bb (one MFMA product), Sigma_ba, Sigma_ab; the live dimension goes back to what
+        region_begin() found.  Returns {Na, Nb, corrections, row_maps, group_bytes, elapsed_ms}"""
+        rep, ms = RegionReport(), C.c_double()
+        _check(self._lib.ekf_dense64_region_end(self._h, C.byref(rep), C.byref(ms)))
+        out = {name: getattr(rep, name) for name, _ in RegionReport._fields_}
+        out["elapsed_ms"] = ms.value
+        return out
+
+    def region_info(self):
+        """{active, Na (0 without a region), corrections, row_maps (of the open region or the last one),
+        ended_by_other_call (regions of this handle that a call outside their terms ended)}"""
+        active, na = C.c_int(), C.c_int()
+        corr, maps, ended = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        _check(self._lib.ekf_dense64_region_info(self._h, C.byref(active), C.byref(na), C.byref(corr), C.byref(maps),
+                                                 C.byref(ended)))
+        return {"active": bool(active.value), "Na": na.value, "corrections": corr.value, "row_maps": maps.value,
+                "ended_by_other_call": ended.value}
+
+    def region_launch_info(self, Na):
+        """the plan of a region of Na states: {tile_rows, tile_cols, threads, pitch, update_tiles, gemm_tiles, gemm_k,
+        group_bytes}"""
+        v = [C.c_int() for _ in range(7)]
+        b = C.c_longlong()
+        _check(self._lib.ekf_dense64_region_launch_info(self._h, int(Na), *[C.byref(x) for x in v], C.byref(b)))
+        names = ("tile_rows", "tile_cols", "threads", "pitch", "update_tiles", "gemm_tiles", "gemm_k")
+        return {**{k: x.value for k, x in zip(names, v)}, "group_bytes": b.value}
+
+    def padded(self):
+        """test hook: (Sigma (ld, ld), state (ld,)) as they sit in memory, padding included; flushes, and ends a region"""
+        ld = self.launch_info()["ld"]
+        S, x = np.empty((ld, ld)), np.empty(ld)
+        _check(self._lib.ekf_dense64_get_padded(self._h, S.ctypes.data_as(_dp), x.ctypes.data_as(_dp)))
+        return S, x
+
+    def region(self, Na):
+        """context manager: region_begin(Na) ... region_end(); the report of the end is the manager's .report (None when a
+        call inside the block ended the region first)"""
+        return _Region(self, Na)
+
     @staticmethod
     def _r_merge(r_merge):
         r_merge = float(r_merge)
@@ -1660,6 +1722,22 @@ class DensePropagator64(_DensePropagatorBase):
         return self._launch_info()
 
 
+class _Region:
+    """DensePropagator64.region(Na)"""
+
+    def __init__(self, handle, Na):
+        self._d, self._Na, self.report = handle, int(Na), None
+
+    def __enter__(self):
+        self._d.region_begin(self._Na)
+        return self
+
+    def __exit__(self, *exc):
+        if self._d.region_info()["active"]:
+            self.report = self._d.region_end()
+        return False
+
+
 class DenseEKFSLAM:
     """rigid2d::EKF_SLAM (ekf_slam.hpp:19-57) on one DensePropagator64 handle: the reference's three methods, each one call
     into the library, the state never leaving the device.  n landmarks in a handle with room for `capacity` (default n).
@@ -1741,6 +1819,16 @@ class DenseEKFSLAM:
             self._known = e.known
             raise
         return centres, assoc
+
+    def local_region(self, n_local):
+        """context manager: a local region over the pose and the first n_local landmarks (3 + 2 n_local states).  While it
+        is open prediction() and the handle's structured calls on those landmarks (handle.correct_sparse(),
+        handle.score_landmarks(), handle.measure_landmarks() with n_lm = n_local, ...) cost what a map of n_local
+        landmarks costs, and the rest of the map is paid once at the end -- exact for a surveyed (coupled) map.
+        measurement() addresses all n landmarks and therefore ends the region; data_association() is refused while
+        known landmarks lie beyond it.  The caller brings
+        the landmarks it sees into the prefix with handle.swap_blocks() first."""
+        return self.handle.region(3 + 2 * int(n_local))
 
     def find_duplicates(self, gate, r_merge):
         """the pairs (a, b), a < b, of known landmarks that are each other's nearest partner with d2 < gate, in ascending

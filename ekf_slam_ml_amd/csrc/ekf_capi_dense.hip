@@ -136,6 +136,7 @@ ekf_status ekf_dense64_create(int N, int device, ekf_dense64_handle* out) {
 }
 ekf_status ekf_dense64_destroy(ekf_dense64_handle d) { return dense_destroy(d); }
 ekf_status ekf_dense64_set(ekf_dense64_handle d, const double* F, const double* Sigma, const double* Q) {
+    if (d) d->leave_region();   // outside a region's terms: it ends first
     return dense_set(d, F, Sigma, Q);
 }
 ekf_status ekf_dense64_propagate(ekf_dense64_handle d, int iterations, double* elapsed_ms) {

@@ -25,6 +25,7 @@ ekf_status ekf_dense64_s::created() {
     HIPC(ekf::dense64_sparse_prepare());
     HIPC(ekf::dense64_joseph_prepare());
     HIPC(ekf::dense64_init_prepare());
+    HIPC(ekf::dense64_region_prepare());
     live = N;
     pl_full = pl_live = ekf::dense64_correct_plan(N, ld);
     const char *fn = "ekf_dense64_create", *what = "the operand buffers";
@@ -86,6 +87,7 @@ void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool h
     const double* dnu = have_nu ? in.nu : nullptr;
     if (!deferred || d->pend_rows + m > kMaxP) d->flush_pending();   // deferred: only when there is no room for m more rows
     const PendView p = d->panels();
+    const int p0 = d->pend_rows;   // (behind the flush) where a deferred call leaves its rows of K^T
     if (joseph != Joseph::kNo)
         ekf::launch_dense64_correct_sparse_joseph(
             d->pl_live, d->S, d->x, d->workspace(), in.cols, in.Hc, in.R, dnu,
@@ -97,6 +99,11 @@ void correct_sparse_launch(ekf_dense64_s* d, bool deferred, int m, int s, bool h
     else
         ekf::launch_dense64_correct_sparse(d->pl_live, d->S, d->x, d->workspace(), in.cols, in.Hc, in.R, dnu, m, s, out.nis,
                                            out.verdict, d->stream);
+    if (d->region_on)   // the accumulators take the gain, S^-1 and nu the live call used (no Joseph form inside a region)
+        ekf::launch_dense64_region_correct(d->region_pl, d->region_mem.acc,
+                                           deferred ? p.K + (size_t)p0 * d->ld : d->workspace() + d->pl_live.off_Kt, d->ld,
+                                           d->workspace() + d->pl_live.off_Sinv, in.cols, in.Hc, dnu, m, s, out.verdict,
+                                           d->stream);
 }
 
 // the one synchronisation of a correction, its verdict, the count of the pending rows
@@ -110,6 +117,7 @@ ekf_status correct_sparse_finish(ekf_dense64_s* d, const char* fn, bool deferred
                                        (deferred ? "state, Sigma and the pending rows are unchanged"
                                                  : "state and Sigma are unchanged"));
     if (deferred) d->pend_rows += m;
+    if (d->region_on) d->region_corrections++;
     if (nis_out) *nis_out = nis;
     return EKF_OK;
 }
@@ -145,6 +153,7 @@ ekf_status dense64_correct_sparse_joseph(ekf_dense64_s* d, int m, int s, const i
                                          double* elapsed_ms) {
     const std::string fn = "ekf_dense64_correct_sparse_joseph";
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!cols || !Hc || !R || m < 1 || m > kJosephMaxM || m > d->live || s < 1 || s > kMaxS || s > d->live || (nis_out && !nu))
         return fail(EKF_ERR_INVALID, fn + ": bad argument (1 <= m <= 32)");
     if (!index_lists_ok(d->host_stamp, d->live, 1, s, cols))
@@ -208,12 +217,14 @@ void init_block_launch(ekf_dense64_s* d, int first, int r, int s, const double* 
         ekf::launch_dense64_panel_map(p.K, p.T, d->pend_rows, in.G, s > 0 ? in.cols : nullptr, d->ld, first, r, s, d->stream);
     });
     ekf::launch_dense64_init(d->S, d->x, in.cols, in.G, W, xb, d->live, d->ld, first, r, s, d->stream);
+    d->region_row_map(in.G, s > 0 ? in.cols : nullptr, first, r, s);
 }
 
 ekf_status dense64_state_block(const char* name, ekf_dense64_s* d, int first, int count, double* out, const double* x) {
     if (!d) return fail(EKF_ERR_INVALID, std::string(name) + ": null handle");
     if ((!out && !x) || count < 1 || first < 0 || count > d->N || first > d->N - count)
         return fail(EKF_ERR_INVALID, std::string(name) + ": bad argument");
+    if (first + count > d->live) d->leave_region();   // (live < N inside a region: the block reaches beyond it)
     HIPC(hipSetDevice(d->device));
     if (out) HIPC(hipMemcpyAsync(out, d->x + first, sizeof(double) * count, hipMemcpyDeviceToHost, d->stream));
     else HIPC(hipMemcpyAsync(d->x + first, x, sizeof(double) * count, hipMemcpyHostToDevice, d->stream));
@@ -252,6 +263,7 @@ ekf_status scan_fit(ekf_dense64_s* d, const char* fn, const double* ranges, int 
     HIPC(hipMemcpyAsync(v.ranges, sg.host, sizeof(double) * n_beams, hipMemcpyHostToDevice, d->stream));
     EKFC(sg.mark(d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
     ekf::launch_dense64_scan_circles(v.ranges, n_beams, max_out, v.head, v.centres, v.radii, v.all, d->stream);
     char* host = reinterpret_cast<char*>(d->scan_rec.data());
     EKFC(finish_timed(d, elapsed_ms, {{host, v.head, l.record_bytes},
@@ -318,6 +330,7 @@ ekf_status associate_readings(ekf_dense64_s* d, const char* fnc, const ekf::Para
         SpsView v{};
         if (k > 0) v = view(d->sps.p, L::sps_layout(k, 2, 5, true, false), false);   // (k <= n_max: inside the buffer)
         HIPC(hipEventRecord(d->e0, d->stream));
+        d->finish_leave();   // (a region that is being left ends here)
         if (k > 0) {
             ekf::launch_dense64_lm_terms(d->x, d->x, sx, sy, 0, k, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu, d->stream);
             score_sparse_launch(d, v, k, 2, 5, true, true, true);
@@ -414,6 +427,7 @@ ekf_status associate_joint(ekf_dense64_s* d, const char* fnc, const ekf::Params&
     const int k = *known;
     HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
     if (k > 0)
         // (cut as for the full map, whatever is known: the launches stay inside the buffer reserved for it)
         score_readings_launch(d, p, jv, J, 0, k, joint_chunk(J, n_max), true, [&](int j0, int nr, const SpsView& v) {
@@ -484,14 +498,18 @@ extern "C" {
 
 ekf_status ekf_dense64_set_state(ekf_dense64_handle d, const double* x) {
     if (!d || !x) return fail(EKF_ERR_INVALID, "ekf_dense64_set_state: null argument");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     HIPC(hipSetDevice(d->device));
+    d->finish_leave();   // (a region that is being left ends here)
     HIPC(hipMemcpyAsync(d->x, x, sizeof(double) * d->N, hipMemcpyHostToDevice, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
     return EKF_OK;
 }
 ekf_status ekf_dense64_get_state(ekf_dense64_handle d, double* out) {
     if (!d || !out) return fail(EKF_ERR_INVALID, "ekf_dense64_get_state: null argument");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     HIPC(hipSetDevice(d->device));
+    d->finish_leave();   // (a region that is being left ends here)
     HIPC(hipMemcpyAsync(out, d->x, sizeof(double) * d->N, hipMemcpyDeviceToHost, d->stream));
     HIPC(hipStreamSynchronize(d->stream));
     return EKF_OK;
@@ -509,6 +527,7 @@ ekf_status ekf_dense64_correct(ekf_dense64_handle d, int m, const double* H, con
                                double* nis_out, double* elapsed_ms) {
     if (!d || !H || !R || m < 1 || m > kMaxM || m > d->N || (nis_out && !nu))
         return fail(EKF_ERR_INVALID, "ekf_dense64_correct: bad argument");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     HIPC(hipSetDevice(d->device));
     const int N = d->N, ld = d->ld;
     const L::CorrInLayout l = L::corr_in_layout(ld);
@@ -549,6 +568,7 @@ ekf_status ekf_dense64_score(ekf_dense64_handle d, int J, int m, const double* H
     if (!d || !H || !R || J < 1 || m < 1 || m > kMaxM || m > d->N || (long long)J * m > kScoreRows ||
         (nis_out && !nu) || (!nis_out && !S_out && !flag_out))
         return fail(EKF_ERR_INVALID, "ekf_dense64_score: bad argument");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     HIPC(hipSetDevice(d->device));
     const int N = d->N, ld = d->ld;
     const ekf::Dense64ScorePlan sp = ekf::dense64_score_plan(N, ld, J, m);
@@ -602,6 +622,7 @@ ekf_status ekf_dense64_propagate_block(ekf_dense64_handle d, int first, int r, c
     });
     ekf::launch_dense64_block(d->S, d->x, in.Fr, Qr ? in.Qr : nullptr, dx ? in.dx : nullptr, d->live, d->ld, first, r,
                               d->stream);
+    d->region_row_map(in.Fr, nullptr, first, r, r);
     return finish_timed(d, elapsed_ms);
 }
 
@@ -713,6 +734,7 @@ ekf_status ekf_dense64_init_block(ekf_dense64_handle d, int first, int r, int s,
 // the handle carries them, and are applied first otherwise.
 ekf_status ekf_dense64_swap_blocks(ekf_dense64_handle d, int first_a, int first_b, int r, double* elapsed_ms) {
     if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (r < 1 || r > kMaxR || r > d->live || first_a < 0 || first_b < 0 || first_a > d->live - r || first_b > d->live - r)
         return fail(EKF_ERR_INVALID, "ekf_dense64_swap_blocks: bad argument (both blocks must lie inside the live dimension)");
     if (std::abs(first_a - first_b) < r)
@@ -738,6 +760,12 @@ ekf_status ekf_dense64_get_sigma_block(ekf_dense64_handle d, int nr, const int* 
     for (int c = 0; c < nc; c++)
         if (cols[c] < 0 || cols[c] >= d->N)
             return fail(EKF_ERR_INVALID, "ekf_dense64_get_sigma_block: every index of cols must lie in [0, N)");
+    if (d->region_on)
+        for (int e = 0; e < nr + nc; e++)
+            if ((e < nr ? rows[e] : cols[e - nr]) >= d->live) {   // an index beyond the region: it ends first
+                d->leave_region();
+                break;
+            }
     HIPC(hipSetDevice(d->device));
     const RdBufView rd = view(d->rd_buf, L::rd_buf_layout());
     HIPC(hipMemcpyAsync(rd.rows, rows, sizeof(int) * nr, hipMemcpyHostToDevice, d->stream));
@@ -762,7 +790,9 @@ ekf_status ekf_dense64_get_sigma_block(ekf_dense64_handle d, int nr, const int* 
 // first, at the old width.
 ekf_status ekf_dense64_set_live(ekf_dense64_handle d, int Na) {
     if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_set_live: null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (Na < 1 || Na > d->N) return fail(EKF_ERR_INVALID, "ekf_dense64_set_live: the live dimension must lie in [1, N]");
+    d->finish_leave();   // (a region that is being left ends here)
     if (Na == d->live) return EKF_OK;
     if (d->pend_rows > 0) {
         HIPC(hipSetDevice(d->device));
@@ -788,9 +818,89 @@ ekf_status ekf_dense64_get_live(ekf_dense64_handle d, int* Na) {
     return EKF_OK;
 }
 
+// ---- a local region (ekf_dense64_region.hip) ------------------------------------------------------------------------------
+// The accumulators and the scratch of the global update are one all-or-nothing group of the ledger, kept for the next
+// region that needs no more; the pending rows are applied at the old width, live becomes Na, Phi = I, Psi = 0, theta = 0.
+ekf_status ekf_dense64_region_begin(ekf_dense64_handle d, int Na, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_region_begin";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (d->region_on) return fail(EKF_ERR_STATE, std::string(fn) + ": a region is open already (ekf_dense64_region_end first)");
+    if (Na < ekf::kDense64RegionMinNa || Na >= d->N)
+        return fail(EKF_ERR_INVALID, std::string(fn) + ": the region must hold 3 <= Na < N states");
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64RegionPlan pl = ekf::dense64_region_plan(Na, d->N, d->ld);
+    EKFC(d->region_mem.reserve(d->mem, pl, fn));   // all or nothing; on a failure nothing has changed
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->flush_pending();   // at the old width
+    ekf::launch_dense64_region_reset(pl, d->region_mem.acc, d->stream);
+    EKFC(finish_timed(d, elapsed_ms));
+    d->region_pl = pl;
+    d->region_back = d->live;
+    d->live = Na;
+    d->pl_live = ekf::dense64_live_plan(d->pl_full, Na);
+    d->region_on = 1;
+    d->region_corrections = d->region_row_maps = 0;
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_region_end(ekf_dense64_handle d, ekf_dense64_region_report* report, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_region_end";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!d->region_on) return fail(EKF_ERR_STATE, std::string(fn) + ": no region is open");
+    HIPC(hipSetDevice(d->device));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->close_region();
+    if (report)
+        *report = ekf_dense64_region_report{d->region_pl.Na, d->region_pl.nb, d->region_corrections, d->region_row_maps,
+                                            (long long)d->region_mem.held};
+    return finish_timed(d, elapsed_ms);
+}
+
+ekf_status ekf_dense64_region_info(ekf_dense64_handle d, int* active, int* Na, long long* corrections, long long* row_maps,
+                                   long long* ended_by_other_call) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_region_info: null handle");
+    if (active) *active = d->region_on;
+    if (Na) *Na = d->region_on ? d->region_pl.Na : 0;
+    if (corrections) *corrections = d->region_corrections;
+    if (row_maps) *row_maps = d->region_row_maps;
+    if (ended_by_other_call) *ended_by_other_call = d->region_ended_by_other;
+    return EKF_OK;
+}
+
+// Test hook: the buffers as they sit in memory, padding included (which every kernel of the handle has to keep at +0).
+ekf_status ekf_dense64_get_padded(ekf_dense64_handle d, double* sigma_out, double* state_out) {
+    if (!d || (!sigma_out && !state_out)) return fail(EKF_ERR_INVALID, "ekf_dense64_get_padded: null argument");
+    HIPC(hipSetDevice(d->device));
+    d->sigma_needed();
+    HIPC(hipGetLastError());
+    if (sigma_out) HIPC(hipMemcpyAsync(sigma_out, d->S, sizeof(double) * d->ld * d->ld, hipMemcpyDeviceToHost, d->stream));
+    if (state_out) HIPC(hipMemcpyAsync(state_out, d->x, sizeof(double) * d->ld, hipMemcpyDeviceToHost, d->stream));
+    HIPC(hipStreamSynchronize(d->stream));
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_region_launch_info(ekf_dense64_handle d, int Na, int* tile_rows, int* tile_cols, int* threads,
+                                          int* pitch, int* update_tiles, int* gemm_tiles, int* gemm_k,
+                                          long long* group_bytes) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_region_launch_info: null handle");
+    if (Na < ekf::kDense64RegionMinNa || Na >= d->N)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_region_launch_info: 3 <= Na < N");
+    const ekf::Dense64RegionPlan pl = ekf::dense64_region_plan(Na, d->N, d->ld);
+    if (tile_rows) *tile_rows = ekf::kDense64RegionTileRows;
+    if (tile_cols) *tile_cols = ekf::kDense64RegionTileCols;
+    if (threads) *threads = ekf::kDense64RegionThreads;
+    if (pitch) *pitch = pl.pitch;
+    if (update_tiles) *update_tiles = pl.upd_tiles_r * pl.upd_tiles_c;
+    if (gemm_tiles) *gemm_tiles = pl.gemm_tiles * pl.gemm_tiles;
+    if (gemm_k) *gemm_k = pl.gemm_k;
+    if (group_bytes) *group_bytes = (long long)pl.group_bytes;
+    return EKF_OK;
+}
+
 // One streaming launch over the two rectangles; the two result words sit where a correction's nis and verdict do.
 ekf_status ekf_dense64_coupling(ekf_dense64_handle d, int Na, long long* nonzero, double* max_abs, double* elapsed_ms) {
     if (!d || !nonzero) return fail(EKF_ERR_INVALID, "ekf_dense64_coupling: null argument");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (Na < 1 || Na > d->N) return fail(EKF_ERR_INVALID, "ekf_dense64_coupling: Na must lie in [1, N]");
     HIPC(hipSetDevice(d->device));
     static_assert(sizeof(unsigned long long) == sizeof(double), "two words in corr_out");
@@ -827,6 +937,7 @@ ekf_status health_reserve(ekf_dense64_s* d, const char* fn, ekf::Dense64HealthPl
 ekf_status ekf_dense64_health(ekf_dense64_handle d, ekf_dense64_health_report* out, double* elapsed_ms) {
     const char* fn = "ekf_dense64_health";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null report");
     HIPC(hipSetDevice(d->device));
     ekf::Dense64HealthPlan pl;
@@ -854,6 +965,7 @@ ekf_status ekf_dense64_health(ekf_dense64_handle d, ekf_dense64_health_report* o
 ekf_status ekf_dense64_symmetrize(ekf_dense64_handle d, long long* n_changed, double* max_asym, double* elapsed_ms) {
     const char* fn = "ekf_dense64_symmetrize";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     HIPC(hipSetDevice(d->device));
     ekf::Dense64HealthPlan pl;
     EKFC(health_reserve(d, fn, &pl));
@@ -880,6 +992,7 @@ ekf_status ekf_dense64_factor_launch_info(ekf_dense64_handle d, int* block, int*
 ekf_status ekf_dense64_factor(ekf_dense64_handle d, ekf_dense64_factor_report* out, double* elapsed_ms) {
     const char* fn = "ekf_dense64_factor";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null report");
     HIPC(hipSetDevice(d->device));
     const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->live);
@@ -1001,6 +1114,7 @@ bool is_identity(const double* G) {
 ekf_status ekf_dense64_map_congruence(ekf_dense64_handle d, const double* G, const double* C, double* elapsed_ms) {
     const char* fn = "ekf_dense64_map_congruence";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!G) return fail(EKF_ERR_INVALID, std::string(fn) + ": null G");
     ekf::Dense64FramePlan pl;
     EKFC(frame_reserve(d, fn, &pl));
@@ -1018,6 +1132,7 @@ ekf_status ekf_dense64_reframe_landmarks(ekf_dense64_handle d, int mode, double 
                                          double* elapsed_ms) {
     const char* fn = "ekf_dense64_reframe_landmarks";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (mode != EKF_DENSE64_FRAME_FIXED && mode != EKF_DENSE64_FRAME_ROBOT)
         return fail(EKF_ERR_INVALID, std::string(fn) + ": mode is EKF_DENSE64_FRAME_FIXED or EKF_DENSE64_FRAME_ROBOT");
     const bool robot = mode == EKF_DENSE64_FRAME_ROBOT;
@@ -1050,6 +1165,7 @@ ekf_status ekf_dense64_score_landmark_pairs(ekf_dense64_handle d, int n_lm, doub
                                             double* d2, long long* n_below, long long* n_flagged, double* elapsed_ms) {
     const char* fn = "ekf_dense64_score_landmark_pairs";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!nearest && !d2) return fail(EKF_ERR_INVALID, std::string(fn) + ": nearest and d2 are both NULL");
     if (n_lm < 1 || 3 + 2 * (long long)n_lm > d->live)
         return fail(EKF_ERR_INVALID, std::string(fn) + ": the n_lm >= 1 landmarks must lie inside the live dimension");
@@ -1079,6 +1195,7 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     const char* fnc = "ekf_dense64_merge_landmarks";
     const std::string fn = fnc;
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!known) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (*known < 0 || 3 + 2 * (long long)*known > d->live)
         return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
@@ -1097,6 +1214,7 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     double* pms = elapsed_ms ? &ms : nullptr;
     auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
     HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
     ekf::launch_dense64_pair_terms(d->x, lo, hi, r_merge, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
     correct_sparse_launch(d, deferred, 2, 4, true, lm_joseph((unsigned)flags));
     EKFC(leg(correct_sparse_finish(d, fnc, deferred, 2, d2_out, pms)));   // singular: nothing was written, *known stands
@@ -1146,6 +1264,7 @@ ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_param
     const char* fnc = "ekf_dense64_associate_landmarks";
     const std::string fn = fnc;
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving((flags & EKF_DENSE64_LM_JOSEPH) ? d : nullptr);   // the Joseph form is outside a region's terms
     if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (J < 1) return fail(EKF_ERR_INVALID, fn + ": J must be at least 1");
     EKFC(associate_checks(d, fn, n_max, known, flags,
@@ -1192,6 +1311,7 @@ ekf_status ekf_dense64_associate_scan(ekf_dense64_handle d, const ekf_params* pa
     const char* fnc = "ekf_dense64_associate_scan";
     const std::string fn = fnc;
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kScanClusters)
         return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 128]");
@@ -1224,6 +1344,7 @@ ekf_status ekf_dense64_score_readings(ekf_dense64_handle d, const ekf_params* pa
                                       int first_lm, int count, double* nis_out, int* flag_out, double* elapsed_ms) {
     const char* fnc = "ekf_dense64_score_readings";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!meas_xy || J < 1 || J > kJointReadings || count < 1 || count > kSparseRows / 2 || first_lm < 0 ||
         3 + 2 * ((long long)first_lm + count) > d->live || (!nis_out && !flag_out))
         return fail(EKF_ERR_INVALID, std::string(fnc) + ": bad argument (1 <= J <= 128, 1 <= count <= 32768, the landmarks "
@@ -1236,6 +1357,7 @@ ekf_status ekf_dense64_score_readings(ekf_dense64_handle d, const ekf_params* pa
     const JointView jv = view(d->joint.p, L::joint_layout());
     HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
     hipError_t queued = hipSuccess;
     score_readings_launch(d, p, jv, J, first_lm, count, chunk, nis_out != nullptr, [&](int j0, int nr, const SpsView& v) {
         const size_t at = (size_t)j0 * count, n = (size_t)nr * count;
@@ -1260,6 +1382,7 @@ ekf_status ekf_dense64_joint_operands(ekf_dense64_handle d, const ekf_params* pa
                                       double* elapsed_ms) {
     const char* fnc = "ekf_dense64_joint_operands";
     if (!d) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!lm_idx || !meas_xy || V < 1 || V > kJointPairs || (!cols_out && !Hc_out && !nu_out))
         return fail(EKF_ERR_INVALID, std::string(fnc) + ": bad argument (1 <= V <= 30)");
     for (int v = 0; v < V; v++) {
@@ -1277,6 +1400,7 @@ ekf_status ekf_dense64_joint_operands(ekf_dense64_handle d, const ekf_params* pa
     HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * V, hipMemcpyHostToDevice, d->stream));
     HIPC(hipMemcpyAsync(jv.pair_lm, lm_idx, sizeof(int) * V, hipMemcpyHostToDevice, d->stream));
     HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
     ekf::launch_dense64_joint_operands(d->x, jv.xy, jv.pair_lm, nullptr, V, p.r_meas, cin.cols, cin.Hc, cin.R, cin.nu,
                                        d->stream);
     return finish_timed(d, elapsed_ms, {{cols_out, cin.cols, sizeof(int) * s},
@@ -1290,6 +1414,7 @@ ekf_status ekf_dense64_associate_joint(ekf_dense64_handle d, const ekf_params* p
     const char* fnc = "ekf_dense64_associate_joint";
     const std::string fn = fnc;
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (J < 1 || J > kJointReadings) return fail(EKF_ERR_INVALID, fn + ": J must lie in [1, 128]");
     EKFC(associate_checks(d, fn, n_max, known, flags));
@@ -1314,6 +1439,7 @@ ekf_status ekf_dense64_associate_scan_joint(ekf_dense64_handle d, const ekf_para
     const char* fnc = "ekf_dense64_associate_scan_joint";
     const std::string fn = fnc;
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
     if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kScanClusters)
         return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 128]");
@@ -1357,6 +1483,7 @@ ekf_status ekf_dense64_predict_landmarks(ekf_dense64_handle d, const ekf_params*
         ekf::launch_dense64_panel_map(pv.K, pv.T, d->pend_rows, in.Fr, nullptr, d->ld, 0, 3, 3, d->stream);
     });
     ekf::launch_dense64_block(d->S, d->x, in.Fr, in.Qr, in.dx, d->live, d->ld, 0, 3, d->stream);
+    d->region_row_map(in.Fr, nullptr, 0, 3, 3);
     return finish_timed(d, elapsed_ms, {{Fr_out, in.Fr, sizeof(double) * 9}, {dx_out, in.dx, sizeof(double) * 3}});
 }
 
@@ -1369,6 +1496,7 @@ ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle d, const ekf_params*
     const char* fnc = "ekf_dense64_measure_landmarks";
     const std::string fn = fnc;
     if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving((flags & EKF_DENSE64_LM_JOSEPH) ? d : nullptr);   // the Joseph form is outside a region's terms
     if (!sensor_xy || !visible || !initialised) return fail(EKF_ERR_INVALID, fn + ": null argument");
     if (n_lm < 1 || 3 + 2 * (long long)n_lm > d->live)
         return fail(EKF_ERR_INVALID, fn + ": the n_lm >= 1 landmarks must lie inside the live dimension");
@@ -1389,6 +1517,7 @@ ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle d, const ekf_params*
     // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
     auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
     HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
     ekf::launch_dense64_model_snapshot(d->x, mv.pose, d->stream);                        // :109-111
     if (init) ekf::launch_dense64_model_init(mv.pose, mv.xy, n_lm, d->x, d->stream);     // :113-128, Sigma untouched
     bool open = true;   // e0 is recorded and nothing has synchronised behind it yet

@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include "ekf_dense64_layout.hpp"
+#include "ekf_dense64_region.hpp"
 #include "ekf_dense_split.hpp"   // kDenseTile = 128: ld must be a multiple of it
 
 namespace ekf {
@@ -372,4 +373,26 @@ void launch_dense64_frame_state(const Dense64FramePlan& p, int mode, const doubl
 // snapshot and the panels, the pass over Sigma[3:Na, 3:Na], the new pose rows and columns.  Nothing at an index >= Na is
 // read or written.
 void launch_dense64_frame_congruence(const Dense64FramePlan& p, double* Sigma, double* ws, bool has_C, hipStream_t st);
+
+// ---- a local region (ekf_dense64_region.hip; plan and layout in ekf_dense64_region.hpp, the definition is
+// include/ekfslam.h's, ekf_dense64_region_begin): the accumulators Phi, Psi, theta of the compressed filter in `acc`
+// (Dense64RegionPlan::acc_bytes), the two panels of the global update in `scratch` (scratch_bytes).
+hipError_t dense64_region_prepare();   // raises the dynamic-LDS limit of the Sigma_bb product (64.8 KiB)
+// One launch: Phi = I, Psi = 0, theta = 0.
+void launch_dense64_region_reset(const Dense64RegionPlan& p, void* acc, hipStream_t st);
+// The two launches behind a sparse correction of the live corner: the panels W = Hc Phi[cols, :], Z = S^-1 W and
+// theta += Z^T nu, then Phi -= K W and Psi += W^T Z.  Kt [m][ldk] = K^T, Sinv [64][64], cols, Hc, nu (nullable) and the
+// verdict word are the live call's own, on the device; a set verdict leaves everything as it was.
+void launch_dense64_region_correct(const Dense64RegionPlan& p, void* acc, const double* Kt, int ldk, const double* Sinv,
+                                   const int* cols, const double* Hc, const double* nu, int m, int s, const int* verdict,
+                                   hipStream_t st);
+// One launch: Phi[first .. first + r, :] <- M Phi[src, :], M r x s row-major on the device; src: s indices on the device,
+// or NULL for the block itself (s == r, in place); s = 0 writes +0.
+void launch_dense64_region_rowmap(const Dense64RegionPlan& p, void* acc, const double* M, const int* src, int first, int r,
+                                  int s, hipStream_t st);
+// The six launches of the global update, in the order the algebra needs (the first three read Sigma0_ab and Sigma0_ba):
+// x_b, Y and V, Sigma_bb on the MFMA tile, Sigma_ba through the scratch, Sigma_ab.  Nothing with a row and a column index
+// below Na is read or written; the padding of Sigma and of the state is neither.
+void launch_dense64_region_end(const Dense64RegionPlan& p, double* Sigma, double* state, const void* acc, void* scratch,
+                               hipStream_t st);
 }  // namespace ekf

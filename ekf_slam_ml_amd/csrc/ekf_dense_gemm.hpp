@@ -110,10 +110,21 @@ static_assert(gemm_is<GemmTailTile<float, true>>(64, 64, 1, 1, 1, 16640) && gemm
 static_assert(gemm_is<GemmMainTile<double, true>>(128, 128, 2, 4, 4, 66048) && gemm_is<GemmMainTile<double, false>>(128, 128, 2, 4, 4, 66304));
 static_assert(gemm_is<GemmTailTile<double, true>>(64, 64, 1, 2, 2, 16640) && gemm_is<GemmTailTile<double, false>>(64, 64, 1, 2, 2, 16768));
 
+// What a caller may hang on the tile's loads and stores.  The default hangs nothing, and every `if constexpr` below then
+// leaves the code as it is written for the propagation.  A mask with kOn (ekf_dense64_region.hip) provides
+//   Vec a(const E* p, int row, int k)    the A operand at rows / columns (row, k .. k + VW) of A, p pointing at it
+//   Vec b(const E* p, int k, int col)    the row-major B operand at (k, col .. col + VW)
+//   bool c(int row, int col)             whether C (and Qadd) at (row, col) is read and written at all
+// and answers with zeros instead of loading what does not belong to the product: 0 x NaN is a NaN, so an entry that is to
+// stay out must not reach the MFMA.
+struct GemmNoMask { static constexpr bool kOn = false; };
+
 // One output tile of (2 FR WTM) x (2 FR WTN) at row0 / col0 of C; smem: GemmTile::kLdsBytes, 16-byte aligned.
-template <class E, bool BT, int NBUF, int WTM, int WTN>
+template <class E, bool BT, int NBUF, int WTM, int WTN, class Mask = GemmNoMask>
 __device__ __forceinline__ void gemm_tile(const E* __restrict__ A, const E* __restrict__ B, E* __restrict__ C,
-                                          const E* __restrict__ Qadd, int ld, int row0, int col0, E* smem, int kdim) {
+                                          const E* __restrict__ Qadd, int ld, int row0, int col0, E* smem, int kdim,
+                                          Mask mask = Mask()) {
+    static_assert(!Mask::kOn || !BT, "a mask is defined for a row-major B");
     using Tile = GemmTile<E, BT, NBUF, WTM, WTN>;
     using TR = GemmTraits<E>;
     using Vec = typename TR::Vec;
@@ -133,7 +144,8 @@ __device__ __forceinline__ void gemm_tile(const E* __restrict__ A, const E* __re
 #pragma unroll
         for (int p = 0; p < PA; p++) {  // 8 lanes cover one 128-B row segment
             const int row = p * 32 + (t >> 3), kv = (t & 7) * VW;
-            ra[p] = *reinterpret_cast<const Vec*>(Ag + (size_t)row * ld + k0 + kv);
+            if constexpr (Mask::kOn) ra[p] = mask.a(Ag + (size_t)row * ld + k0 + kv, row0 + row, k0 + kv);
+            else ra[p] = *reinterpret_cast<const Vec*>(Ag + (size_t)row * ld + k0 + kv);
         }
         if constexpr (BT) {
 #pragma unroll
@@ -145,7 +157,8 @@ __device__ __forceinline__ void gemm_tile(const E* __restrict__ A, const E* __re
 #pragma unroll
             for (int p = 0; p < PB; p++) {  // TN / VW lanes cover one row segment of the tile
                 const int k = p * RB + t / (TN / VW), jv = (t % (TN / VW)) * VW;
-                rb[p] = *reinterpret_cast<const Vec*>(Bg + (size_t)(k0 + k) * ld + jv);
+                if constexpr (Mask::kOn) rb[p] = mask.b(Bg + (size_t)(k0 + k) * ld + jv, k0 + k, col0 + jv);
+                else rb[p] = *reinterpret_cast<const Vec*>(Bg + (size_t)(k0 + k) * ld + jv);
             }
         }
     };
@@ -244,6 +257,8 @@ __device__ __forceinline__ void gemm_tile(const E* __restrict__ A, const E* __re
             for (int r = 0; r < NACC; r++) {
                 const int row = i * FR + TR::c_row(r, lk);
                 const int col = j * FR + li;
+                if constexpr (Mask::kOn)
+                    if (!mask.c(row0 + wm * FR * WTM + row, col0 + wn * FR * WTN + col)) continue;
                 E v = acc[i][j][r];
                 if (Qg) v += Qg[(size_t)row * ld + col];
                 Cg[(size_t)row * ld + col] = v;

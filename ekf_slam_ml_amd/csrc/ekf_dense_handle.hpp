@@ -5,6 +5,7 @@
 // ledger (ekf_device_mem.hpp).  Also here: the typed views of the
 // layouts of ekf_dense64_layout.hpp, and the end of a timed entry point.
 #pragma once
+#include "ekf_dense64_region_mem.hpp"
 #include "ekf_runtime.hpp"
 
 namespace ekfrt {
@@ -121,9 +122,19 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekf::Dense64CorrectPlan pl_full{};     // of (N, ld): the dense correction, and the layout of the workspace
     ekf::Dense64CorrectPlan pl_live{};     // of (live, ld) on that layout: the sparse corrections and the flush
 
+    // a local region (ekf_dense64_region_begin): the accumulators and the scratch of the global update, one group of the
+    // ledger that stays for the next region of the same size; the live value to go back to; what the region absorbed
+    ekfrt::RegionMem region_mem;           // the accumulators and the scratch (ekf_dense64_region_mem.hpp)
+    int region_on = 0;                     // a region is open
+    int region_back = 0;                   // the live dimension region_end restores
+    long long region_corrections = 0, region_row_maps = 0;   // of the open region, or of the last one
+    long long region_ended_by_other = 0;   // regions of this handle that a call outside the region's terms ended
+    ekf::Dense64RegionPlan region_pl{};
+    int region_leaving = 0;                // a call outside the terms is between its checks and its first launch (begin_leave)
+
     ekf_status created();
     void destroying();
-    void sigma_needed() { flush_pending(); }
+    void sigma_needed() { begin_leave(); flush_pending(); }   // (the flush ends a region that is being left)
     void sigma_replaced() { pend_rows = 0; }   // the pending rows belonged to the covariance that was replaced
 
     double* workspace() const { return ws_own ? ws_own : T; }   // (the product buffer is dead between propagations)
@@ -133,6 +144,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     // Sigma <- Sigma_cur: one launch on the handle's stream when rows are pending, nothing otherwise.  For every entry point
     // that reads or writes Sigma in memory, after its argument checks and inside its timed region.
     void flush_pending() {
+        finish_leave();   // a call outside a region's terms: the region ends here, behind the call's e0
         if (pend_rows == 0) return;
         const ekfrt::PendView p = panels();
         ekf::launch_dense64_flush(pl_live, S, p.K, p.T, pend_rows, p.zero, stream);
@@ -142,7 +154,65 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     // them, and are applied first otherwise.
     template <class Launch>
     void carry_or_flush(Launch&& on_panels) {
+        finish_leave();
         if (carries()) on_panels(panels());
         else flush_pending();
     }
+    // ---- the local region ----------------------------------------------------------------------------------------------
+    // The end of a region, launches only, on the handle's stream: the pending rows at width Na, the global update, the live
+    // dimension the region found.  (The accumulators are set again by the next region_begin.)
+    void close_region() {
+        flush_pending();
+        if (region_corrections || region_row_maps)   // (a region that absorbed nothing owes nothing: every bit stays)
+            ekf::launch_dense64_region_end(region_pl, S, x, region_mem.acc, region_mem.scratch, stream);
+        region_on = 0;
+        live = region_back;
+        pl_live = ekf::dense64_live_plan(pl_full, live);
+    }
+    // An entry point outside the region's terms leaves in two steps, so that a refused call ends nothing and the global
+    // update runs inside the call's own timed region.  begin_leave (through RegionLeave, on entry): host only -- the live
+    // dimension the region found is back, so the call checks its arguments as it always did.  finish_leave (behind the call's
+    // e0: inside flush_pending and carry_or_flush, or spelled where a call has neither): the launches.  cancel_leave
+    // (RegionLeave's destructor): the call returned before its first launch, the region stays open.
+    void begin_leave() {
+        if (!region_on || region_leaving) return;
+        region_leaving = 1;
+        live = region_back;
+        pl_live = ekf::dense64_live_plan(pl_full, live);
+    }
+    void finish_leave() {
+        if (!region_leaving) return;
+        region_leaving = 0;
+        live = region_pl.Na;   // (the pending rows have the region's width)
+        pl_live = ekf::dense64_live_plan(pl_full, live);
+        (void)hipSetDevice(device);
+        close_region();
+        region_ended_by_other++;
+    }
+    void cancel_leave() {
+        if (!region_leaving) return;
+        region_leaving = 0;
+        live = region_pl.Na;
+        pl_live = ekf::dense64_live_plan(pl_full, live);
+    }
+    // the two steps at once: for the calls that have no timed region and check nothing against the live dimension
+    void leave_region() {
+        begin_leave();
+        finish_leave();
+    }
+    // the accumulator step of a call inside a region, behind the live call's own launches
+    void region_row_map(const double* M, const int* src, int first, int r, int s) {
+        if (!region_on) return;
+        ekf::launch_dense64_region_rowmap(region_pl, region_mem.acc, M, src, first, r, s, stream);
+        region_row_maps++;
+    }
+};
+
+// on entry of a call outside a region's terms (d may be null: nothing)
+struct RegionLeave {
+    ekf_dense64_s* d;
+    explicit RegionLeave(ekf_dense64_s* h) : d(h) { if (d) d->begin_leave(); }
+    ~RegionLeave() { if (d) d->cancel_leave(); }
+    RegionLeave(const RegionLeave&) = delete;
+    RegionLeave& operator=(const RegionLeave&) = delete;
 };

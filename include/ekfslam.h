@@ -1031,6 +1031,73 @@ ekf_status ekf_dense64_coupling(ekf_dense64_handle h, int Na,
                                 double* max_abs,     /* largest |Sigma[i][j]| among them (0 when none); nullable */
                                 double* elapsed_ms);
 
+/* A LOCAL REGION: the live corner made exact for a COUPLED tail (the compressed EKF, Guivant & Nebot 2001).  The live
+ * dimension is exact only while the tail is decoupled; on a surveyed map every correction owes the whole of Sigma.  Between
+ * ekf_dense64_region_begin(h, Na) and ekf_dense64_region_end the structured calls run at live = Na on A = [0, Na) exactly as
+ * they do with ekf_dense64_set_live(Na) -- the corner Sigma_aa, x_a and every returned S, nis and flag are BIT FOR BIT
+ * those -- and three accumulators (Phi, Na x Na, from I; Psi, Na x Na, from 0; theta, Na, from 0) record what the rest
+ * B = [Na, N) of the map will owe.  With Sigma0 = Sigma as stored at region_begin the region keeps
+ *   Sigma_ab = Phi Sigma0_ab    Sigma_ba = Sigma0_ba Phi^T    Sigma_bb = Sigma0_bb - Sigma0_ba Psi Sigma0_ab
+ *   x_b = x0_b + Sigma0_ba theta
+ * and region_end pays B once: that is exact algebra, not an approximation (for a Sigma_aa that is symmetric; for one that
+ * is not symmetric in bits Sigma_ba is taken as Sigma0_ba Phi^T where the eager sequence gives Sigma0_ba Gamma,
+ * Gamma = prod (I - H_a^T S^-1 T_a), which differs from Phi^T at rounding level: DESIGN.md 4.8.21).
+ * What a call inside a region adds, behind its own launches, on the handle's stream and inside its timed region:
+ *   a correction (correct_sparse, correct_sparse_deferred -- at the call, where its gain exists; measure_landmarks and
+ *   associate_landmarks without EKF_DENSE64_LM_JOSEPH): with the gain K_a, S^-1 and nu the live call used, and the Phi from
+ *   before the call, W = Hc Phi[cols, :], Z = S^-1 W; theta += Z^T nu; Psi += W^T Z; Phi -= K_a W.  32 Na^2 bytes.  A
+ *   refused correction (EKF_ERR_STATE) adds nothing.
+ *   propagate_block(first, r, Fr) and predict_landmarks: Phi[b, :] <- Fr Phi[b, :], b = [first, first + r); Q and dx do
+ *   not reach B.      init_block(first, r, s, cols, G): Phi[b, :] <- G Phi[cols, :], zeros at s = 0.
+ *   score_sparse, score_landmarks, flush, get_sigma_block / get_state_block / set_state_block with every index < Na: nothing.
+ * Every sum runs in ascending index, one fused multiply-add per term, no floating-point atomics: a run repeats bit for
+ * bit, and nothing before region_end depends on N or ld.  Entries between Na and a tile's edge are masked element by
+ * element, as the live launches do.
+ * EVERY OTHER CALL ENDS THE REGION FIRST and then runs as it always did, so no result is ever stale: get_sigma, get_state,
+ * set, set_state, propagate, correct, score, swap_blocks, health, symmetrize, factor, coupling, map_congruence,
+ * reframe_landmarks, score_landmark_pairs, merge_landmarks, score_readings, joint_operands, associate_joint,
+ * associate_scan, associate_scan_joint, correct_sparse_joseph and EKF_DENSE64_LM_JOSEPH, set_live (also the one inside
+ * EKF_DENSE64_LM_GROW_LIVE), and a block readout or state block with an index >= Na.  Such a call checks its arguments
+ * first, against the live dimension the region found -- a REFUSED call ends nothing, the region stays open -- and the
+ * global update then runs on the handle's stream INSIDE that call's own timed region, ahead of its own launches: its
+ * elapsed_ms includes it (the calls without a timed region -- get_state, set_state, set, set_live, the block readouts --
+ * just run it first).  ekf_dense64_region_info counts these endings.
+ * ekf_dense64_region_begin: 3 <= Na < N (EKF_ERR_INVALID otherwise); EKF_ERR_STATE when a region is open.  The pending rows
+ * are applied first, at the old width; the live value is remembered and live = Na.  The accumulators (2 Na pitch + 129 pitch
+ * doubles, pitch = Na rounded up to 128) and the scratch of the global update (2 Na ld doubles) come from the handle's
+ * ledger as ONE all-or-nothing group and stay for the next region that needs no more; on a failure the call returns
+ * EKF_ERR_NOMEM (EKF_ERR_HIP for another error), the HIP error is cleared, no region is open and the handle is otherwise as
+ * it was.
+ * ekf_dense64_region_end: EKF_ERR_STATE when no region is open.  The pending rows are applied at width Na, then, in this order
+ * because the first two read Sigma0_ab and Sigma0_ba:  x_b += Sigma0_ba theta;  Y = -(Psi Sigma0_ab) and V = Phi Sigma0_ab
+ * into the scratch;  Sigma_bb += Sigma0_ba Y on the fp64 MFMA tile of the dense propagation, on Sigma's own 128-grid with
+ * K = Na rounded up to 16 -- 2 Na (N - Na)^2 flop, the one large product; operands outside the product are answered with
+ * zeros AT THE LOAD and no entry with a row or column index < Na (or in the padding) is stored, so a NaN or an Inf in
+ * Sigma_bb or Sigma_aa reaches nothing it does not belong to;  Sigma_ba <- Sigma0_ba Phi^T through the scratch;
+ * Sigma_ab <- V.  The padding of Sigma and of the state stays +0.  The remembered live value is restored.  *report
+ * (nullable): what the region was and absorbed.  elapsed_ms (nullable) = HIP-event time of the launches. */
+typedef struct {
+    int Na, Nb;                  /* the region and the rest, Nb = N - Na */
+    long long corrections;       /* corrections absorbed (refused ones not counted) */
+    long long row_maps;          /* propagate_block / init_block calls absorbed */
+    long long group_bytes;       /* device bytes of the accumulators and the scratch */
+} ekf_dense64_region_report;
+ekf_status ekf_dense64_region_begin(ekf_dense64_handle h, int Na, double* elapsed_ms);
+ekf_status ekf_dense64_region_end(ekf_dense64_handle h, ekf_dense64_region_report* report, double* elapsed_ms);
+/* every output nullable; *Na = 0 without a region; corrections and row_maps: of the open region, or of the last one */
+ekf_status ekf_dense64_region_info(ekf_dense64_handle h, int* active, int* Na, long long* corrections, long long* row_maps,
+                                   long long* ended_by_other_call);
+/* Test hook: Sigma as it sits in memory, ld x ld doubles row-major (ld from ekf_dense64_launch_info), and the state, ld
+ * doubles, padding included -- every call of the handle keeps the padding at +0, and this is how a test looks at it.
+ * Either output nullable.  It needs Sigma in memory: pending rows are applied and an open region ends first. */
+ekf_status ekf_dense64_get_padded(ekf_dense64_handle h, double* sigma_out, double* state_out);
+/* the plan of a region of Na states on this handle (every output nullable): the tile of the accumulator pass and its
+ * workgroup, the row pitch of Phi and Psi, the tiles of that pass, the 128 x 128 tiles and the K of the Sigma_bb product,
+ * the bytes of the group */
+ekf_status ekf_dense64_region_launch_info(ekf_dense64_handle h, int Na, int* tile_rows, int* tile_cols, int* threads,
+                                          int* pitch, int* update_tiles, int* gemm_tiles, int* gemm_k,
+                                          long long* group_bytes);
+
 /* (Re)initialisation of a block of states: what a map that grows, or a fixed-capacity map that recycles a slot, does to
  * Sigma.  The states b = [first, first + r) are replaced by a new variable y = g(x[cols], z) of s other states and a
  * reading z: G (r x s) is the Jacobian of g with respect to x[cols], W the caller's Gz R Gz^T, xb the value g(..).  The
