@@ -63,7 +63,7 @@ SYMBOLS = [
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
     "ekf_dense64_frame_launch_info", "ekf_dense64_map_congruence", "ekf_dense64_reframe_landmarks",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
-    "ekf_batch_rank2_variant", "ekf_batch_rank2_resident",
+    "ekf_batch_rank2_variant", "ekf_batch_rank2_resident", "ekf_batch_rank2_packing", "ekf_batch_spec_counts",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
     "ekf_phase_trace", "ekf_test_raise_device_error",
@@ -292,6 +292,8 @@ def load():
         "ekf_dense64_set_state_block": [h, C.c_int, C.c_int, _dp],
         "ekf_batch_rank2_variant": [h, _ip, _ip, _ip, _ip],
         "ekf_batch_rank2_resident": [h, _ip],
+        "ekf_batch_rank2_packing": [h, _ip],
+        "ekf_batch_spec_counts": [h, C.POINTER(C.c_longlong)],
         "ekf_batch_set_known_counts": [h, _ip],
         "ekf_set_profiling": [h, C.c_int],
         "ekf_set_forms": [h, C.c_uint],
@@ -737,11 +739,29 @@ class BatchEKF:
         f = self.forms & ~(FORM_STEP_FUSED | FORM_STEP_SPLIT_PASS)
         self.set_forms(f | (0 if e == 0 else FORM_STEP_FUSED | (FORM_STEP_SPLIT_PASS if e == 1 else 0)))
 
+    def rank2_packing(self):
+        """P of a full-width eager correction of this pool: the rows k_rank2_packed streams as one virtual row; 1 = the
+        plain kernel (the launcher and this hook read one plan, csrc/ekf_rank2_plan.hpp)"""
+        P = C.c_int()
+        _check(self._lib.ekf_batch_rank2_packing(self._h, C.byref(P)))
+        return P.value
+
+    def spec_counts(self):
+        """(eligible, hits) of EKF_FORM_STEP_SPECULATE since creation / reset: readings of delayed unknown-association
+        steps whose decision was compared with the guesses of the launch in front, and those that found their winner
+        among them and continued from its rebuilt rows"""
+        c = (C.c_longlong * 2)()
+        _check(self._lib.ekf_batch_spec_counts(self._h, c))
+        return int(c[0]), int(c[1])
+
     def rank2_kernel(self):
-        """name of the k_rank2 instantiation a full-width eager correction of this pool launches, + rows per workgroup"""
+        """name of the kernel instantiation a full-width eager correction of this pool launches (k_rank2, k_rank2_queue
+        or, where rank2_packing() > 1, k_rank2_packed), + rows (packed: virtual rows) per workgroup"""
         v = [C.c_int() for _ in range(4)]
         _check(self._lib.ekf_batch_rank2_variant(self._h, *[C.byref(x) for x in v]))
         u, nt, tpb, rows = (x.value for x in v)
+        if self.rank2_packing() > 1:
+            return f"ekf::k_rank2_packed<{u},{'true' if nt else 'false'}>", rows
         res = C.c_int()
         _check(self._lib.ekf_batch_rank2_resident(self._h, C.byref(res)))
         return f"ekf::k_rank2{'_queue' if res.value else ''}<{u},{'true' if nt else 'false'},{tpb}>", rows

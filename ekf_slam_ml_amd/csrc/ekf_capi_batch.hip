@@ -36,6 +36,19 @@ ekf_status ekf_batch_form_counts(ekf_batch_handle hb, long long counts[8]) {
     return EKF_OK;
 }
 
+ekf_status ekf_batch_spec_counts(ekf_batch_handle hb, long long out[2]) {
+    if (!hb || !out) return fail(EKF_ERR_INVALID, "null argument");
+    Pool& P = hb->pool;
+    out[0] = out[1] = 0;
+    if (!P.spec_cnt) return EKF_OK;   // no speculating step has run
+    EKFC(P.use());
+    unsigned long long c[2] = {0, 0};
+    EKFC(P.download(c, P.spec_cnt, sizeof(c)));
+    out[0] = (long long)c[0];
+    out[1] = (long long)c[1];
+    return EKF_OK;
+}
+
 ekf_status ekf_batch_create(int B, int n, const ekf_params* params, int device, ekf_batch_handle* out) {
     if (!out) return fail(EKF_ERR_INVALID, "ekf_batch_create: out is null");
     *out = nullptr;
@@ -77,16 +90,29 @@ ekf_status ekf_batch_set_tuning(ekf_batch_handle hb, int rows_per_block, int non
     return EKF_OK;
 }
 
+// The three report hooks read the plan launch_rank2 launches from (ekf_rank2_plan.hpp) for a full-width view of the pool.
 ekf_status ekf_batch_rank2_variant(ekf_batch_handle hb, int* group_rows, int* nontemporal, int* threads, int* rows_per_block) {
     if (!hb) return fail(EKF_ERR_INVALID, "null handle");
-    ekf::rank2_variant(hb->pool.pv, hb->pool.tuning, group_rows, nontemporal, threads, rows_per_block);
+    const ekf::PoolView& pv = hb->pool.pv;   // (none of the four depends on the CU count: no device is touched)
+    const ekf::Rank2Plan p = ekf::rank2_plan(pv.B, pv.N, pv.ld, hb->pool.tuning, true, pv.queue != nullptr, 0);
+    if (group_rows) *group_rows = p.group_rows;
+    if (nontemporal) *nontemporal = p.nontemporal;
+    if (threads) *threads = p.threads;
+    if (rows_per_block) *rows_per_block = p.rows;
     return EKF_OK;
 }
 
 ekf_status ekf_batch_rank2_resident(ekf_batch_handle hb, int* resident) {
     if (!hb || !resident) return fail(EKF_ERR_INVALID, "null argument");
     EKFC(hb->pool.use());
-    *resident = ekf::rank2_resident(hb->pool.pv, hb->pool.tuning) ? 1 : 0;
+    *resident = ekf::rank2_plan_of(hb->pool.pv, hb->pool.tuning, true).kind == ekf::RANK2_QUEUE ? 1 : 0;
+    return EKF_OK;
+}
+
+ekf_status ekf_batch_rank2_packing(ekf_batch_handle hb, int* P) {
+    if (!hb || !P) return fail(EKF_ERR_INVALID, "null argument");
+    const ekf::PoolView& pv = hb->pool.pv;
+    *P = ekf::rank2_plan(pv.B, pv.N, pv.ld, hb->pool.tuning, true, pv.queue != nullptr, 0).P;
     return EKF_OK;
 }
 
@@ -473,7 +499,7 @@ ekf_status ekf_batch_run_unknown(ekf_batch_handle hb, int t_begin, int t_end, in
                                                   P.active_prefix ? 3 + 2 * P.touched_hwm : P.pv.N,
                                                   P.ulog_assoc + (size_t)t * B * jmax, P.pending(), P.corr_counter, P.cf_cnt,
                                                   P.blk_cache, P.cf_pred, P.stream, speculate ? P.spec : nullptr,
-                                                  speculate ? P.specw : nullptr);
+                                                  speculate ? P.specw : nullptr, speculate ? P.spec_cnt : nullptr);
             P.pend_count += 2 * jmax;
             P.form_counts[5]++;
             smax = 0;  // the step is done

@@ -998,13 +998,14 @@ static int device_cus() {   // CUs of the current device (grid of the resident k
 }
 
 template <int U, int TPB>
-static void launch_rank2_ut(const PoolView& pv, int rows, bool nt, hipStream_t s, bool resident) {
-    const int ld2a = (pv.N + 1) / 2;
-    dim3 grid((ld2a + TPB - 1) / TPB, (pv.N + rows - 1) / rows, pv.B);
-    // resident workgroups on one tile queue (rank2_resident: big pools only), the queue word zeroed in front
+static void launch_rank2_ut(const PoolView& pv, const Rank2Plan& p, hipStream_t s) {
+    const int rows = p.rows;
+    const bool nt = p.nontemporal != 0;
+    dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    // resident workgroups on one tile queue (RANK2_QUEUE: big pools only), the queue word zeroed in front
     const long long total = (long long)grid.x * grid.y * grid.z;
     const int cus = device_cus();
-    if (resident && hipMemsetAsync(pv.queue, 0, sizeof(unsigned), s) == hipSuccess) {
+    if (p.kind == RANK2_QUEUE && hipMemsetAsync(pv.queue, 0, sizeof(unsigned), s) == hipSuccess) {
         if (nt)
             hipLaunchKernelGGL((k_rank2_queue<U, true, TPB>), dim3(cus), dim3(TPB), 0, s, pv.sigma, pv.Kg, pv.Gh, pv.rec, pv.state,
                                pv.N, pv.ld, pv.sigma_stride, rows, (int)grid.x, (int)grid.y, (unsigned)total, pv.queue);
@@ -1022,98 +1023,44 @@ static void launch_rank2_ut(const PoolView& pv, int rows, bool nt, hipStream_t s
 }
 
 template <int U>
-static void launch_rank2_u(const PoolView& pv, int rows, bool nt, hipStream_t s, bool resident) {
-    const int ld2a = (pv.N + 1) / 2;  // double2 columns of an active row
-    if (ld2a <= 64) launch_rank2_ut<U, 64>(pv, rows, nt, s, resident);
-    else if (ld2a <= 128) launch_rank2_ut<U, 128>(pv, rows, nt, s, resident);
-    else if (ld2a <= 192) launch_rank2_ut<U, 192>(pv, rows, nt, s, resident);
-    else launch_rank2_ut<U, 256>(pv, rows, nt, s, resident);
-}
-
-// which instantiation of k_rank2 (and how many rows per workgroup) a launch over this view takes
-void rank2_variant(const PoolView& pv, const Rank2Tuning& t, int* u_out, int* nt_out, int* tpb_out, int* rows_out) {
-    // Non-temporal only when the pool cannot stay resident in the 256 MiB Infinity Cache between
-    // two corrections; a single filter's covariance (32 MB at n = 1000) should stay cached.
-    // (the bytes this launch touches: pv.N may be a discovered prefix of a much larger pool)
-    const size_t pool_bytes = (size_t)pv.B * pv.N * ((size_t)pv.N * sizeof(double));
-    const bool nt = t.nontemporal >= 0 ? t.nontemporal != 0 : pool_bytes > ((size_t)192 << 20);
-    int u = t.group_rows;
-    int rows = t.rows_per_block;
-    if (rows <= 0) {
-        // Measured on MI355X (profiles/): a big pool streams fastest with 32 rows per workgroup taken as
-        // two 16-row groups (32 x 16 B in flight per lane, 2 waves/SIMD): 6.17 TB/s algorithmic.  A small
-        // pool needs enough workgroups to cover 256 CUs a few times over.
-        const long long strips = (long long)pv.B * (((pv.N + 1) / 2 + 255) / 256);
-        const long long total = strips * pv.N;
-        rows = total >= 256LL * 8 * 32 ? 32 : (total >= 256LL * 4 * 8 ? 8 : 4);
+static void launch_rank2_u(const PoolView& pv, const Rank2Plan& p, hipStream_t s) {
+    switch (p.threads) {
+        case 64: launch_rank2_ut<U, 64>(pv, p, s); break;
+        case 128: launch_rank2_ut<U, 128>(pv, p, s); break;
+        case 192: launch_rank2_ut<U, 192>(pv, p, s); break;
+        default: launch_rank2_ut<U, 256>(pv, p, s); break;
     }
-    if (rows > 1024) rows = 1024;
-    if (u != 2 && u != 4 && u != 8 && u != 16) u = rows >= 32 ? 16 : (rows >= 8 ? 8 : (rows >= 4 ? 4 : 2));
-    const int ld2a = (pv.N + 1) / 2;
-    const int tpb = ld2a <= 64 ? 64 : (ld2a <= 128 ? 128 : (ld2a <= 192 ? 192 : 256));
-    if (u_out) *u_out = u;
-    if (nt_out) *nt_out = nt ? 1 : 0;
-    if (tpb_out) *tpb_out = tpb;
-    if (rows_out) *rows_out = rows;
 }
 
-// P > 1: the row-packed kernel serves this (full-width) view -- the smallest P <= 32 whose virtual rows fill the
-// 256-lane strips to >= 97 %; 1: the plain kernel (rows already fill their strips, rows shorter than a wavefront, or a
-// small pool that needs more workgroups than packing leaves)
-int rank2_packing(const PoolView& pv, const Rank2Tuning& t) {
-    const int ld2n = pv.ld / 2;
-    if (!t.row_packing) return 1;                             // EKF_FORM_ROW_PACKING off: the plain kernel
-    if (ld2n < 64) return 1;                                  // a wavefront may straddle at most two sub-rows
-    if (pick_ld(pv.N) != pv.ld) return 1;                     // a prefix view: columns beyond it must stay untouched
-    auto util = [&](int P) { const long long w = (long long)P * ld2n; return (double)w / (double)((w + 255) / 256 * 256); };
-    if (util(1) >= 0.93) return 1;
-    if ((long long)pv.B * pv.N * ld2n < 256LL * 256 * 64) return 1;   // too little work for fat workgroups
-    for (int P = 2; P <= 32; P++)
-        if (util(P) >= 0.97) return P;
-    return 1;
-}
-
-// Whether a launch over this view runs as resident workgroups on one tile queue (k_rank2_queue): the 256-lane, 16-row-group
-// instantiation on pools with at least 16 tiles per CU
-bool rank2_resident(const PoolView& pv, const Rank2Tuning& t) {
-    int u, nti, tpb, rows;
-    rank2_variant(pv, t, &u, &nti, &tpb, &rows);
-    if (!t.tile_queue || !pv.queue || u != 16 || tpb != 256) return false;
-    const int cus = device_cus();
-    const long long total = (long long)(((pv.N + 1) / 2 + tpb - 1) / tpb) * ((pv.N + rows - 1) / rows) * pv.B;
-    return cus > 0 && total >= 16LL * cus && total < 0x7fffffffLL;
+// Which kernel a launch over this view takes, in which instantiation and grid: every decision is in ekf_rank2_plan.hpp
+// (host only: tests/cpp/rank2_plan_check.cpp sweeps it); only the CU count of the current device is asked here.
+Rank2Plan rank2_plan_of(const PoolView& pv, const Rank2Tuning& t, bool full_width) {
+    return rank2_plan(pv.B, pv.N, pv.ld, t, full_width, pv.queue != nullptr, device_cus());
 }
 
 void launch_rank2(const PoolView& pv, const Rank2Tuning& t, hipStream_t s, bool full_width) {
-    int u, nti, tpb, rows;
-    rank2_variant(pv, t, &u, &nti, &tpb, &rows);
-    const bool nt = nti != 0;
-    const int P = full_width ? rank2_packing(pv, t) : 1;
-    if (P > 1) {
-        const int ld2n = pv.ld / 2;
-        // measured (tools/rank2_width_sweep.py, profiles/r02/rank2_width_sweep.txt): ONE 8-row group per workgroup
-        // (n = 200, B = 16384: 6.26 TB/s = 0.78 of peak; 16 rows 0.73, 32 rows 0.64; the plain kernel 0.67)
-        const int vrows = t.rows_per_block > 0 ? t.rows_per_block : 8;
-        dim3 grid((P * ld2n + 255) / 256, ((pv.N + P - 1) / P + vrows - 1) / vrows, pv.B);
-        if (t.group_rows == 16) {
+    const Rank2Plan p = rank2_plan_of(pv, t, full_width);
+    if (p.kind == RANK2_PACKED) {
+        const bool nt = p.nontemporal != 0;
+        dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+        if (p.group_rows == 16) {
             if (nt) hipLaunchKernelGGL((k_rank2_packed<16, true>), grid, dim3(256), 0, s, pv.sigma, pv.Kg, pv.Gh, pv.rec, pv.state,
-                                       pv.N, pv.ld, pv.sigma_stride, P, vrows);
+                                       pv.N, pv.ld, pv.sigma_stride, p.P, p.rows);
             else hipLaunchKernelGGL((k_rank2_packed<16, false>), grid, dim3(256), 0, s, pv.sigma, pv.Kg, pv.Gh, pv.rec, pv.state,
-                                    pv.N, pv.ld, pv.sigma_stride, P, vrows);
+                                    pv.N, pv.ld, pv.sigma_stride, p.P, p.rows);
         } else {
             if (nt) hipLaunchKernelGGL((k_rank2_packed<8, true>), grid, dim3(256), 0, s, pv.sigma, pv.Kg, pv.Gh, pv.rec, pv.state,
-                                       pv.N, pv.ld, pv.sigma_stride, P, vrows);
+                                       pv.N, pv.ld, pv.sigma_stride, p.P, p.rows);
             else hipLaunchKernelGGL((k_rank2_packed<8, false>), grid, dim3(256), 0, s, pv.sigma, pv.Kg, pv.Gh, pv.rec, pv.state,
-                                    pv.N, pv.ld, pv.sigma_stride, P, vrows);
+                                    pv.N, pv.ld, pv.sigma_stride, p.P, p.rows);
         }
         return;
     }
-    const bool resident = rank2_resident(pv, t);
-    switch (u) {
-        case 2: launch_rank2_u<2>(pv, rows, nt, s, resident); break;
-        case 4: launch_rank2_u<4>(pv, rows, nt, s, resident); break;
-        case 16: launch_rank2_u<16>(pv, rows, nt, s, resident); break;
-        default: launch_rank2_u<8>(pv, rows, nt, s, resident); break;
+    switch (p.group_rows) {
+        case 2: launch_rank2_u<2>(pv, p, s); break;
+        case 4: launch_rank2_u<4>(pv, p, s); break;
+        case 16: launch_rank2_u<16>(pv, p, s); break;
+        default: launch_rank2_u<8>(pv, p, s); break;
     }
 }
 

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ekf_rank2_plan.hpp"
+
 namespace ekf {
 
 constexpr double kPI = 3.14159265358979323846;  // rigid2d/include/rigid2d/rigid2d.hpp:13
@@ -464,26 +466,10 @@ __device__ __forceinline__ void wave_terms_s(int lane, const double* H, double r
     if (lane < 4) outSi[lane] = si;
 }
 
-// Leading dimension of Sigma, the factor vectors and the state: N rounded up to 16 doubles (rows on 128-byte lines), and
-// to 256 doubles -- rows on 2-KB boundaries -- where that costs at most 1/32 of a row (n = 1000: 2003 -> 2048, n = 5000:
-// 10003 -> 10240).  The strip-form flush reads a row as 2-KB pieces, one per workgroup: on a 2-KB boundary a piece is one
-// DRAM page visit instead of two halves (48.3 -> 47.0 ms at 64 pending vectors, 46.8 -> 43.9 at 2; k_rank2 40.09 -> 39.90:
-// profiles/r04/ld_alignment_ab.txt).
-inline int pick_ld(int N) {
-    const int wide = (N + 255) / 256 * 256;
-    return (wide - N) * 32 <= N ? wide : (N + 15) / 16 * 16;
-}
+// pick_ld (the leading dimension of Sigma, the factor vectors and the state), Rank2Tuning and the launch plan of the eager
+// rank-2 correction live in ekf_rank2_plan.hpp (host only, no HIP).
 
 // ---- host-side launchers (ekf_kernels.hip) ---------------------------------------------------
-struct Rank2Tuning {
-    int rows_per_block;  // <= 0: automatic
-    int nontemporal;     // < 0: automatic
-    int group_rows;      // rows per load/store group U in {2,4,8}; other values: automatic
-    int row_packing;     // 1: narrow full-width views may take the row-packed kernel (EKF_FORM_ROW_PACKING)
-    int strip_flush;     // delayed mode: 0 never, 1 automatic, 2 always the strip-form flush (EKF_FORM_STRIP_FLUSH*)
-    int tile_queue;      // 1: big pools stream the rank-2 update as resident workgroups on one tile queue (EKF_FORM_TILE_QUEUE)
-};
-
 void launch_init(const PoolView& pv, hipStream_t s);
 // data_association() of a single filter ends here: the association record and the call's J decisions go to mapped host
 // memory, then the sequence number (host layout: [record 32 B | seq 4 B | .. | decisions from byte 64])
@@ -520,10 +506,8 @@ void launch_gain(const PoolView& pv, const CmdSrc& src, hipStream_t s);
 // full_width: the caller guarantees valid K / G scratch over the whole row and column range (known-association paths),
 // which lets narrow maps take the row-packed kernel
 void launch_rank2(const PoolView& pv, const Rank2Tuning& t, hipStream_t s, bool full_width = false);
-int rank2_packing(const PoolView& pv, const Rank2Tuning& t);
-// the k_rank2<U, NT, TPB> instantiation and rows per workgroup launch_rank2 takes for this view (report hook)
-void rank2_variant(const PoolView& pv, const Rank2Tuning& t, int* u, int* nontemporal, int* tpb, int* rows);
-bool rank2_resident(const PoolView& pv, const Rank2Tuning& t);   // the launch runs as k_rank2_queue (EKF_FORM_TILE_QUEUE)
+// the plan launch_rank2 launches from for this view (ekf_rank2_plan.hpp; the report hooks read it too)
+Rank2Plan rank2_plan_of(const PoolView& pv, const Rank2Tuning& t, bool full_width);
 // Same update restricted to the rows of the touched set (exact: every other row has K = 0).
 // max_touched: host-side upper bound of touch_count over the pool (sizes the grid).
 void launch_rank2_active(const PoolView& pv, const Rank2Tuning& t, int max_touched, hipStream_t s);
@@ -653,7 +637,8 @@ void launch_pool_step_unknown(const PoolView& pv, const double* meas, const int*
 void launch_pool_step_unknown_delayed(const PoolView& pv, const double* meas, const int* count, int jmax, int min_active,
                                       int* assoc_out, const Pending& pend, unsigned long long* corr_counter, int* cnt_scratch,
                                       double* blocks, const double* pred /* [B][2] (a10, a20) of the step's prediction */,
-                                      hipStream_t s, const double* spec = nullptr, const int* specw = nullptr);
+                                      hipStream_t s, const double* spec = nullptr, const int* specw = nullptr,
+                                      unsigned long long* spec_cnt = nullptr /* [2] test hook: guesses compared / matched */);
 int step_pending_pairs_max();   // pairs a filter can carry between flushes in that mode
 // Delayed mode, in front of launch_pool_step_unknown_delayed when pairs of earlier steps are pending: the "old part" of
 // what the step's gains will need.  A reading's gain needs Sigma(r, c5) and Sigma(c5, r) of its winner as they stand now =

@@ -234,12 +234,15 @@ struct Pool {
     // pools' delayed association: the old part of a step's gains for the guessed winners (ekf_kernels.hpp, launch_pool_step_spec)
     double* spec = nullptr;        // [B][spec_rows()][ld]
     int* specw = nullptr;          // [B][kCallV]
+    // test hook (ekf_batch_spec_counts): [0] readings whose decision was compared with the guesses, [1] those that found
+    // their winner among them (the step kernel's decision lane adds to them)
+    unsigned long long* spec_cnt = nullptr;
     int step_speculate = 1;        // EKF_FORM_STEP_SPECULATE
     ekf_status ensure_spec() {
-        if (!spec) {
-            EKFC(dalloc(&spec, (size_t)pv.B * ekf::spec_rows() * pv.ld));
-            EKFC(dalloc(&specw, (size_t)pv.B * ekf::kCallV));
-        }
+        if (!spec)
+            EKFC(mem.replace_group({target(&spec, (size_t)pv.B * ekf::spec_rows() * pv.ld), target(&specw, (size_t)pv.B * ekf::kCallV),
+                                    target(&spec_cnt, 2, Fill::kZero)},
+                                   "Pool", "the speculation buffers"));
         return EKF_OK;
     }
     ekf_status ensure_blk_cache() {
@@ -541,6 +544,7 @@ struct Pool {
         std::fill(host_touched.begin(), host_touched.end(), 0);
         ekf::launch_init(pv, stream);
         HIPC(hipGetLastError());
+        if (spec_cnt) HIPC(hipMemsetAsync(spec_cnt, 0, 2 * sizeof(*spec_cnt), stream));
         init_flag = 0;
         dev_known_count = 0;  // k_init resets the association record
         return EKF_OK;

@@ -42,7 +42,8 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
                                                                     int pair_rows, double* __restrict__ blocks_all,
                                                                     const double* __restrict__ pred, int sym,
                                                                     const double* __restrict__ spec_all,
-                                                                    const int* __restrict__ specw_all) {
+                                                                    const int* __restrict__ specw_all,
+                                                                    unsigned long long* __restrict__ spec_cnt) {
     constexpr int kPairs = DELAYED ? kStepPendingPairs : kCallV;
     // cnt_out == nullptr: the final pass runs here (one workgroup streams its filter's covariance).  Otherwise the step
     // ends with the pairs in Uall / Vall (rows beyond the filter's pair count zero-filled up to `zero_upto` pairs) and
@@ -250,8 +251,13 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
             out[j] = sh_lm;
             if (active) sh_applied++;
             int slot = -1;   // the launch in front guessed this winner (k_pool_step_spec): its old part is ready
-            if (DELAYED && spec_all && active && !is_new)
+            if (DELAYED && spec_all && active && !is_new) {
                 for (int q = 0; q < kCallV; q++) if (specw_all[(size_t)b * kCallV + q] == idx) { slot = q; break; }
+                if (spec_cnt) {   // test hook: readings compared with the guesses / found among them
+                    atomicAdd(spec_cnt, 1ull);
+                    if (slot >= 0) atomicAdd(spec_cnt + 1, 1ull);
+                }
+            }
             sh_slot = slot;
         }
         __syncthreads();
@@ -656,15 +662,16 @@ void launch_pool_step_unknown(const PoolView& pv, const double* meas, const int*
                               int* assoc_out, double* U, double* V, unsigned long long* corr_counter, hipStream_t s,
                               int* cnt_out, int zero_upto, double* blocks) {
     hipLaunchKernelGGL(k_pool_step_unknown<false>, dim3(pv.B), dim3(kStepThreads), 0, s, pv, meas, count, jmax, min_active,
-                       assoc_out, U, V, corr_counter, cnt_out, zero_upto, 0, 2 * kCallV, blocks, nullptr, 0, nullptr, nullptr);
+                       assoc_out, U, V, corr_counter, cnt_out, zero_upto, 0, 2 * kCallV, blocks, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
 void launch_pool_step_unknown_delayed(const PoolView& pv, const double* meas, const int* count, int jmax, int min_active,
                                       int* assoc_out, const Pending& pend, unsigned long long* corr_counter, int* cnt_scratch,
-                                      double* blocks, const double* pred, hipStream_t s, const double* spec, const int* specw) {
+                                      double* blocks, const double* pred, hipStream_t s, const double* spec, const int* specw,
+                                      unsigned long long* spec_cnt) {
     hipLaunchKernelGGL(k_pool_step_unknown<true>, dim3(pv.B), dim3(kStepThreads), 0, s, pv, meas, count, jmax, min_active,
                        assoc_out, pend.U, pend.V, corr_counter, cnt_scratch, jmax, pend.count / 2, pend.cap, blocks, pred,
-                       pend.symmetric != 0, spec, specw);
+                       pend.symmetric != 0, spec, specw, spec_cnt);
 }
 
 int step_pending_pairs_max() { return kStepPendingPairs; }

@@ -191,6 +191,10 @@ ekf_status ekf_batch_get_forms(ekf_batch_handle hb, unsigned* forms);
  * [4] per-landmark rank-2 streams, [5] step-fused launches with a separate pass, [6] mirrored flushes (symmetric
  * option of ekf_set_update_mode), [7] delayed gain launches that read the column panel (EKF_FORM_COLUMN_PANEL). */
 ekf_status ekf_batch_form_counts(ekf_batch_handle hb, long long counts[8]);
+/* Test hook of EKF_FORM_STEP_SPECULATE, since creation / ekf_batch_reset: out[0] readings of delayed unknown-association
+ * steps whose decision (an active re-observation) was compared with the guesses of the launch in front, out[1] those that
+ * found their winner among the guesses and continued from its rebuilt rows (out[1] <= out[0]; both 0 with the form off). */
+ekf_status ekf_batch_spec_counts(ekf_batch_handle hb, long long out[2]);
 
 /* Active-set covariance update (opt-in, default 0; reported separately from the dense contract path):
  * the eager correction streams only the rows of the TOUCHED set -- the pose rows and the rows of landmarks
@@ -304,12 +308,17 @@ ekf_status ekf_batch_checksum(ekf_batch_handle hb, double out[4]);
  * rows per load/store group (2, 4, 8 or 16).  0 (nontemporal: < 0) restores the automatic choice.
  * Results do not depend on them, bit for bit. */
 ekf_status ekf_batch_set_tuning(ekf_batch_handle hb, int rows_per_block, int nontemporal, int group_rows);
-/* Report hook: the instantiation ekf::k_rank2<group_rows, nontemporal, threads> and the rows per workgroup that a
- * full-width eager correction of this pool launches (bench.py ties its PMC traffic record to this name). */
+/* Report hooks of the launch a full-width eager correction of this pool makes (bench.py ties its PMC traffic record to the
+ * kernel's name); all three read the one plan the launcher launches from.
+ * _packing: P, the rows the row-packed kernel streams as one virtual row; 1 = the plain kernel (EKF_FORM_ROW_PACKING).
+ * _variant: P == 1: the instantiation ekf::k_rank2<group_rows, nontemporal, threads> and its rows per workgroup;
+ *           P > 1: ekf::k_rank2_packed<group_rows, nontemporal>, threads = 256, and its VIRTUAL rows per workgroup.
+ * _resident: the launch runs as resident workgroups on one tile queue (ekf::k_rank2_queue<...>, EKF_FORM_TILE_QUEUE);
+ *           0 whenever P > 1 (the packed kernel is taken first). */
 ekf_status ekf_batch_rank2_variant(ekf_batch_handle hb, int* group_rows, int* nontemporal, int* threads,
                                    int* rows_per_block);
-/* ... and whether that launch runs as resident workgroups on one tile queue (ekf::k_rank2_queue<...>, EKF_FORM_TILE_QUEUE). */
 ekf_status ekf_batch_rank2_resident(ekf_batch_handle hb, int* resident);
+ekf_status ekf_batch_rank2_packing(ekf_batch_handle hb, int* P);
 ekf_status ekf_set_tuning(ekf_handle h, int rows_per_block, int nontemporal, int group_rows);
 
 /* ---- on-device Monte-Carlo inputs and consistency statistics --------

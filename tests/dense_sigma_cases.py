@@ -34,6 +34,23 @@ DELAYED_SINGLE_N, DELAYED_SINGLE_K, DELAYED_SINGLE_STEPS = 200, (1, 3, 16, 64), 
 POOL_CALLFUSED = ((7, 400, 5), (5, 130, 12), (10, 1000, 2), (6, 401, 7), (3, 640, 16))   # (B, n, vmax) of test_call_fused_pool_bitwise_and_vs_checker
 POOL_PACKED = ((200, 64), (60, 540), (376, 20))          # (n, B) of test_row_packed_rank2_is_bit_identical
 POOL_PACKED_VMAX = 3
+# k_rank2_packed at the edge of its heuristic: (n, B, P) from tests/golden/rank2_packing_table.txt (the rows of
+# tests/cpp/rank2_plan_check.cpp's table; tests/test_rank2_plan_host.py holds this list against it).  B is the SMALLEST pool
+# of that map size that clears the work floor B * N * ld/2 >= 256 * 256 * 64, so every case holds 67 MB of Sigma.
+POOL_PACKED_PLAN = (
+    (55, 580, 4),     # ld/2 = 64, the narrowest map that packs; N = 113 = 28 * 4 + 1: the last virtual row holds ONE sub-row
+    (159, 78, 3),     # N = 321 = 107 * 3: no ragged row; ld/2 = 168 is no multiple of 64: wavefronts straddle two sub-rows
+    (79, 297, 17),    # P = 17, the largest P any pool takes (every row of the table is < 100 MB); ld/2 = 88, N = 161 = 9 * 17 + 8
+    (367, 16, 2),     # P = 2, the smallest; ld/2 = 376; N = 737 is odd: again one sub-row in the last virtual row
+)
+# all four instantiations k_rank2_packed<8|16, false|true> on one shape: set_tuning(rows_per_block, nontemporal, group_rows).
+# 40 virtual rows per workgroup: ceil(321 / 3) = 107 = 2 * 40 + 27 (a short last block), and with 8-row groups 5 groups per
+# block (the three-buffer ring goes round once, two groups left), 3 groups + 3 single rows in the last; with 16-row groups 2.
+POOL_PACKED_TUNING_N, POOL_PACKED_TUNING = 159, ((40, 0, 8), (40, 1, 8), (40, 0, 16), (40, 1, 16))
+POOL_PACKED_BELOW = (159, 77)                            # (n, B) one filter under the work floor: P = 1, the plain kernel
+# (n, B, P): the smallest pool of n = 376 (rows of 768 doubles, util(1) = 0.75) that is big enough for the tile queue on 256
+# CUs: with packing on the launch is packed (and the hook must not say queue), with packing off it is the queue.  400 MB.
+POOL_PACKED_QUEUE = (376, 86, 2)
 POOL_QUEUE = ((500, 80), (1000, 24))                     # (n, B) of test_rank2_tile_queue_is_bit_identical
 POOL_QUEUE_VMAX = 2
 POOL_ACTIVE = (2, 130, 4)                                # (B, n, vmax)
@@ -291,6 +308,10 @@ def gpu_case_logs():
         out.append((f"pool call-fused B={B} n={n}", survey_log(n, vmax, B=B, seed=400 + n), (0, B - 1), False))
     for n, B in POOL_PACKED:
         out.append((f"pool row-packed n={n} B={B}", survey_log(n, POOL_PACKED_VMAX, B=B, seed=500 + n), (0, B - 1), False))
+    for n, B, _ in POOL_PACKED_PLAN + (POOL_PACKED_QUEUE,):
+        out.append((f"pool row-packed at the work floor n={n} B={B}", packed_plan_log(n, B), (0, B - 1), False))
+    n, B = POOL_PACKED_BELOW
+    out.append((f"pool under the work floor n={n} B={B}", packed_plan_log(n, B), (0, B - 1), False))
     for n, B in POOL_QUEUE:
         out.append((f"pool tile queue n={n} B={B}", survey_log(n, POOL_QUEUE_VMAX, B=B, seed=600 + n), (0, B - 1), False))
     B, n, vmax = POOL_ACTIVE
@@ -309,11 +330,18 @@ def gpu_case_logs():
     for B, n, k, vmax, strip in POOL_PANEL:
         for cur in ("on", "off"):
             out.append((f"pool current columns {cur} B={B} n={n} k={k}", survey_log(n, vmax, B=B, seed=900 + n, extra_steps=POOL_PANEL_STEPS), (0, B - 1), False))
+    for rows, nt, group in POOL_PACKED_TUNING:
+        n, B = POOL_PACKED_TUNING_N, dict((c[0], c[1]) for c in POOL_PACKED_PLAN)[POOL_PACKED_TUNING_N]
+        out.append((f"pool row-packed n={n} B={B} set_tuning({rows}, {nt}, {group})", packed_plan_log(n, B), (0, B - 1), False))
     for B, n in POOL_UNKNOWN:
         for spec in ("on", "off"):
             out.append((f"pool unknown delayed k={POOL_UNKNOWN_DELAYED_K} speculate {spec} B={B} n={n}", unknown_case_log(B, n), (0, B - 1), True))
     out.append(("maha", survey_log(MAHA_N, SINGLE_VMAX, seed=100 + MAHA_N), (0,), False))
     return out
+
+
+def packed_plan_log(n, B):
+    return survey_log(n, POOL_PACKED_VMAX, B=B, seed=550 + n)
 
 
 def unknown_case_log(B, n):

@@ -527,14 +527,16 @@ def test_delayed_data_association_with_a_step_nobody_reads(hip, k, silent):
         assert_parity(snap[1][2][b], snap[1][3][i], snap[0][2][b], snap[0][3][i], FP64_TOL, f"delayed vs eager, filter {b}")
 
 
-@pytest.mark.parametrize("k,surveyed_share,symmetric", [(32, 1.0, False), (64, 0.6, False), (24, 1.0, False), (32, 1.0, True)])
-def test_speculative_old_part_is_bit_identical(hip, k, surveyed_share, symmetric):
-    """EKF_FORM_STEP_SPECULATE (pools' delayed data_association()): a launch in front of every step guesses each reading's
-    winner and rebuilds "stored covariance minus the pairs of earlier steps" for the guessed landmarks once per step
-    (k_pool_step_spec); the step kernel continues from it where its decision agrees (ekf_slam.cpp:300-309 decides, :331-390
-    corrects) and rebuilds from scratch where it does not -- new landmarks, readings between the gates, filters still
-    discovering their map.  Same operations in the same order: decisions, known counts, states and covariances must be
-    BIT-identical to the run with the form off; ragged reading counts, filters that sit steps out, a run boundary."""
+SPECULATE_CASES = [(32, 1.0, False), (64, 0.6, False), (24, 1.0, False), (32, 1.0, True)]
+_speculate_runs = {}
+
+
+def _speculate_run(hip, k, surveyed_share, symmetric):
+    """the run of test_speculative_old_part_is_bit_identical with EKF_FORM_STEP_SPECULATE on and off (once per case: the
+    tests below share it): [(decisions, known counts, states, covariances, spec_counts())] for on, off"""
+    key = (k, surveyed_share, symmetric)
+    if key in _speculate_runs:
+        return _speculate_runs[key]
     n, B, T = 150, 10, 12
     cfg = synth.SimConfig(n=n, steps=T, filters=B, seed=6161, half_extent=5.0, min_spacing=0.3, max_visible_dis=1.4, vmax=8,
                           v_cmd=1.0, w_cmd=0.6)
@@ -556,10 +558,41 @@ def test_speculative_old_part_is_bit_identical(hip, k, surveyed_share, symmetric
         bt.set_known_counts(known0)
         bt.set_update_mode(k, symmetric_gather=symmetric)
         bt.upload_unknown_log(log.twist, cnt, meas)
+        assert bt.spec_counts() == (0, 0)
         bt.run_unknown(0, 7); bt.run_unknown(7, T)
-        snap.append((bt.decisions().copy(), bt.known_counts().copy(), [bt.state(b) for b in range(B)], [bt.cov(b) for b in range(B)]))
+        snap.append((bt.decisions().copy(), bt.known_counts().copy(), [bt.state(b) for b in range(B)], [bt.cov(b) for b in range(B)],
+                     bt.spec_counts()))
         bt.close()
+    _speculate_runs[key] = snap
+    return snap
+
+
+@pytest.mark.parametrize("k,surveyed_share,symmetric", SPECULATE_CASES)
+def test_speculative_old_part_is_bit_identical(hip, k, surveyed_share, symmetric):
+    """EKF_FORM_STEP_SPECULATE (pools' delayed data_association()): a launch in front of every step guesses each reading's
+    winner and rebuilds "stored covariance minus the pairs of earlier steps" for the guessed landmarks once per step
+    (k_pool_step_spec); the step kernel continues from it where its decision agrees (ekf_slam.cpp:300-309 decides, :331-390
+    corrects) and rebuilds from scratch where it does not -- new landmarks, readings between the gates, filters still
+    discovering their map.  Same operations in the same order: decisions, known counts, states and covariances must be
+    BIT-identical to the run with the form off; ragged reading counts, filters that sit steps out, a run boundary.
+    That the form ENGAGED is shown by spec_counts(): with it on, readings were compared with the guesses and some continued
+    from a guessed slot (the consuming branch, sh_slot >= 0 in k_pool_step_unknown); with it off, none."""
+    B = 10
+    snap = _speculate_run(hip, k, surveyed_share, symmetric)
+    eligible, hits = snap[0][4]
+    print(f"measured speculation k={k} surveyed_share={surveyed_share} symmetric={symmetric}: eligible {eligible}, hits {hits}")
+    assert 0 < hits <= eligible, (eligible, hits)
+    assert eligible <= (snap[0][0] >= 0).sum()              # (new landmarks are corrected without a comparison)
+    assert snap[1][4] == (0, 0), snap[1][4]
     assert np.array_equal(snap[0][0], snap[1][0]) and np.array_equal(snap[0][1], snap[1][1])
     assert (snap[0][0] >= 0).sum() > 300
     for b in range(B):
         assert np.array_equal(snap[0][2][b], snap[1][2][b]) and np.array_equal(snap[0][3][b], snap[1][3][b]), f"filter {b}"
+
+
+def test_speculation_misses_as_well_as_hits(hip):
+    """over the cases above at least one run has a reading whose decision is NOT among the guesses (hits < eligible): the
+    rebuild-from-scratch branch runs beside the consuming one inside a speculating launch"""
+    counts = {c: _speculate_run(hip, *c)[0][4] for c in SPECULATE_CASES}
+    print(f"measured speculation (eligible, hits) per case: {counts}")
+    assert any(hits < eligible for eligible, hits in counts.values()), counts

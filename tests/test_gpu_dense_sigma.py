@@ -201,6 +201,17 @@ def test_pool_eager_and_call_fused(hip, oracle, B, n, vmax):
     print(f"measured pool call-fused B={B} n={n}: {max(res[True][0], res[False][0]):.3e}")
 
 
+def _assert_packing(bt, packed, P=None, plain="ekf::k_rank2<"):
+    """the plan the launcher launches from (BatchEKF.rank2_packing / rank2_kernel): the packed kernel with P > 1 rows per
+    virtual row, or P = 1 and the plain kernel"""
+    got, kname = bt.rank2_packing(), bt.rank2_kernel()[0]
+    if packed:
+        assert got > 1 and "k_rank2_packed" in kname and "k_rank2_queue" not in kname, (got, kname)
+        assert P is None or got == P, (got, P)
+    else:
+        assert got == 1 and kname.startswith(plain), (got, kname)
+
+
 @pytest.mark.parametrize("n,B", cases.POOL_PACKED)
 def test_pool_row_packed(hip, oracle, n, B):
     """k_rank2_packed (test_row_packed_rank2_is_bit_identical's shapes) against the plain kernel bit for bit and against the
@@ -214,6 +225,7 @@ def test_pool_row_packed(hip, oracle, n, B):
             bt.set_call_fused(False)   # the per-landmark rank-2 stream is what packs rows
             bt.set_row_packing(packed)
             assert bool(bt.forms & hip.FORM_ROW_PACKING) == packed and not bt.forms & hip.FORM_CALL_FUSED
+            _assert_packing(bt, packed)
         res[packed] = _eager_pool_run(hip, log, configure, traces, filters, f"row packing {packed} n={n} B={B}",
                                       "k_rank2_packed" if packed else "k_rank2")
         assert res[packed][3]["rank2_streams"] > 0 and res[packed][3]["call_fused_passes"] == 0
@@ -222,6 +234,91 @@ def test_pool_row_packed(hip, oracle, n, B):
         _same_bits(res[True][1][b], res[False][1][b], f"n={n} B={B} filter {b}: packed vs plain")
     assert np.allclose(res[True][2], res[False][2], rtol=1e-12)
     print(f"measured pool row-packed n={n} B={B}: {max(res[True][0], res[False][0]):.3e}")
+
+
+def _packed_run(hip, log, traces, filters, name, packed, P=None, tuning=None, plain="ekf::k_rank2<", want_name=None):
+    def configure(bt):
+        bt.set_call_fused(False)   # the per-landmark rank-2 stream is what packs rows
+        bt.set_row_packing(packed)
+        if tuning:
+            bt.set_tuning(*tuning)
+        _assert_packing(bt, packed, P, plain)
+        if want_name:
+            assert bt.rank2_kernel() == want_name, (bt.rank2_kernel(), want_name)
+    res = _eager_pool_run(hip, log, configure, traces, filters, name, "k_rank2_packed" if packed else "k_rank2")
+    assert res[3]["rank2_streams"] > 0 and res[3]["call_fused_passes"] == 0
+    return res
+
+
+@pytest.mark.parametrize("n,B,P", cases.POOL_PACKED_PLAN)
+def test_pool_row_packed_at_the_work_floor(hip, oracle, n, B, P):
+    """k_rank2_packed on the smallest pools that take it (cases.POOL_PACKED_PLAN says what each shape is there for), with the
+    P the plan reports asserted: against the plain kernel bit for bit, filters 0, B // 2, B - 1 against the checker, the pool
+    checksum against the sum over all filters' checker results"""
+    log = cases.packed_plan_log(n, B)
+    filters = [0, B // 2, B - 1]
+    traces, sums = _traces(oracle, log, filters, want_sums=True)
+    res = {packed: _packed_run(hip, log, traces, filters, f"row packing {packed} n={n} B={B} P={P}", packed, P) for packed in (True, False)}
+    for packed in (True, False):
+        assert np.abs(res[packed][2] - sums).max() / np.abs(sums).max() < 1e-9, (res[packed][2], sums)
+    for b in filters:
+        _same_bits(res[True][1][b], res[False][1][b], f"n={n} B={B} P={P} filter {b}: packed vs plain")
+    assert np.allclose(res[True][2], res[False][2], rtol=1e-12)
+    print(f"measured pool row-packed at the work floor n={n} B={B} P={P}: {max(res[True][0], res[False][0]):.3e}")
+
+
+def test_pool_row_packed_instantiations(hip, oracle):
+    """k_rank2_packed<8|16, false|true> on one shape, each named by the plan hook, with 40 virtual rows per workgroup (a short
+    last block; several row groups per block): all bit-identical to the plain kernel and against the checker"""
+    n = cases.POOL_PACKED_TUNING_N
+    _, B, P = next(c for c in cases.POOL_PACKED_PLAN if c[0] == n)
+    log = cases.packed_plan_log(n, B)
+    filters = [0, B // 2, B - 1]
+    traces, _ = _traces(oracle, log, filters)
+    plain = _packed_run(hip, log, traces, filters, f"plain n={n} B={B}", False)
+    worst = plain[0]
+    for rows, nt, group in cases.POOL_PACKED_TUNING:
+        want = (f"ekf::k_rank2_packed<{group},{'true' if nt else 'false'}>", rows)
+        res = _packed_run(hip, log, traces, filters, f"{want[0]} rows_per_block={rows} n={n} B={B}", True, P,
+                          tuning=(rows, nt, group), want_name=want)
+        for b in filters:
+            _same_bits(res[1][b], plain[1][b], f"n={n} B={B} filter {b}: {want[0]} vs plain")
+        worst = max(worst, res[0])
+    print(f"measured pool row-packed instantiations n={n} B={B}: {worst:.3e}")
+
+
+def test_pool_under_the_work_floor_stays_plain(hip, oracle):
+    """one filter fewer than the smallest pool that packs: P = 1 and the plain kernel with packing allowed, and still the
+    checker's result"""
+    n, B = cases.POOL_PACKED_BELOW
+    log = cases.packed_plan_log(n, B)
+    filters = [0, B // 2, B - 1]
+    traces, sums = _traces(oracle, log, filters, want_sums=True)
+
+    def configure(bt):
+        bt.set_call_fused(False)
+        assert bt.forms & hip.FORM_ROW_PACKING
+        _assert_packing(bt, False)
+    res = _eager_pool_run(hip, log, configure, traces, filters, f"under the work floor n={n} B={B}", "k_rank2")
+    assert res[3]["rank2_streams"] > 0
+    assert np.abs(res[2] - sums).max() / np.abs(sums).max() < 1e-9, (res[2], sums)
+    print(f"measured pool under the work floor n={n} B={B}: {res[0]:.3e}")
+
+
+def test_pool_row_packed_where_the_tile_queue_would_run(hip, oracle):
+    """a pool big enough for the tile queue whose rows do not fill their strips: with packing on the launch is packed and the
+    hooks say so (ekf_batch_rank2_resident used to say queue), with packing off it is k_rank2_queue; bit-identical, filters
+    0, B // 2, B - 1 against the checker"""
+    n, B, P = cases.POOL_PACKED_QUEUE
+    log = cases.packed_plan_log(n, B)
+    filters = [0, B // 2, B - 1]
+    traces, _ = _traces(oracle, log, filters)
+    res = {packed: _packed_run(hip, log, traces, filters, f"row packing {packed} n={n} B={B}", packed, P, plain="ekf::k_rank2_queue<")
+           for packed in (True, False)}
+    for b in filters:
+        _same_bits(res[True][1][b], res[False][1][b], f"n={n} B={B} filter {b}: packed vs queue")
+    assert np.allclose(res[True][2], res[False][2], rtol=1e-12)
+    print(f"measured pool row-packed against the tile queue n={n} B={B}: {max(res[True][0], res[False][0]):.3e}")
 
 
 @pytest.mark.parametrize("n,B", cases.POOL_QUEUE)

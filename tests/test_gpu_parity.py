@@ -572,6 +572,12 @@ def test_row_packed_rank2_is_bit_identical(hip, n, B):
         bt = hip.BatchEKF(B, n)
         bt.set_call_fused(False)   # the per-landmark rank-2 stream is what packs rows
         bt.set_row_packing(packed)
+        # the plan the launcher launches from: without this both legs could run the plain kernel and compare equal
+        P, kname = bt.rank2_packing(), bt.rank2_kernel()[0]
+        if packed:
+            assert P > 1 and "k_rank2_packed" in kname, (P, kname)
+        else:
+            assert P == 1 and kname.startswith("ekf::k_rank2<"), (P, kname)
         bt.upload_known_log(log.twist, log.lm_idx, log.z_xy, log.init_xy)
         bt.run_known()
         res.append(([bt.state(b) for b in (0, B // 2, B - 1)], [bt.cov(b) for b in (0, B // 2, B - 1)], bt.checksum()))
