@@ -62,6 +62,7 @@ SYMBOLS = [
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
     "ekf_dense64_frame_launch_info", "ekf_dense64_map_congruence", "ekf_dense64_reframe_landmarks",
+    "ekf_dense64_join_launch_info", "ekf_dense64_join_congruence", "ekf_dense64_join_map",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident", "ekf_batch_rank2_packing", "ekf_batch_spec_counts",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
@@ -285,6 +286,9 @@ def load():
         "ekf_dense64_frame_launch_info": [h, _ip, _ip, _ip],
         "ekf_dense64_map_congruence": [h, _dp, _dp, _dp],
         "ekf_dense64_reframe_landmarks": [h, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp],
+        "ekf_dense64_join_launch_info": [h, _ip, _ip, _ip],
+        "ekf_dense64_join_congruence": [h, h, _dp, _dp, _dp],
+        "ekf_dense64_join_map": [h, h, _dp, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
@@ -1313,6 +1317,56 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_frame_launch_info(self._h, C.byref(tr), C.byref(tc), C.byref(th)))
         return {"tile_rows": tr.value, "tile_cols": tc.value, "threads": th.value}
 
+    def _join_source(self, src):
+        self._open()
+        if not isinstance(src, DensePropagator64):
+            raise ValueError("the source must be a DensePropagator64")
+        src._open()
+        return src
+
+    def join_congruence(self, src, G, E):
+        """The covariance of src's live corner (Nb states) joined onto this handle's (ekf_dense64_join_congruence,
+        include/ekfslam.h): Y = D Sigma_B D^T + E Sigma_pp E^T at the indices 0, 1, 2, live, live + 1, ..., the cross terms
+        E P and Pc E^T beside it; Sigma[3:live, 3:live] is not touched and src is read only.  G 2 x 2, E Nb x 3, every
+        entry multiplied through.  Both live dimensions must be 3 + 2 n.  Flushes the pending rows of both handles; touches
+        neither state; afterwards live is live + Nb - 3.  Returns elapsed_ms"""
+        src = self._join_source(src)
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        if G.shape != (2, 2):
+            raise ValueError("G must be 2 x 2")
+        if src.region_info()["active"]:   # (the library would end it and take the live dimension behind it: E could not be checked)
+            raise ValueError("the source is inside a local region: end it before join_congruence()")
+        if E.shape != (src.live, 3):
+            raise ValueError("E must be (the source's live) x 3")
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_join_congruence(self._h, src._h, _d(G), _d(E), C.byref(ms)))
+        return ms.value
+
+    def join_map(self, src, want_terms=False):
+        """Map joining (ekf_dense64_join_map): src holds a local map in the frame of this handle's robot pose, independent
+        of this map (started at pose 0 with zero pose covariance -- the caller's duty).  The pose becomes the composition
+        (theta not wrapped), src's landmarks are appended in this frame at the states live, live + 1, ..., Sigma as
+        join_congruence() with G and E built on the device.  src keeps its state, its Sigma and its live dimension.
+        Returns elapsed_ms, or with want_terms (G (2, 2), E (Nb, 3), elapsed_ms): join_congruence(src, G, E) gives the same
+        Sigma bit for bit."""
+        src = self._join_source(src)
+        terms = np.empty(4 + 3 * src.N, dtype=np.float64) if want_terms else None   # (a region src is in ends: Nb <= N)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_join_map(self._h, src._h, _d(terms) if want_terms else None, C.byref(ms)))
+        if not want_terms:
+            return ms.value
+        Nb = src.live
+        return terms[:4].reshape(2, 2).copy(), terms[4:4 + 3 * Nb].reshape(Nb, 3).copy(), ms.value
+
+    def join_launch_info(self):
+        """{tile_rows, tile_cols, threads}: the tile of the join's pass over the source's Sigma[3:Nb, 3:Nb] in states
+        (origins at 3 + a tile_rows, 3 + b tile_cols) and its workgroup size (test hook)"""
+        self._open()
+        tr, tc, th = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_join_launch_info(self._h, C.byref(tr), C.byref(tc), C.byref(th)))
+        return {"tile_rows": tr.value, "tile_cols": tc.value, "threads": th.value}
+
     def _sparse_operands(self, cols, Hc, R, nu, max_m):
         """the shape and range checks of a sparse correction -> (cols int32, Hc, R, nu or None, m, s), contiguous"""
         cols = self._index_lists(cols, 1)
@@ -1904,6 +1958,44 @@ class DenseEKFSLAM:
     def robot_frame(self):
         """the map in the robot's own frame (FRAME_ROBOT); call it again before filtering on"""
         return self._framed(lambda: self.handle.reframe(DensePropagator64.FRAME_ROBOT))
+
+    def join(self, other):
+        """map joining (DensePropagator64.join_map): `other` is a DenseEKFSLAM that built a local map in the frame of this
+        filter's robot pose, started at pose 0 and independent of this map.  Its known landmarks become this filter's
+        landmarks known .. known + other.known - 1, the pose becomes the composition of the two; find_duplicates() and
+        merge() then fuse what both maps saw.  States of either filter beyond its known landmarks must be decoupled from
+        them, as for reframe() (coupling() is checked on both).  Two things beyond the library call: both live dimensions
+        are set to 3 + 2 known for the call and put back afterwards -- on `other` too, which like the join itself flushes
+        its pending rows; its state, its covariance values and, on return, its live dimension are as they were (reset or
+        close it) -- and the call is refused once measurement() has placed all n landmarks of either filter, since
+        there is then no "behind the known landmarks" to append to.  Returns elapsed_ms"""
+        if not isinstance(other, DenseEKFSLAM):
+            raise ValueError("join() takes another DenseEKFSLAM")
+        if self._init_flag or other._init_flag:
+            raise ValueError("join() appends behind the known landmarks of data_association(); measurement() placed all n")
+        d, src = self.handle, other.handle
+        if self._known + other._known > self.n:
+            raise ValueError(f"{self._known} + {other._known} landmarks do not fit n = {self.n}")
+        live, W = d.live, 3 + 2 * self._known
+        src_live, Wb = src.live, 3 + 2 * other._known
+        if W > live or Wb > src_live:
+            raise ValueError("the map reaches beyond the live dimension")
+        for h, w, lv in ((d, W, live), (src, Wb, src_live)):
+            if w < lv and h.coupling(w)[0] != 0:
+                raise ValueError(f"states beyond {w} are coupled to the map: a join of the first {w} alone is not exact")
+        if W < live:
+            d.live = W
+        if Wb < src_live:
+            src.live = Wb
+        try:
+            ms = d.join_map(src)
+        finally:
+            if Wb < src_live:
+                src.live = src_live
+            if d.live < live:
+                d.live = live
+        self._known += other._known
+        return ms
 
     def map_nees(self, truth):
         """(state - truth)^T Sigma^-1 (state - truth) over the live dimension against the last factor(): the NEES of the

@@ -7,7 +7,7 @@
 // scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), the health check of the live corner and its
 // exact symmetrisation (ekf_dense64_health.hip), its Cholesky factor with the substitution against it
 // (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), the
-// map re-expressed in another frame (ekf_dense64_frame.hip), and
+// map re-expressed in another frame (ekf_dense64_frame.hip), a second handle's map joined onto it (ekf_dense64_join.hip), and
 // the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
@@ -1149,6 +1149,67 @@ ekf_status ekf_dense64_reframe_landmarks(ekf_dense64_handle d, int mode, double 
     HIPC(hipMemcpyAsync(d->x, ws + pl.off_state, sizeof(double) * pl.Na, hipMemcpyDeviceToDevice, d->stream));
     if (terms_out && !robot) std::fill(terms_out + 4, terms_out + 4 + 3 * (size_t)pl.Na, 0.0);   // (no C was used)
     return finish_timed(d, elapsed_ms, {{terms_out, ws + pl.off_terms, sizeof(double) * (robot ? 4 + 3 * (size_t)pl.Na : 4)}});
+}
+
+// ---- map joining (ekf_dense64_join.hip) -------------------------------------------------------------------------------------
+ekf_status ekf_dense64_join_launch_info(ekf_dense64_handle d, int* tile_rows, int* tile_cols, int* threads) {
+    if (!d || !tile_rows || !tile_cols || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_join_launch_info: null argument");
+    *tile_rows = ekf::kDense64JoinTileRows;
+    *tile_cols = ekf::kDense64JoinTileCols;
+    *threads = ekf::kDense64JoinThreads;
+    return EKF_OK;
+}
+
+namespace {
+// Both calls: the refusals in the header's order (host only: a region that either handle is in stays open when one strikes),
+// the workspace from the destination's ledger, then behind the destination's e0 its pending rows, the source's on the
+// source's own stream with an event the destination's stream waits on, the launches, and the new live dimension.
+// map: G and E are built on the device and the state goes along; otherwise they go up from the caller.
+ekf_status dense64_join(const char* fnc, ekf_dense64_s* dst, ekf_dense64_s* src, bool map, const double* G, const double* E,
+                        double* terms_out, double* elapsed_ms) {
+    const std::string fn = fnc;
+    if (!dst) return fail(EKF_ERR_INVALID, fn + ": null destination handle");
+    if (!src) return fail(EKF_ERR_INVALID, fn + ": null source handle");
+    if (dst == src) return fail(EKF_ERR_INVALID, fn + ": the destination and the source are the same handle");
+    if (dst->device != src->device) return fail(EKF_ERR_INVALID, fn + ": the two handles live on different devices");
+    const RegionLeave leaving_dst(dst), leaving_src(src);   // outside a region's terms: it ends behind the checks and e0
+    const int Na = dst->live, Nb = src->live;
+    if (Na < 3 || Na % 2 == 0 || Nb < 3 || Nb % 2 == 0)
+        return fail(EKF_ERR_INVALID, fn + ": both live dimensions must be 3 + 2 n (a pose and whole landmarks)");
+    if ((long long)Na + Nb - 3 > dst->N)
+        return fail(EKF_ERR_INVALID, fn + ": the joined map (Na + Nb - 3 states) does not fit the destination's N");
+    if (!map && (!G || !E)) return fail(EKF_ERR_INVALID, fn + ": null G or E");
+    HIPC(hipSetDevice(dst->device));
+    const ekf::Dense64JoinPlan pl = ekf::dense64_join_plan(Na, dst->ld, Nb, src->ld);
+    EKFC(dst->join.reserve(dst->mem, sizeof(double) * pl.doubles, false, fnc, "the join's workspace"));
+    double* ws = dst->join.as<double>();
+    const size_t terms_bytes = sizeof(double) * (4 + 3 * (size_t)Nb);
+    if (!map) {
+        HIPC(hipMemcpyAsync(ws + pl.off_terms, G, sizeof(double) * 4, hipMemcpyHostToDevice, dst->stream));
+        HIPC(hipMemcpyAsync(ws + pl.off_terms + 4, E, terms_bytes - sizeof(double) * 4, hipMemcpyHostToDevice, dst->stream));
+    }
+    HIPC(hipEventRecord(dst->e0, dst->stream));
+    dst->flush_pending();
+    src->sigma_needed();   // (on the source's stream)
+    HIPC(hipEventRecord(src->e1, src->stream));
+    HIPC(hipStreamWaitEvent(dst->stream, src->e1, 0));
+    if (map) ekf::launch_dense64_join_state(pl, dst->x, src->x, ws, dst->stream);
+    ekf::launch_dense64_join_congruence(pl, dst->S, src->S, ws, dst->stream);
+    if (map) HIPC(hipMemcpyAsync(dst->x, ws + pl.off_pose, sizeof(double) * 3, hipMemcpyDeviceToDevice, dst->stream));
+    EKFC(finish_timed(dst, elapsed_ms, {{map ? terms_out : nullptr, ws + pl.off_terms, terms_bytes}}));
+    dst->live = pl.Nj;   // (no rows are pending: nothing to widen)
+    dst->pl_live = ekf::dense64_live_plan(dst->pl_full, dst->live);
+    return EKF_OK;
+}
+}  // namespace
+
+ekf_status ekf_dense64_join_congruence(ekf_dense64_handle dst, ekf_dense64_handle src, const double* G, const double* E,
+                                       double* elapsed_ms) {
+    return dense64_join("ekf_dense64_join_congruence", dst, src, false, G, E, nullptr, elapsed_ms);
+}
+
+ekf_status ekf_dense64_join_map(ekf_dense64_handle dst, ekf_dense64_handle src, double* terms_out, double* elapsed_ms) {
+    return dense64_join("ekf_dense64_join_map", dst, src, true, nullptr, nullptr, terms_out, elapsed_ms);
 }
 
 // ---- duplicate landmarks: the all-pairs scan (ekf_dense64_pairs.hip) and the merge, a layer over the calls above ----------

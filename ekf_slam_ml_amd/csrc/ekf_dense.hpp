@@ -374,6 +374,17 @@ void launch_dense64_frame_state(const Dense64FramePlan& p, int mode, const doubl
 // read or written.
 void launch_dense64_frame_congruence(const Dense64FramePlan& p, double* Sigma, double* ws, bool has_C, hipStream_t st);
 
+// ---- map joining (ekf_dense64_join.hip; the definition is include/ekfslam.h's, ekf_dense64_join_congruence; the plan and
+// the workspace are ekf_dense64_layout.hpp's Dense64JoinPlan).  Everything runs on the one stream given: the destination's.
+// One launch: cos and sin of state_dst[0] on the device, G and E into the terms, the composed pose into the staging slot
+// (ws + off_pose; state_dst[0 .. 2] is not written), the source's landmarks in the destination's frame into state_dst[Na ...].
+void launch_dense64_join_state(const Dense64JoinPlan& p, double* state_dst, const double* state_src, double* ws, hipStream_t st);
+// Up to five launches on the terms that sit in the workspace: the snapshot and W, the pass over the source's Sigma[3:Nb, 3:Nb]
+// (Nb > 3), the two rectangles (Na > 3 and Nb > 3), the new pose rows and columns.  The source is read only; of the
+// destination nothing inside [3, Na) x [3, Na) and nothing at an index >= Na + Nb - 3 is read or written.
+void launch_dense64_join_congruence(const Dense64JoinPlan& p, double* Sigma_dst, const double* Sigma_src, double* ws,
+                                    hipStream_t st);
+
 // ---- a local region (ekf_dense64_region.hip; plan and layout in ekf_dense64_region.hpp, the definition is
 // include/ekfslam.h's, ekf_dense64_region_begin): the accumulators Phi, Psi, theta of the compressed filter in `acc`
 // (Dense64RegionPlan::acc_bytes), the two panels of the global update in `scratch` (scratch_bytes).

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ekf_dense.hpp"
+#include "ekf_dense64_rot2.hpp"
 
 namespace ekf {
 
@@ -35,20 +36,7 @@ constexpr int kUnits = kTr / 2 / (kThreads / 64);   // row pairs of a wave
 constexpr int kSmall = 256;                         // threads of the three small kernels
 static_assert(kTc == 2 * 64 && kUnits == 8, "a lane per pair of columns, eight pairs of rows per wave");
 
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef f64x2 f64x2u __attribute__((aligned(8)));   // a pair starts on an odd index: 8-byte aligned only
-
-// (b0, b1) times one row of G: fl(fma(g1, b1, fl(g0 b0))).  The product from the left (G B, down a column of B) and the one
-// from the right (B G^T, along a row of B) are this same expression.
-__device__ __forceinline__ double one_sided(double g0, double g1, double b0, double b1) { return fma(g1, b1, g0 * b0); }
-
-// Z = (G B) G^T for the block B = [a; b] (two rows of two)
-__device__ __forceinline__ void both_sided(const double (&G)[4], f64x2 a, f64x2 b, f64x2* za, f64x2* zb) {
-    const double y00 = one_sided(G[0], G[1], a[0], b[0]), y01 = one_sided(G[0], G[1], a[1], b[1]);
-    const double y10 = one_sided(G[2], G[3], a[0], b[0]), y11 = one_sided(G[2], G[3], a[1], b[1]);
-    *za = f64x2{one_sided(G[0], G[1], y00, y01), one_sided(G[2], G[3], y00, y01)};
-    *zb = f64x2{one_sided(G[0], G[1], y10, y11), one_sided(G[2], G[3], y10, y11)};
-}
+using namespace rot2;   // f64x2, f64x2u, one_sided, both_sided: the rotation of a 2 x 2 block (ekf_dense64_rot2.hpp)
 
 // ---- the state and the terms ----------------------------------------------------------------------------------------------
 // terms: G [4] | C [Na][3].  xs [Na]: the new state.  Thread p: index 0 (p = 0) or the pair (2 p - 1, 2 p).

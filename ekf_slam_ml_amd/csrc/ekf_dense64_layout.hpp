@@ -87,4 +87,39 @@ inline JointLayout joint_layout() {
     return {0, pre, head, rec, xb, pair_lm, pair_j, W_full, W_last, W_last + kF * kR * kR, pair_lm - head};
 }
 }  // namespace d64
+
+// ---- map joining (ekf_dense64_join.hip; the definition is include/ekfslam.h's, ekf_dense64_join_congruence): launch geometry
+// and the workspace, which comes from the DESTINATION's ledger.  Offsets in doubles: the old pose rows P [3][ld] (their first
+// three columns are Sigma_pp) | the old pose columns Pc, transposed [3][ld] | terms = G [4] | E [Nb][3] | W = E Sigma_pp
+// [Nb][3] | the new pose [3] (then one double of padding).  Na, Nb odd and >= 3, Na + Nb - 3 <= the destination's N.
+constexpr int kDense64JoinTileRows = 64;    // the hot pass: tiles of the SOURCE's Sigma[3:Nb, 3:Nb], origins on odd indices
+constexpr int kDense64JoinTileCols = 128;
+constexpr int kDense64JoinThreads = 256;
+constexpr int kDense64JoinCrossRows = 8;    // the two rectangles: a workgroup writes 8 rows of 512 columns
+constexpr int kDense64JoinCrossCols = 2 * kDense64JoinThreads;
+struct Dense64JoinPlan {
+    int Na, Nb, Nj, ld_dst, ld_src;      // Nj = Na + Nb - 3, the joined live dimension
+    int pairs_dst, pairs_src, pairs_j;   // index 0 and the pairs (1, 2), (3, 4), ... below Na, Nb, Nj
+    int corner_gx, corner_gy;            // k_jn_corner's grid (0 x 0 at Nb = 3: not launched)
+    int rows_gx, rows_gy;                // k_jn_cross, X_rows[3:, 3:Na]: (Nb - 3) rows of (Na - 3) columns
+    int cols_gx, cols_gy;                // k_jn_cross, X_cols[3:Na, 3:]: (Na - 3) rows of (Nb - 3) columns
+    size_t off_rows, off_cols, off_terms, off_W, off_pose, doubles;
+};
+inline Dense64JoinPlan dense64_join_plan(int Na, int ld_dst, int Nb, int ld_src) {
+    Dense64JoinPlan p{};
+    p.Na = Na, p.Nb = Nb, p.Nj = Na + Nb - 3, p.ld_dst = ld_dst, p.ld_src = ld_src;
+    p.pairs_dst = (Na + 1) / 2, p.pairs_src = (Nb + 1) / 2, p.pairs_j = (p.Nj + 1) / 2;
+    const int a = Na - 3, b = Nb - 3;
+    auto cdiv = [](int x, int y) { return (x + y - 1) / y; };
+    p.corner_gx = cdiv(b, kDense64JoinTileCols), p.corner_gy = cdiv(b, kDense64JoinTileRows);
+    p.rows_gx = cdiv(a, kDense64JoinCrossCols), p.rows_gy = cdiv(b, kDense64JoinCrossRows);
+    p.cols_gx = cdiv(b, kDense64JoinCrossCols), p.cols_gy = cdiv(a, kDense64JoinCrossRows);
+    p.off_rows = 0;
+    p.off_cols = 3 * (size_t)ld_dst;
+    p.off_terms = 6 * (size_t)ld_dst;
+    p.off_W = p.off_terms + 4 + 3 * (size_t)Nb;
+    p.off_pose = p.off_W + 3 * (size_t)Nb;
+    p.doubles = p.off_pose + 4;
+    return p;
+}
 }  // namespace ekf

@@ -109,6 +109,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf factor_ws;  // Dense64FactorPlan: the verdict word, the per-block records, the diagonal of L
     ekfrt::DeviceBuf whiten;     // ekf_dense64_whiten: the working copy of B and Y, then d2
     ekfrt::DeviceBuf frame;      // Dense64FramePlan (ekf_dense64_map_congruence, ekf_dense64_reframe_landmarks), a function of ld
+    ekfrt::DeviceBuf join;       // Dense64JoinPlan (ekf_dense64_join_congruence, ekf_dense64_join_map) of the DESTINATION, grows with Nb
     ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads

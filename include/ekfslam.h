@@ -1064,7 +1064,7 @@ ekf_status ekf_dense64_coupling(ekf_dense64_handle h, int Na,
  * element, as the live launches do.
  * EVERY OTHER CALL ENDS THE REGION FIRST and then runs as it always did, so no result is ever stale: get_sigma, get_state,
  * set, set_state, propagate, correct, score, swap_blocks, health, symmetrize, factor, coupling, map_congruence,
- * reframe_landmarks, score_landmark_pairs, merge_landmarks, score_readings, joint_operands, associate_joint,
+ * reframe_landmarks, join_congruence, join_map (on either handle), score_landmark_pairs, merge_landmarks, score_readings, joint_operands, associate_joint,
  * associate_scan, associate_scan_joint, correct_sparse_joseph and EKF_DENSE64_LM_JOSEPH, set_live (also the one inside
  * EKF_DENSE64_LM_GROW_LIVE), and a block readout or state block with an index >= Na.  Such a call checks its arguments
  * first, against the live dimension the region found -- a REFUSED call ends nothing, the region stays open -- and the
@@ -1425,7 +1425,8 @@ ekf_status ekf_dense64_whiten(ekf_dense64_handle h, int nrhs, const double* B /*
  *     call it again before filtering on.
  *   terms_out (nullable, [4 + 3 Na] doubles): G [4] then C [Na][3] as they were used (FIXED: C comes back as zeros).  THE
  *   COVARIANCE RESULT IS, BIT FOR BIT, ekf_dense64_map_congruence WITH THOSE OPERANDS (FIXED: with C = NULL).
- * Out of scope: a transform with a covariance of its own, joining two handles, carrying the pending rows through the call.
+ * Out of scope: a transform with a covariance of its own, carrying the pending rows through the call.  (Joining two
+ * handles is ekf_dense64_join_map, below.)
  * Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the launches, the flush included. */
 #define EKF_DENSE64_FRAME_FIXED 0
 #define EKF_DENSE64_FRAME_ROBOT 1
@@ -1434,6 +1435,84 @@ ekf_status ekf_dense64_map_congruence(ekf_dense64_handle h, const double* G /* [
                                       double* elapsed_ms);
 ekf_status ekf_dense64_reframe_landmarks(ekf_dense64_handle h, int mode, double dtheta, double tx, double ty,
                                          double* terms_out /* [4 + 3 Na], nullable */, double* elapsed_ms);
+
+/* Map joining (Tardos, Neira, Newman, Leonard 2002): the map of a second handle appended to the map of the first, on the
+ * device.  A local map B is built in a handle of its own (`src`), started at the robot's current pose with pose 0 and zero
+ * pose covariance, so that every call on it costs Nb^2 and not N^2; the join then expresses its landmarks in the global frame
+ * through the global robot pose, correlates them with the global map A (`dst`) through that pose's covariance, and replaces
+ * the global pose by the composition of the two.  ekf_dense64_score_landmark_pairs / ekf_dense64_merge_landmarks then fuse
+ * the landmarks both maps saw.  Instead of ekf_dense64_get_sigma of both handles, a host product and ekf_dense64_set of the
+ * N^2 result, the join reads the source's corner once and writes the new corner and two rank-3 rectangles: 16 (Nb - 3)^2 +
+ * 32 b (Na - 3) bytes and a few small launches.  Opt-in: no other entry point calls these or launches anything different
+ * because they exist.
+ * SETTING.  dst holds A: live dimension Na = 3 + 2 a, state (theta_A, p_A, l_1 .. l_a).  src holds B: live dimension
+ * Nb = 3 + 2 b, b >= 0, state (theta_B, p_B, m_1 .. m_b), expressed in the frame of A's robot pose.  B MUST BE
+ * STATISTICALLY INDEPENDENT OF A (the local map was started with pose 0 and zero pose covariance): THIS IS THE CALLER'S DUTY
+ * AND IS NOT CHECKED.  With M = R(theta_A) = [c -s; s c] and M' = dM/dtheta = [-s -c; c -s] the joined state is
+ *   pose' = (theta_A + theta_B, p_A + M p_B), THETA' IS NOT WRAPPED (as ekf_dense64_predict_landmarks and FRAME_FIXED do not);
+ *   A's landmarks unchanged;  B's landmark j goes to dst's states Na + 2 j, Na + 2 j + 1 as p_A + M m_j,
+ * and the new live dimension of dst is Na' = Na + 2 b.  b = 0 is legal: a pure pose composition.
+ * OPERANDS.  G = M (row-major G[4]); D = blockdiag(1, G, ..., G), Nb x Nb, over the pairs (1, 2), (3, 4), ... as in the frame
+ * calls; E, Nb x 3 row-major: row 0 = [1, 0, 0], rows (1, 2) = [M' p_B | I_2], rows (3 + 2 j, 4 + 2 j) = [M' m_j | I_2].
+ * E IS A GENERAL OPERAND: every entry is multiplied through, the zeros and ones are not skipped.  From dst's Sigma ON ENTRY
+ * (after the flush): P = Sigma_A[0:3, :] (the three pose rows, read along rows), Pc = Sigma_A[:, 0:3] (the three pose
+ * columns), Sigma_pp the 3 x 3 corner.
+ * DEFINITION, every operation in IEEE binary64, round to nearest even, each rounded on its own (fl) unless it is written as
+ * a fused multiply-add fma(a, b, c) = fl(a b + c).  SIGMA IS NEVER SYMMETRISED, neither A's nor B's:
+ *   1. Z = D Sigma_B D^T: exactly step 1 of ekf_dense64_map_congruence on src's corner -- the same four products and four
+ *      fused steps per 2 x 2 block, the same one-sided products on row 0 and column 0.
+ *   2. W = E Sigma_pp (Nb x 3): W[k][l] = fl(E[k][0] * Sigma_pp[0][l]), then W[k][l] = fma(E[k][t], Sigma_pp[t][l], W[k][l])
+ *      for t = 1, 2.
+ *   3. Y = Z + W E^T: acc = Z[i][j]; acc = fma(W[i][l], E[j][l], acc) for l = 0, 1, 2.
+ *   4. The cross terms.  X_rows (Nb x Na): X_rows[k][j] = fl(E[k][0] * P[0][j]), then fma(E[k][l], P[l][j], .) for l = 1, 2.
+ *      X_cols (Na x Nb): X_cols[i][k] = fl(Pc[i][0] * E[k][0]), then fma(Pc[i][l], E[k][l], .) for l = 1, 2.
+ *   5. Placement, with iota: src index 0, 1, 2 -> 0, 1, 2 and 3 + t -> Na + t:
+ *        Sigma'[iota(i)][iota(j)] = Y[i][j];
+ *        Sigma'[iota(k)][j] = X_rows[k][j] for 3 <= j < Na;      Sigma'[i][iota(k)] = X_cols[i][k] for 3 <= i < Na;
+ *        SIGMA'[3:Na, 3:Na] IS NOT TOUCHED: NOT READ, NOT WRITTEN.  Nothing at a dst index >= Na' and nothing at a src index
+ *        >= Nb is read or written: loads and stores are masked element by element, a pair is inside or outside as a whole.
+ * AN ENTRY OF Y SEES 14 ROUNDED OPERATIONS (4 products and 4 fused steps of step 1, 3 of step 2, 3 of step 3), A CROSS ENTRY
+ * 3.  With J the Na' x (Na + Nb) Jacobian of the joined state on (A, B) -- the identity on A's landmarks, [E | 0 | D] in the
+ * rows iota(.) -- and Sigma = blockdiag(Sigma_A, Sigma_B):
+ *   |Sigma' - J Sigma J^T|_ij <= gamma_14 (|J| |Sigma| |J|^T)_ij,  gamma_k = k u / (1 - k u), u = 2^-53
+ * (gamma_3 on the two rectangles and on the pose rows and columns below Na).  On integer operands small enough for every
+ * intermediate to stay below 2^53 the result is exact in any order.
+ * ekf_dense64_join_congruence is the kernels' own entry point: Sigma only, with the caller's G and E.  It sets dst's live
+ * dimension to Na' and TOUCHES NEITHER STATE VECTOR.
+ * ekf_dense64_join_map builds G and E ON THE DEVICE from dst's own heading (the device's cos and sin, as FRAME_ROBOT does)
+ * and src's state, transforms the state with FRAME_FIXED's expressions -- x' = fl(fma(-s, y, fl(c x)) + p_Ax),
+ * y' = fl(fma(c, y, fl(s x)) + p_Ay), theta' = fl(theta_A + theta_B) -- and runs the same covariance launches.  terms_out
+ * (nullable, [4 + 3 Nb] doubles): G [4] then E [Nb][3] as they were used.  ITS COVARIANCE RESULT IS, BIT FOR BIT,
+ * ekf_dense64_join_congruence WITH THOSE OPERANDS.
+ * REFUSALS.  Every refusal returns EKF_ERR_INVALID before the device is looked at and changes nothing in either handle, the
+ * pending rows and an open region included.  THE CHECKS COME IN THIS ORDER: (1) NULL dst; (2) NULL src; (3) dst == src;
+ * (4) the handles live on different devices; (5) dst's live and src's live both odd and >= 3; (6) Na + 2 b <= dst's N;
+ * (7) NULL G or E (ekf_dense64_join_congruence only).
+ * PENDING ROWS, REGIONS, STREAMS.  dst needs Sigma in memory, so it FLUSHES ITS PENDING ROWS FIRST, carry or not, after the
+ * checks and inside the timed region; an open region on dst is ended first, like every call outside a region's terms.  src
+ * is brought to Sigma in memory as ekf_dense64_get_sigma would: its pending rows are flushed and an open region is ended,
+ * on src's own stream; an event recorded there is waited on by dst's stream.  OTHERWISE SRC IS READ-ONLY: its Sigma values,
+ * its state and its live dimension are unchanged, and the caller can go on using it or reset it.  All join launches run on
+ * dst's stream, which is synchronised before the call returns.  dst's factor snapshot stays as taken (ekf_dense64_factor).
+ * THE LAUNCHES.  A small launch snapshots P and Pc of dst -- the only walk down a column of dst, 3 Na entries -- and builds W.
+ * The hot kernel makes one pass over src's Sigma[3:Nb, 3:Nb] in the frame pass's shape: tiles of tile_rows x tile_cols
+ * states whose ORIGINS SIT ON ODD INDICES, a 2 x 2 block per lane, loads along src's rows issued ahead of use, E of a tile's
+ * columns in registers, W of its rows through the scalar cache, no LDS; it stores to dst at the shifted origin with dst's
+ * leading dimension, so it is out of place and has no hazard.  One launch per rectangle writes X_rows[3:, 3:Na] and
+ * X_cols[3:Na, 3:] along rows, and a sibling of the snapshot writes the three new pose rows and columns over [0, Na').
+ * (join_map: one small launch in front for the terms and the state; the new pose goes through a staging slot and is copied
+ * over behind the launches, so every thread reads the old pose.)  NO ATOMICS, NO REDUCTIONS: A RUN REPEATS BIT FOR BIT, and an entry's bits depend on neither handle's
+ * N or ld.  ekf_dense64_join_launch_info reports the hot kernel's tile sides in states and its workgroup size.  The workspace
+ * (6 ld + 6 Nb + 8 doubles) comes from DST's ledger, allocated on first use and grown with Nb; a failure there returns
+ * EKF_ERR_NOMEM and leaves both handles as they were.
+ * Out of scope: joining across devices, carrying the pending rows through the join, a source pose with a prior correlation
+ * to A.  Synchronous.  elapsed_ms (nullable) = HIP-event time on dst's stream, both flushes included;
+ * ekf_dense64_join_congruence: the uploads of G and E are queued in front of it and are not (as ekf_dense64_map_congruence's). */
+ekf_status ekf_dense64_join_launch_info(ekf_dense64_handle h, int* tile_rows, int* tile_cols, int* threads);
+ekf_status ekf_dense64_join_congruence(ekf_dense64_handle dst, ekf_dense64_handle src, const double* G /* [4] */,
+                                       const double* E /* [Nb][3] */, double* elapsed_ms);
+ekf_status ekf_dense64_join_map(ekf_dense64_handle dst, ekf_dense64_handle src, double* terms_out /* [4 + 3 Nb], nullable */,
+                                double* elapsed_ms);
 
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
