@@ -472,12 +472,9 @@ class EKF_SLAM:
         return f.value
 
     def set_forms(self, forms=FORMS_DEFAULT):
-        """which launch structures may be taken (FORM_* bits; test / measurement hook).  Most forms are exact: the same
-        operations in the same order, bit-identical results.  Two things move results at ROUNDING level (1e-10-class, inside
-        the 1e-9 contract): FORM_CURRENT_COLUMNS (on by default: the kept rows / columns carry their rounding from launch
-        to launch instead of being rebuilt from all pending factors), and whatever moves a delayed flush -- the forms that
-        decide how many corrections a launch appends (FORM_DELAYED_PAIR), run boundaries, getters in mid-run -- because the
-        delayed mode's reconstruction and flush contract their multiply-adds over what is pending"""
+        """which launch structures may be taken (FORM_* bits; test / measurement hook).  The forms a single filter takes are
+        exact (bit-identical results); in delayed mode, what moves a flush moves the results at rounding level, inside the
+        1e-9 contract -- BatchEKF.set_forms lists which forms are bit-identical and which agree to rounding"""
         _check(self._lib.ekf_set_forms(self._h, int(forms)))
 
     def _form(self, bit, enable):
@@ -654,12 +651,22 @@ class BatchEKF:
         return f.value
 
     def set_forms(self, forms=FORMS_DEFAULT):
-        """which launch structures may be taken (FORM_* bits; test / measurement hook).  Most forms are exact: the same
-        operations in the same order, bit-identical results.  Two things move results at ROUNDING level (1e-10-class, inside
-        the 1e-9 contract): FORM_CURRENT_COLUMNS (on by default: the kept rows / columns carry their rounding from launch
-        to launch instead of being rebuilt from all pending factors), and whatever moves a delayed flush -- the forms that
-        decide how many corrections a launch appends (FORM_DELAYED_PAIR), run boundaries, getters in mid-run -- because the
-        delayed mode's reconstruction and flush contract their multiply-adds over what is pending"""
+        """which launch structures may be taken (FORM_* bits; test / measurement hook).  What a form does to the results:
+
+        BIT-IDENTICAL (the same operations in the same order, read from or written to another place): FORM_SMALL_MAP,
+        FORM_CALL_FUSED, FORM_ACTIVE_PREFIX, FORM_STEP_FUSED, FORM_STEP_SPLIT_PASS, FORM_ROW_PACKING, FORM_TILE_QUEUE,
+        FORM_STRIP_FLUSH / _ALWAYS (strip against plain flush), FORM_STEP_SPECULATE, and the column panel -- FORM_COLUMN_PANEL
+        on, off, or with FORM_COLUMN_PANEL_ONE_SLOT give the same bits in state and Sigma (tools/soak_panel.py and its slice
+        in tests/test_gpu_pool_soak.py assert it, across run boundaries, getters, blind steps and sit-outs).
+
+        EQUAL TO ROUNDING, not to the bit: FORM_CURRENT_COLUMNS (on by default).  The kept current rows / columns carry
+        their rounding from launch to launch instead of being rebuilt from all pending factors: another association of the
+        same sums, within 1e-10 of the rebuilt form (FORM_CURRENT_COLUMNS off) in state and, relative to its largest entry,
+        in Sigma -- the bound the panel soak asserts -- and like every form within the 1e-9 contract of the eager run.
+        The same holds for whatever moves a delayed flush: FORM_DELAYED_PAIR (how many corrections a launch appends), run
+        boundaries and getters in mid-run, because the delayed mode's reconstruction and its flush contract their
+        multiply-adds over what is pending; compare two delayed runs bit for bit only over the same
+        run boundaries and the same pairing."""
         _check(self._lib.ekf_batch_set_forms(self._h, int(forms)))
 
     def _form(self, bit, enable):

@@ -1,64 +1,20 @@
 """Extended differential check of the batched unknown-association run against the single-filter API (bit for bit):
-random pool sizes, map sizes, ragged measurement counts, split runs, LDS-resident / multi-kernel / prefix switches."""
+random pool sizes, map sizes, ragged measurement counts, split runs, LDS-resident / multi-kernel / prefix switches.
+(scenarios and runs: tests/pool_soak_cases.py, which the seeded slice under -m gpu shares -- BATCH_SEEDS, tests/test_gpu_pool_soak.py)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import torch  # noqa: F401  (one HIP runtime)
 from ekf_slam_ml_amd import capi as hip
+import pool_soak_cases as cases
 
-bad = 0
 N_SCEN = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+bad = 0
 for seed in range(N_SCEN):
-    rng = np.random.default_rng(70000 + seed)
-    B, n, T, J = int(rng.integers(1, 7)), int(rng.integers(3, 91)), int(rng.integers(4, 26)), int(rng.integers(1, 7))
-    heavy = seed % 20 == 19   # big prefixes on a pool with fresh known counts: the two-launch step (k_rank2v, K in LDS)
-    if heavy:
-        B, n, T, J = int(rng.integers(64, 72)), int(rng.integers(300, 340)), int(rng.integers(3, 6)), int(rng.integers(2, 9))
-    world = rng.uniform(-2.5, 2.5, size=(max(n, 8), 2)) * (3.0 if heavy else 1.0)
-    twist = np.stack([rng.normal(0, 0.2, (T, B)), rng.normal(0.05, 0.03, (T, B))], axis=2)
-    count = rng.integers(0, J + 1, size=(T, B)).astype(np.int32)
-    meas = np.zeros((T, B, J, 2))
-    pose = np.zeros((B, 3))
-    for t in range(T):
-        pose[:, 1] += twist[t, :, 1] * np.cos(pose[:, 0]); pose[:, 2] += twist[t, :, 1] * np.sin(pose[:, 0]); pose[:, 0] += twist[t, :, 0]
-        for b in range(B):
-            pick = rng.choice(len(world), size=J, replace=False)
-            d = world[pick] - pose[b, 1:]
-            c, s = np.cos(pose[b, 0]), np.sin(pose[b, 0])
-            meas[t, b] = np.stack([c * d[:, 0] + s * d[:, 1], -s * d[:, 0] + c * d[:, 1]], axis=1) + rng.normal(0, 0.004, (J, 2))
-    bt = hip.BatchEKF(B, n)
-    bt.set_small_map_path(bool(rng.integers(0, 2)))
-    bt.set_step_fused(int(rng.integers(0, 3)))   # four launches per slot / automatic / always one launch per step
-    bt.set_active_prefix(bool(rng.integers(0, 2)))
-    surveyed = heavy and bool(rng.integers(0, 2))
-    init = (world[:n][None] + rng.normal(0, 0.004, (B, n, 2))).reshape(B, 2 * n) if surveyed else None
-    if surveyed:   # known_list all true from the start: the map comes from a first known-association call
-        bt.upload_known_log(np.zeros((1, B, 2)), np.full((1, B, 1), -1, dtype=np.int32), np.zeros((1, B, 1, 2)), init)
-        bt.run_known()
-        bt.set_known_counts(n)
-    bt.upload_unknown_log(twist, count, meas)
-    cut = int(rng.integers(0, T + 1))
-    bt.run_unknown(0, cut); bt.run_unknown(cut, T)
-    dec, kc = bt.decisions(), bt.known_counts()
-    ok = True
-    for b in range(B):
-        f = hip.EKF_SLAM(n)
-        f.set_call_fused(bool(rng.integers(0, 2)))
-        k = np.zeros(n, dtype=np.uint8)
-        if surveyed:
-            f.prediction((0.0, 0.0)); f.measurement(init[b], np.zeros(n, dtype=np.uint8))
-            k[:] = 1
-        for t in range(T):
-            f.prediction(twist[t, b])
-            a = f.data_association(meas[t, b, :count[t, b]], k)
-            ok &= np.array_equal(a, dec[t, b, :count[t, b]])
-        ok &= int(k.sum()) == int(kc[b]) and np.array_equal(f.state, bt.state(b)) and np.array_equal(f.cov, bt.cov(b))
-        f.close()
-    bt.close()
-    if not ok:
+    r = cases.run_batch(hip, cases.batch_scenario(seed))
+    if not r.ok:
         bad += 1
-        print(f"FAIL scenario {seed}: B={B} n={n} T={T} J={J}", flush=True)
+        print(r.fail_line(), flush=True)
     if seed % 50 == 0:
         print("scenario", seed, "failures so far", bad, flush=True)
 print("done, failures:", bad)
