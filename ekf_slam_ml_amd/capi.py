@@ -65,6 +65,7 @@ SYMBOLS = [
     "ekf_dense64_join_launch_info", "ekf_dense64_join_congruence", "ekf_dense64_join_map",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident", "ekf_batch_rank2_packing", "ekf_batch_spec_counts",
+    "ekf_batch_set_chain", "ekf_batch_chain_counts",
     "ekf_set_profiling", "ekf_get_profile", "ekf_batch_set_known_counts",
     "ekf_set_forms", "ekf_get_forms", "ekf_batch_set_forms", "ekf_batch_get_forms", "ekf_batch_form_counts",
     "ekf_phase_trace", "ekf_test_raise_device_error",
@@ -75,8 +76,10 @@ FORM_SMALL_MAP, FORM_CALL_FUSED, FORM_ACTIVE_PREFIX = 1 << 0, 1 << 2, 1 << 3   #
 FORM_STEP_FUSED, FORM_STEP_SPLIT_PASS, FORM_DELAYED_PAIR, FORM_ROW_PACKING = 1 << 4, 1 << 5, 1 << 6, 1 << 7
 FORM_STRIP_FLUSH, FORM_STRIP_FLUSH_ALWAYS = 1 << 8, 1 << 9
 FORM_COLUMN_PANEL, FORM_COLUMN_PANEL_ONE_SLOT, FORM_STEP_SPECULATE, FORM_CURRENT_COLUMNS = 1 << 10, 1 << 11, 1 << 12, 1 << 13
-FORM_TILE_QUEUE = 1 << 14
-FORMS_DEFAULT = ((1 << 9) - 1) | FORM_COLUMN_PANEL | FORM_STEP_SPECULATE | FORM_CURRENT_COLUMNS | FORM_TILE_QUEUE
+FORM_TILE_QUEUE, FORM_STEP_CHAIN = 1 << 14, 1 << 15
+FORMS_DEFAULT = (((1 << 9) - 1) | FORM_COLUMN_PANEL | FORM_STEP_SPECULATE | FORM_CURRENT_COLUMNS | FORM_TILE_QUEUE
+                 | FORM_STEP_CHAIN)
+CHAIN_POLICY_EXPLICIT = 16   # set_chain(policy=CHAIN_POLICY_EXPLICIT | bits): the four bits as given (0 = automatic)
 
 
 class EkfError(RuntimeError):
@@ -298,6 +301,8 @@ def load():
         "ekf_batch_rank2_resident": [h, _ip],
         "ekf_batch_rank2_packing": [h, _ip],
         "ekf_batch_spec_counts": [h, C.POINTER(C.c_longlong)],
+        "ekf_batch_set_chain": [h, C.c_int, C.c_int],
+        "ekf_batch_chain_counts": [h, C.POINTER(C.c_longlong)],
         "ekf_batch_set_known_counts": [h, _ip],
         "ekf_set_profiling": [h, C.c_int],
         "ekf_set_forms": [h, C.c_uint],
@@ -655,6 +660,7 @@ class BatchEKF:
 
         BIT-IDENTICAL (the same operations in the same order, read from or written to another place): FORM_SMALL_MAP,
         FORM_CALL_FUSED, FORM_ACTIVE_PREFIX, FORM_STEP_FUSED, FORM_STEP_SPLIT_PASS, FORM_ROW_PACKING, FORM_TILE_QUEUE,
+        FORM_STEP_CHAIN (a step's corrections in one launch, tile batch by tile batch; any set_chain setting),
         FORM_STRIP_FLUSH / _ALWAYS (strip against plain flush), FORM_STEP_SPECULATE, and the column panel -- FORM_COLUMN_PANEL
         on, off, or with FORM_COLUMN_PANEL_ONE_SLOT give the same bits in state and Sigma (tools/soak_panel.py and its slice
         in tests/test_gpu_pool_soak.py assert it, across run boundaries, getters, blind steps and sit-outs).
@@ -763,6 +769,23 @@ class BatchEKF:
         among them and continued from its rebuilt rows"""
         c = (C.c_longlong * 2)()
         _check(self._lib.ekf_batch_spec_counts(self._h, c))
+        return int(c[0]), int(c[1])
+
+    def set_step_chain(self, enable=True):
+        """eager pools on the tile queue: all corrections of a step in ONE launch over Sigma (default) / one launch per
+        correction"""
+        self._form(FORM_STEP_CHAIN, enable)
+
+    def set_chain(self, tiles_per_batch=0, policy=0):
+        """experiment / test hook of FORM_STEP_CHAIN: tiles per queue item (0 = automatic) and the cache policy of its four
+        access sets (0 = automatic; CHAIN_POLICY_EXPLICIT | bits: non-temporal where set -- 1 first loads, 2 stores of all
+        sweeps but the last, 4 re-loads, 8 last stores).  Speed only: bit-identical results."""
+        _check(self._lib.ekf_batch_set_chain(self._h, int(tiles_per_batch), int(policy)))
+
+    def chain_counts(self):
+        """(chained launches, correction passes they applied) since the pool was created; (0, 0) with FORM_STEP_CHAIN off"""
+        c = (C.c_longlong * 2)()
+        _check(self._lib.ekf_batch_chain_counts(self._h, c))
         return int(c[0]), int(c[1])
 
     def rank2_kernel(self):

@@ -49,6 +49,22 @@ ekf_status ekf_batch_spec_counts(ekf_batch_handle hb, long long out[2]) {
     return EKF_OK;
 }
 
+ekf_status ekf_batch_set_chain(ekf_batch_handle hb, int tiles_per_batch, int policy) {
+    if (!hb) return fail(EKF_ERR_INVALID, "null handle");
+    if (tiles_per_batch < 0 || policy < 0 || policy >= 2 * ekf::kChainPolicyExplicit)
+        return fail(EKF_ERR_INVALID, "ekf_batch_set_chain: tiles_per_batch >= 0, policy 0 or 16 + four bits");
+    hb->pool.chain_m = tiles_per_batch;
+    hb->pool.chain_policy = policy;
+    return EKF_OK;
+}
+
+ekf_status ekf_batch_chain_counts(ekf_batch_handle hb, long long out[2]) {
+    if (!hb || !out) return fail(EKF_ERR_INVALID, "null argument");
+    out[0] = hb->pool.chain_counts[0];
+    out[1] = hb->pool.chain_counts[1];
+    return EKF_OK;
+}
+
 ekf_status ekf_batch_create(int B, int n, const ekf_params* params, int device, ekf_batch_handle* out) {
     if (!out) return fail(EKF_ERR_INVALID, "ekf_batch_create: out is null");
     *out = nullptr;
@@ -178,6 +194,10 @@ ekf_status ekf_batch_run_known(ekf_batch_handle hb, int t_begin, int t_end, int 
     const bool delayed = P.pend_cap > 0;
     const bool callf = !delayed && P.call_fused_ok();
     if (callf) EKFC(P.ensure_callfused());
+    // eager pools: steps with two or more active slots may take the chained pass (the plan decides per step)
+    const bool chain_capable = !delayed && !callf && !P.active_set && P.chain_plan(2).chains;
+    if (chain_capable) EKFC(P.ensure_callfused());
+    size_t chained_extra = 0;
     // worst-case number of covariance passes (rank-2 launches, or flushes in delayed mode) for the events
     // (paired slots flush when FOUR rows no longer fit: up to one flush per two corrections for tiny k)
     const size_t max_passes = delayed ? launches / (size_t)(P.pend_cap >= 4 ? (P.pend_cap / 2 > 2 ? P.pend_cap / 2 - 1 : 1) : 1) + 2 : launches;
@@ -289,6 +309,27 @@ ekf_status ekf_batch_run_known(ekf_batch_handle hb, int t_begin, int t_end, int 
             }
             continue;
         }
+        if (chain_capable) {   // all corrections of the step in one launch over Sigma (EKF_FORM_STEP_CHAIN)
+            int vtop = 0;      // (a known log is -1 padded: the active slots of a step are 0 .. vtop - 1)
+            for (int v = 0; v < vmax; v++) if (P.slot_active[(size_t)t * vmax + v] > 0) vtop = v + 1;
+            const ekf::ChainPlan cp = P.chain_plan(vtop);
+            if (cp.chains) {
+                ekf::CallSrc cs{};
+                cs.mode = ekf::SRC_COMPACT_LOG;
+                cs.lm_idx = src.lm_idx;
+                cs.z_xy = src.z_xy;
+                cs.vmax = vmax;
+                for (int v0 = 0; v0 < vtop; v0 += ekf::kCallV) {
+                    cs.v0 = v0;
+                    cs.vcount = vtop - v0 < ekf::kCallV ? vtop - v0 : ekf::kCallV;
+                    cs.fresh_pose = 0;
+                    EKFC(P.chained_pass(cs, cp, ev ? ev[2 * k] : nullptr, ev ? ev[2 * k + 1] : nullptr));
+                    k++;
+                    chained_extra += (size_t)cs.vcount - 1;   // a chained launch is vcount passes over Sigma under one event pair
+                }
+                continue;
+            }
+        }
         for (int v = 0; v < vmax; v++) {
             if (P.slot_active[(size_t)t * vmax + v] == 0) continue;
             src.v = v;
@@ -318,7 +359,7 @@ ekf_status ekf_batch_run_known(ekf_batch_handle hb, int t_begin, int t_end, int 
     if (panel_on && panel_cols_stale) ekf::launch_panel_repair(P.pv, P.colp, P.colp_rows(), P.stream);   // (the same, panel form)
     P.panel_active = false;
     P.panel_valid = panel_on;   // the panel holds the columns of the covariance as this run leaves it
-    const size_t passes = k;
+    const size_t passes = k;   // (event pairs; chained launches count their further passes in chained_extra)
     HIPC(hipEventRecord(P.ev_end, P.stream));
     EKFC(checked_launch());
     HIPC(hipStreamSynchronize(P.stream));
@@ -327,7 +368,7 @@ ekf_status ekf_batch_run_known(ekf_batch_handle hb, int t_begin, int t_end, int 
         HIPC(hipEventElapsedTime(&ms, P.ev_begin, P.ev_end));
         stats->elapsed_ms = ms;
         stats->rank2_ms = 0.0;
-        stats->rank2_launches = (long long)passes;
+        stats->rank2_launches = (long long)(passes + chained_extra);
         if (ev)
             for (size_t i = 0; i < passes; i++) {
                 float m = 0.f;

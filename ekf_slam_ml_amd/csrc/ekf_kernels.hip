@@ -586,6 +586,74 @@ __global__ __launch_bounds__(TPB) void k_rank2_queue(double* __restrict__ sigma,
     }
 }
 
+// The CHAINED pass: all C corrections of a step in one launch, batch of tiles by batch of tiles.  A queue item is a batch
+// of m consecutive U-row x 512-column tiles of one filter (column chunks fastest, a filter's last batch short); the
+// workgroup sweeps its batch once per correction, in order: load, update, store, and then every lane re-loads exactly the
+// addresses it stored itself -- served by its XCD's L2 (one tile per CU is 2 MB of the 4 MiB) instead of by HBM 40 ms
+// later, and a line rewritten while it is still there is written out once.  The only ordering is a thread's program order
+// on its own addresses.  sigma is NOT __restrict__ and m, C are run-time values: every sweep's loads are global loads.
+// The factors of all corrections of the step come from k_call_factors (U = K, V = G, [b][2 kCallV][ld]; a filter's
+// corrections are slots 0 .. cnt[b] - 1, the state goes with the factor kernel); per element the expression is
+// rank2_tile's.  POL: ekf_rank2_plan.hpp (ChainPlan::policy).
+template <int U, int POL>
+__global__ __launch_bounds__(256) void k_rank2_chain(double* sigma, const double* __restrict__ Uall,
+                                                     const double* __restrict__ Vall, const int* __restrict__ cnt_all, int N,
+                                                     int ld, size_t sigma_stride, int chunks, int row_blocks, int m, int C,
+                                                     unsigned items_per_filter, unsigned total, unsigned* __restrict__ queue) {
+    __shared__ unsigned sh_next[2];
+    const int tiles = chunks * row_blocks, ld2n = ld >> 1, ld2a = (N + 1) >> 1;
+    unsigned ahead = 0;
+    if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
+    for (int par = 0;; par ^= 1) {
+        if (threadIdx.x == 0) sh_next[par] = ahead;
+        __syncthreads();
+        const unsigned s = __builtin_amdgcn_readfirstlane(sh_next[par]);
+        if (s >= total) break;
+        if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
+        const int b = s / items_per_filter, t0 = (int)(s % items_per_filter) * m, t1 = min(t0 + m, tiles);
+        const int cb = min(cnt_all[b], C);   // this filter's corrections in this step (uniform)
+        const double* __restrict__ Ub = Uall + (size_t)b * 2 * kCallV * ld;
+        const double2_t* __restrict__ Vb2 = reinterpret_cast<const double2_t*>(Vall + (size_t)b * 2 * kCallV * ld);
+        double2_t* fsig = reinterpret_cast<double2_t*>(sigma + (size_t)b * sigma_stride);
+        for (int c = 0; c < cb; c++) {
+            const bool first = c == 0, last = c == cb - 1;
+            const double* __restrict__ K0 = Ub + (size_t)(2 * c) * ld;
+            const double* __restrict__ K1 = K0 + ld;
+            for (int t = t0; t < t1; t++) {
+                const int c2 = (t % chunks) * 256 + threadIdx.x, r0 = (t / chunks) * U;
+                if (c2 >= ld2a) continue;
+                const int rows = min(U, N - r0);   // (uniform; > 0: r0 < N)
+                const double2_t g0 = Vb2[(size_t)(2 * c) * ld2n + c2], g1 = Vb2[(size_t)(2 * c + 1) * ld2n + c2];
+                double2_t* col = fsig + c2 + (size_t)r0 * ld2n;
+                double2_t a[U];
+                if (first) {
+#pragma unroll
+                    for (int u = 0; u < U; u++) a[u] = ld2<(POL & 1) != 0>(col + (size_t)min(u, rows - 1) * ld2n);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; u++) a[u] = ld2<(POL & 4) != 0>(col + (size_t)min(u, rows - 1) * ld2n);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const int row = r0 + min(u, rows - 1);
+                    const double k0 = K0[row], k1 = K1[row];   // uniform address -> s_load
+                    a[u].x = a[u].x - (k0 * g0.x + k1 * g1.x);
+                    a[u].y = a[u].y - (k0 * g0.y + k1 * g1.y);
+                }
+                if (last) {
+#pragma unroll
+                    for (int u = 0; u < U; u++)
+                        if (u < rows) st2<(POL & 8) != 0>(col + (size_t)u * ld2n, a[u]);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; u++)
+                        if (u < rows) st2<(POL & 2) != 0>(col + (size_t)u * ld2n, a[u]);
+                }
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Row-PACKED form of the same update for pools whose rows do not fill the 256-lane strips (n = 200: 208 of 256 lanes
 // carry a column, 0.68 of peak): rows are contiguous in memory (ld doubles each, no gap), so P consecutive rows are ONE
@@ -1061,6 +1129,25 @@ void launch_rank2(const PoolView& pv, const Rank2Tuning& t, hipStream_t s, bool 
         case 4: launch_rank2_u<4>(pv, p, s); break;
         case 16: launch_rank2_u<16>(pv, p, s); break;
         default: launch_rank2_u<8>(pv, p, s); break;
+    }
+}
+
+template <int POL>
+static void launch_rank2_chain_p(const PoolView& pv, const double* U, const double* V, const int* cnt, int C, const ChainPlan& c,
+                                 hipStream_t s) {
+    hipLaunchKernelGGL((k_rank2_chain<kChainRows, POL>), dim3(device_cus()), dim3(256), 0, s, pv.sigma, U, V, cnt, pv.N, pv.ld,
+                       pv.sigma_stride, c.chunks, c.row_blocks, c.tiles_per_batch, C, c.items_per_filter, c.total, pv.queue);
+}
+
+void launch_rank2_chain(const PoolView& pv, const double* U, const double* V, const int* cnt, int C, const ChainPlan& c,
+                        hipStream_t s) {
+    if (hipMemsetAsync(pv.queue, 0, sizeof(unsigned), s) != hipSuccess) return;   // (the sticky error reaches checked_launch)
+    switch (c.policy & 15) {
+#define EKF_CHAIN_CASE(P) case P: launch_rank2_chain_p<P>(pv, U, V, cnt, C, c, s); break;
+        EKF_CHAIN_CASE(0) EKF_CHAIN_CASE(1) EKF_CHAIN_CASE(2) EKF_CHAIN_CASE(3) EKF_CHAIN_CASE(4) EKF_CHAIN_CASE(5)
+        EKF_CHAIN_CASE(6) EKF_CHAIN_CASE(7) EKF_CHAIN_CASE(8) EKF_CHAIN_CASE(9) EKF_CHAIN_CASE(10) EKF_CHAIN_CASE(11)
+        EKF_CHAIN_CASE(12) EKF_CHAIN_CASE(13) EKF_CHAIN_CASE(14) EKF_CHAIN_CASE(15)
+#undef EKF_CHAIN_CASE
     }
 }
 

@@ -508,6 +508,9 @@ void launch_gain(const PoolView& pv, const CmdSrc& src, hipStream_t s);
 void launch_rank2(const PoolView& pv, const Rank2Tuning& t, hipStream_t s, bool full_width = false);
 // the plan launch_rank2 launches from for this view (ekf_rank2_plan.hpp; the report hooks read it too)
 Rank2Plan rank2_plan_of(const PoolView& pv, const Rank2Tuning& t, bool full_width);
+// the chained pass (k_rank2_chain): corrections 0 .. C - 1 of a step from k_call_factors' U, V, cnt, plan from rank2_chain_plan
+void launch_rank2_chain(const PoolView& pv, const double* U, const double* V, const int* cnt, int C, const ChainPlan& c,
+                        hipStream_t s);
 // Same update restricted to the rows of the touched set (exact: every other row has K = 0).
 // max_touched: host-side upper bound of touch_count over the pool (sizes the grid).
 void launch_rank2_active(const PoolView& pv, const Rank2Tuning& t, int max_touched, hipStream_t s);

@@ -131,4 +131,50 @@ inline Rank2Plan rank2_plan(int B, int N, int ld, const Rank2Tuning& t, bool ful
     return p;
 }
 
+// The CHAINED pass (k_rank2_chain, EKF_FORM_STEP_CHAIN): one launch applies all corrections of a step, batch of tiles by
+// batch of tiles -- a resident workgroup sweeps its batch once per correction and re-loads what it stored itself while the
+// lines are still on the chip.  Policy bits (non-temporal where set, plain otherwise): 1 = the first sweep's loads, 2 = the
+// stores of every sweep but the last, 4 = the re-loads, 8 = the last sweep's stores.
+constexpr int kChainRows = 16;          // rows of a tile: 256 CUs x 64 KB = half of the L2s (tools/micro/strip_walk.hip chain)
+constexpr int kChainPolicyExplicit = 16;   // set in a policy override: the low four bits are taken as they are (0 = automatic)
+
+struct ChainPlan {
+    int chains;                 // 1: the step takes the chained pass
+    int rows;                   // rows of a tile (512 columns wide)
+    int tiles_per_batch;        // m: consecutive tiles of one filter per queue item (column chunks fastest)
+    int policy;                 // the four policy bits
+    int chunks, row_blocks;     // tiles of one filter: chunks x row_blocks
+    unsigned items_per_filter;  // ceil(chunks * row_blocks / m): a filter's last batch may be short; no item spans two filters
+    unsigned total;             // queue items of the launch: B * items_per_filter
+};
+
+// eager: not delayed, not call-fused, not active-set; `single` is the plan of ONE correction over the same full-width view;
+// active_slots: slots of the step with a correction in at least one filter; m_override / policy_override: 0 = automatic
+inline ChainPlan rank2_chain_plan(int B, int N, int ld, const Rank2Plan& single, bool form_on, bool eager, bool full_width,
+                                  int active_slots, int m_override, int policy_override) {
+    ChainPlan c{};
+    c.rows = kChainRows;
+    c.tiles_per_batch = m_override > 0 ? m_override : 1;
+    c.policy = (policy_override & kChainPolicyExplicit) ? (policy_override & 15) : (single.nontemporal ? 8 : 0);
+    c.chunks = ((N + 1) / 2 + 255) / 256;
+    c.row_blocks = (N + c.rows - 1) / c.rows;
+    const long long tiles = (long long)c.chunks * c.row_blocks;
+    if (c.tiles_per_batch > tiles) c.tiles_per_batch = (int)tiles;
+    const long long ipf = (tiles + c.tiles_per_batch - 1) / c.tiles_per_batch;
+    const long long total = ipf * B;
+    c.items_per_filter = (unsigned)ipf;
+    c.total = (unsigned)total;
+    c.chains = form_on && eager && full_width && single.kind == RANK2_QUEUE && active_slots >= 2 && ld % 2 == 0 &&
+               total < 0x7fffffffLL;
+    return c;
+}
+
+// tile range [first, first + count) of queue item s, and its filter (what k_rank2_chain decodes)
+inline void rank2_chain_item(const ChainPlan& c, unsigned s, int* filter, int* first, int* count) {
+    const int tiles = c.chunks * c.row_blocks;
+    *filter = (int)(s / c.items_per_filter);
+    *first = (int)(s % c.items_per_filter) * c.tiles_per_batch;
+    *count = *first + c.tiles_per_batch < tiles ? c.tiles_per_batch : tiles - *first;
+}
+
 }  // namespace ekf

@@ -276,6 +276,29 @@ struct Pool {
         return EKF_OK;
     }
 
+    // Eager pools, EKF_FORM_STEP_CHAIN: corrections [v0, v0 + vcount) of a step for every filter in ONE launch over Sigma
+    // (k_rank2_chain), factors and state from the call-fused factor kernel in place of the per-correction gain launches
+    int step_chain = 1;
+    int chain_m = 0, chain_policy = 0;       // ekf_batch_set_chain (0 = automatic)
+    long long chain_counts[2] = {0, 0};      // ekf_batch_chain_counts: chained launches, correction passes they applied
+    // the plan of a step with `active_slots` slots in use (ekf_rank2_plan.hpp)
+    ekf::ChainPlan chain_plan(int active_slots) const {
+        const bool eager = pend_cap == 0 && !active_set && !call_fused_ok();
+        return ekf::rank2_chain_plan(pv.B, pv.N, pv.ld, ekf::rank2_plan_of(pv, tuning, true), step_chain != 0, eager,
+                                     pv.n > 0 && pv.ld == ekf::pick_ld(pv.N), active_slots, chain_m, chain_policy);
+    }
+    ekf_status chained_pass(const ekf::CallSrc& src, const ekf::ChainPlan& cp, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+        ekf::launch_call_factors(pv, src, cf_U, cf_V, cf_cnt, cf_state, stream);
+        std::swap(pv.state, cf_state);
+        if (ev0) HIPC(hipEventRecord(ev0, stream));
+        ekf::launch_rank2_chain(pv, cf_U, cf_V, cf_cnt, src.vcount, cp, stream);
+        form_counts[4] += src.vcount;
+        chain_counts[0]++;
+        chain_counts[1] += src.vcount;
+        if (ev1) HIPC(hipEventRecord(ev1, stream));
+        return EKF_OK;
+    }
+
     // execution forms (ekf_set_forms): which launch structures may be taken where they apply
     unsigned forms = EKF_FORMS_DEFAULT;
     long long form_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // ekf_batch_form_counts
@@ -294,6 +317,7 @@ struct Pool {
         tuning.row_packing = (f & EKF_FORM_ROW_PACKING) ? 1 : 0;
         tuning.strip_flush = (f & EKF_FORM_STRIP_FLUSH_ALWAYS) ? 2 : (f & EKF_FORM_STRIP_FLUSH) ? 1 : 0;
         tuning.tile_queue = (f & EKF_FORM_TILE_QUEUE) ? 1 : 0;
+        step_chain = (f & EKF_FORM_STEP_CHAIN) ? 1 : 0;
         return EKF_OK;
     }
     void set_tuning(int rows_per_block, int nontemporal, int group_rows) {

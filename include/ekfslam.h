@@ -180,7 +180,13 @@ typedef enum {
      * one queue (an atomicAdd per tile) instead of a grid of short-lived ones: the dispatcher deals a fixed eighth of a grid to
      * each XCD, and XCDs / CUs do not stream at the same rate (tools/micro/strip_walk.hip).  Speed only: same arithmetic. */
     EKF_FORM_TILE_QUEUE = 1u << 14,
-    EKF_FORMS_DEFAULT = ((1u << 9) - 1) | (1u << 10) | (1u << 12) | (1u << 13) | (1u << 14)
+    /* eager pools whose single correction takes the tile queue apply ALL corrections of a step (two or more active slots) in
+     * ONE launch, tile batch by tile batch: a resident workgroup sweeps its batch once per correction and re-loads what it
+     * stored itself while the lines are still in its XCD's L2 (ekf::k_rank2_chain; the factors of the step come from the
+     * call-fused factor kernel).  Each correction still reads and writes every element through the memory system; same
+     * arithmetic in the same order: bit-identical.  Off: one launch per correction. */
+    EKF_FORM_STEP_CHAIN = 1u << 15,
+    EKF_FORMS_DEFAULT = ((1u << 9) - 1) | (1u << 10) | (1u << 12) | (1u << 13) | (1u << 14) | (1u << 15)
 } ekf_form;
 ekf_status ekf_set_forms(ekf_handle h, unsigned forms);
 ekf_status ekf_get_forms(ekf_handle h, unsigned* forms);
@@ -195,6 +201,12 @@ ekf_status ekf_batch_form_counts(ekf_batch_handle hb, long long counts[8]);
  * steps whose decision (an active re-observation) was compared with the guesses of the launch in front, out[1] those that
  * found their winner among the guesses and continued from its rebuilt rows (out[1] <= out[0]; both 0 with the form off). */
 ekf_status ekf_batch_spec_counts(ekf_batch_handle hb, long long out[2]);
+/* Experiment / test hook of EKF_FORM_STEP_CHAIN.  tiles_per_batch: 16-row x 512-column tiles per queue item (0 = automatic:
+ * 1).  policy: 0 = automatic; 16 + bits = non-temporal accesses where a bit is set, plain otherwise: 1 the first sweep's
+ * loads, 2 the stores of every sweep but the last, 4 the re-loads, 8 the last sweep's stores.  Speed only. */
+ekf_status ekf_batch_set_chain(ekf_batch_handle hb, int tiles_per_batch, int policy);
+/* since the pool was created: out[0] chained launches, out[1] correction passes they applied (both 0 with the form off) */
+ekf_status ekf_batch_chain_counts(ekf_batch_handle hb, long long out[2]);
 
 /* Active-set covariance update (opt-in, default 0; reported separately from the dense contract path):
  * the eager correction streams only the rows of the TOUCHED set -- the pose rows and the rows of landmarks

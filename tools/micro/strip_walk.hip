@@ -3,10 +3,11 @@
 //   strip-major : Sigma[b][strip][row][256 cols] -- a strip workgroup reads one contiguous block of N x 2 KB
 // One workgroup of 16 waves per (filter, strip), 8-row groups per wave, non-temporal loads, +1, non-temporal stores: what
 // k_flush_strip does to memory (ekf_delayed.hip).  160 KB of dynamic LDS keeps it at one workgroup per CU like the flush.
-// build: hipcc --offload-arch=gfx950 -O3 -o strip_walk strip_walk.hip      run: ./strip_walk [B=4096] [N=2003]
+// build: hipcc --offload-arch=gfx950 -O3 -o strip_walk strip_walk.hip      run: ./strip_walk [B=4096] [N=2003] [chain]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 // map: 0 = a filter's workgroups on one XCD (the flush's decode); 1 = plain order (a filter's strips dealt round the XCDs);
@@ -211,6 +212,112 @@ __global__ __launch_bounds__(T) void k_tile_resident(double* __restrict__ sigma,
     }
 }
 
+// CHAINED sweeps: resident workgroups (one per CU) take BATCHES of m consecutive tiles of one filter (column chunks fastest,
+// a filter's last batch short) from the one queue, asked for a batch ahead, and sweep every batch `sweeps` times: load, +1,
+// store, then the same lanes re-load the addresses they stored themselves.  What an eager step's corrections would do to
+// memory if a workgroup applied them batch by batch.  POL picks non-temporal (bit set) or plain per access set: 1 = first
+// sweep's loads, 2 = first sweep's stores, 4 = later sweeps' loads, 8 = later sweeps' stores.  sigma is not __restrict__ and m
+// is a run-time value, so every sweep's loads are real global loads.
+template <int RB, int POL>
+__global__ __launch_bounds__(256) void k_chain(double* sigma, int N, int ld, int chunks, int row_blocks, int m, int sweeps,
+                                               unsigned items_per_filter, unsigned total, unsigned* __restrict__ queue) {
+    __shared__ unsigned sh_next[2];
+    const int P = chunks * row_blocks;
+    const size_t rs = ld >> 1;
+    unsigned ahead = 0;
+    if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
+    for (int par = 0;; par ^= 1) {
+        if (threadIdx.x == 0) sh_next[par] = ahead;
+        __syncthreads();
+        const unsigned s = __builtin_amdgcn_readfirstlane(sh_next[par]);
+        if (s >= total) break;
+        if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
+        const int b = s / items_per_filter, t0 = (s % items_per_filter) * m, t1 = t0 + m < P ? t0 + m : P;
+        double2_t* base = reinterpret_cast<double2_t*>(sigma + (size_t)b * N * ld);
+        for (int sw = 0; sw < sweeps; sw++)
+            for (int t = t0; t < t1; t++) {
+                const int c2 = (t % chunks) * 256 + threadIdx.x, r0 = (t / chunks) * RB;
+                if (c2 >= (ld >> 1)) continue;
+                const int rows = N - r0 < RB ? N - r0 : RB;
+                double2_t* col = base + c2 + (size_t)r0 * rs;
+                double2_t a[RB];
+                if (sw == 0) {
+#pragma unroll
+                    for (int u = 0; u < RB; u++) {
+                        const double2_t* src = col + (size_t)(u < rows ? u : rows - 1) * rs;
+                        a[u] = (POL & 1) ? __builtin_nontemporal_load(src) : *src;
+                    }
+#pragma unroll
+                    for (int u = 0; u < RB; u++) a[u] += 1.0;
+#pragma unroll
+                    for (int u = 0; u < RB; u++)
+                        if (u < rows) { if (POL & 2) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < RB; u++) {
+                        const double2_t* src = col + (size_t)(u < rows ? u : rows - 1) * rs;
+                        a[u] = (POL & 4) ? __builtin_nontemporal_load(src) : *src;
+                    }
+#pragma unroll
+                    for (int u = 0; u < RB; u++) a[u] += 1.0;
+#pragma unroll
+                    for (int u = 0; u < RB; u++)
+                        if (u < rows) { if (POL & 8) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
+                }
+            }
+    }
+}
+
+template <int RB, int POL>
+static float chain_run(double* s, int N, int ld, int B, int m, int sweeps, unsigned* queue, hipEvent_t e0, hipEvent_t e1) {
+    const int chunks = (ld / 2 + 255) / 256, row_blocks = (N + RB - 1) / RB, P = chunks * row_blocks;
+    const unsigned ipf = (unsigned)((P + m - 1) / m), total = ipf * (unsigned)B;
+    float best = 1e9f;
+    for (int rep = 0; rep < 3; rep++) {
+        hipMemsetAsync(queue, 0, sizeof(unsigned));
+        hipEventRecord(e0);
+        hipLaunchKernelGGL((k_chain<RB, POL>), dim3(256), dim3(256), 0, 0, s, N, ld, chunks, row_blocks, m, sweeps, ipf, total, queue);
+        hipEventRecord(e1);
+        hipEventSynchronize(e1);
+        float ms;
+        hipEventElapsedTime(&ms, e0, e1);
+        if (rep && ms < best) best = ms;
+    }
+    return best;
+}
+
+template <int RB, int POL>
+static void chain_row(double* s, int N, int ld, int B, size_t bytes, float single, unsigned* queue, hipEvent_t e0, hipEvent_t e1) {
+    printf("%4d  %c %c %c %c ", RB, POL & 1 ? 'n' : 'p', POL & 2 ? 'n' : 'p', POL & 4 ? 'n' : 'p', POL & 8 ? 'n' : 'p');
+    for (int m : {1, 2, 4, 8}) {
+        const float ms = chain_run<RB, POL>(s, N, ld, B, m, 2, queue, e0, e1);
+        printf(" | %6.2f ms %5.2f TB/s %4.2fx", ms, 4.0 * bytes / (ms * 1e-3) / 1e12, 2.0f * single / ms);
+    }
+    printf("\n");
+    fflush(stdout);
+}
+
+template <int RB, int... POLS>
+static void chain_rows(double* s, int N, int ld, int B, size_t bytes, unsigned* queue, hipEvent_t e0, hipEvent_t e1) {
+    // the yardstick in the same code: ONE sweep (non-temporal loads and stores, m = 1), taken twice
+    const float single = chain_run<RB, 3>(s, N, ld, B, 1, 1, queue, e0, e1);
+    printf("%4d  single sweep, non-temporal: %.2f ms, %.3f TB/s; two of them: %.2f ms\n", RB, single, 2.0 * bytes / (single * 1e-3) / 1e12,
+           2.0 * single);
+    (chain_row<RB, POLS>(s, N, ld, B, bytes, single, queue, e0, e1), ...);
+}
+
+// two chained sweeps per batch of m tiles against two single sweeps: rows of tile x policy, columns m = 1, 2, 4, 8;
+// TB/s is algorithmic bytes (2 sweeps x read + write) over time, the last figure the ratio to two single sweeps
+static void chain_table(double* s, int N, int ld, int B, size_t bytes, hipEvent_t e0, hipEvent_t e1) {
+    unsigned* queue = nullptr;
+    hipMalloc(&queue, sizeof(unsigned));
+    printf("chained sweeps, B = %d, N = %d, ld = %d: tiles of RB rows x 512 columns, 256 resident workgroups, one queue\n", B, N, ld);
+    printf("rows  policy (load 1, store 1, load 2, store 2: n = non-temporal, p = plain) | m = 1 | m = 2 | m = 4 | m = 8\n");
+    chain_rows<16, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(s, N, ld, B, bytes, queue, e0, e1);
+    chain_rows<32, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(s, N, ld, B, bytes, queue, e0, e1);
+    hipFree(queue);
+}
+
 template <int T, int RB, int MODE>
 static void resident_variant(double* s, int N, int ld, int B, size_t bytes, int per_cu, hipEvent_t e0, hipEvent_t e1) {
     static unsigned* queue = nullptr;
@@ -360,6 +467,12 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
+    if (argc > 3 && !strcmp(argv[3], "chain")) {   // only the chained-sweep table
+        chain_table(s, N, ld, B, bytes, e0, e1);
+        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { printf("HIP error\n"); return 1; }
+        hipFree(s);
+        return 0;
+    }
     struct Cfg { int map, row_blocks, order; const char* name; } cfgs[] = {
         {0, 1, 0, "whole strips, filter on one XCD"}, {1, 1, 0, "whole strips, strips round the XCDs"},
         {0, 16, 0, "16 row blocks, strips fastest "}, {0, 16, 1, "16 row blocks, blocks fastest "},
