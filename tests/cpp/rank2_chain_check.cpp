@@ -46,6 +46,39 @@ static void sweep_items(int B, int N, int m) {
     CHECK(bad == 0, "B=%d N=%d m=%d: %zu tiles not visited exactly once", B, N, m, bad);
 }
 
+// The shapes of tests/rank2_chain_cases.py (tests/test_rank2_chain_host.py holds the printed table against that module): on
+// 256 compute units, with the row's packing setting, a correction takes the tile queue, a step of two slots chains, and ld,
+// column chunks, 16-row tiles and the rows of the last tile are what the case is there for.
+struct Case {
+    const char* name;
+    int n, B, ld, chunks, row_blocks, last_rows, packing;
+};
+
+static void check_cases() {
+    const Case table[] = {{"one-chunk", 250, 256, 512, 1, 32, 7, 1},  {"narrow-ld", 478, 72, 960, 2, 60, 15, 1},
+                          {"one-row", 503, 64, 1024, 2, 64, 1, 1},    {"three-chunk", 700, 32, 1408, 3, 88, 11, 0},
+                          {"four-chunk", 1000, 24, 2048, 4, 126, 3, 1}, {"long-call", 500, 80, 1024, 2, 63, 11, 1}};
+    for (const Case& k : table) {
+        const int N = 3 + 2 * k.n, ld = ekf::pick_ld(N);
+        ekf::Rank2Tuning t = tuning();
+        t.row_packing = k.packing;
+        const ekf::Rank2Plan single = ekf::rank2_plan(k.B, N, ld, t, true, true, 256);
+        const ekf::ChainPlan c = ekf::rank2_chain_plan(k.B, N, ld, single, true, true, true, 2, 0, 0);
+        const int last_rows = N - (c.row_blocks - 1) * c.rows;
+        CHECK(single.kind == ekf::RANK2_QUEUE, "%s: kind %d P %d", k.name, single.kind, single.P);
+        CHECK(c.chains == 1, "%s does not chain", k.name);
+        CHECK(ld == k.ld && c.chunks == k.chunks && c.row_blocks == k.row_blocks && last_rows == k.last_rows,
+              "%s: ld %d chunks %d row blocks %d last rows %d", k.name, ld, c.chunks, c.row_blocks, last_rows);
+        if (!k.packing) {   // with packing on the pool would be packed, not queued
+            const ekf::Rank2Plan packed = ekf::rank2_plan(k.B, N, ld, tuning(), true, true, 256);
+            CHECK(packed.kind == ekf::RANK2_PACKED, "%s: packing on gives kind %d", k.name, packed.kind);
+        }
+        std::printf("case %s n=%d B=%d N=%d ld=%d chunks=%d row_blocks=%d last_rows=%d packing=%d\n", k.name, k.n, k.B, N, ld,
+                    c.chunks, c.row_blocks, last_rows, k.packing);
+    }
+    std::printf("ok cases %d\n", failures);
+}
+
 int main(int argc, char** argv) {
     const int head_n = argc > 1 ? std::atoi(argv[1]) : 1000, head_B = argc > 2 ? std::atoi(argv[2]) : 4096;
     const int shapes[][2] = {{head_B, 3 + 2 * head_n}, {24, 2003}, {80, 1003}, {70, 1005}, {1, 2003}, {3, 17}, {2, 16}, {5, 513},
@@ -72,5 +105,6 @@ int main(int argc, char** argv) {
     CHECK(ekf::rank2_chain_plan(head_B, N, ld, q, true, true, true, 2, 4, ekf::kChainPolicyExplicit | 5).policy == 5, "explicit");
     CHECK(ekf::rank2_chain_plan(head_B, N, ld, q, true, true, true, 2, 4, ekf::kChainPolicyExplicit).policy == 0, "explicit 0");
     std::printf("ok conditions %d\n", failures);
+    check_cases();
     return failures ? 1 : 0;
 }
