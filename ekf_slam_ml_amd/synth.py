@@ -253,8 +253,15 @@ def make_known_log(cfg: SimConfig) -> KnownLog:
             continue
         rng2 = rf[:, :, 0] ** 2 + rf[:, :, 1] ** 2
         k = min(vmax, n)
-        near = np.argpartition(rng2, k - 1, axis=1)[:, :k] if k < n else np.tile(np.arange(n), (B, 1))
-        near.sort(axis=1)                                            # ascending landmark index
+        if k < n:
+            # the k first in ascending (d2, landmark index), the rule of k_sim_readings: everything below the k-th
+            # smallest d2, then the lowest indices among those equal to it (a partial sort alone leaves ties to chance)
+            kth = np.partition(rng2, k - 1, axis=1)[:, k - 1:k]
+            below, tie = rng2 < kth, rng2 == kth
+            take = below | (tie & (np.cumsum(tie, axis=1) <= k - below.sum(axis=1, keepdims=True)))
+            near = np.nonzero(take)[1].reshape(B, k)                 # ascending landmark index
+        else:
+            near = np.tile(np.arange(n), (B, 1))
         d2 = np.take_along_axis(rng2, near, axis=1)
         ok = d2 <= cfg.max_visible_dis ** 2
         nu = near.astype(np.uint64)
