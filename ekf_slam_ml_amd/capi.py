@@ -63,6 +63,7 @@ SYMBOLS = [
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
     "ekf_dense64_frame_launch_info", "ekf_dense64_map_congruence", "ekf_dense64_reframe_landmarks",
     "ekf_dense64_join_launch_info", "ekf_dense64_join_congruence", "ekf_dense64_join_map",
+    "ekf_dense64_extract_launch_info", "ekf_dense64_extract_map",
     "ekf_dense64_init_block", "ekf_dense64_swap_blocks", "ekf_dense64_get_sigma_block", "ekf_dense64_get_state_block", "ekf_dense64_set_state_block",
     "ekf_batch_rank2_variant", "ekf_batch_rank2_resident", "ekf_batch_rank2_packing", "ekf_batch_spec_counts",
     "ekf_batch_set_chain", "ekf_batch_chain_counts",
@@ -292,6 +293,8 @@ def load():
         "ekf_dense64_join_launch_info": [h, _ip, _ip, _ip],
         "ekf_dense64_join_congruence": [h, h, _dp, _dp, _dp],
         "ekf_dense64_join_map": [h, h, _dp, _dp],
+        "ekf_dense64_extract_launch_info": [h, _ip, _ip, _ip],
+        "ekf_dense64_extract_map": [h, h, C.c_int, _ip, _dp],
         "ekf_dense64_init_block": [h, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp],
         "ekf_dense64_swap_blocks": [h, C.c_int, C.c_int, C.c_int, _dp],
         "ekf_dense64_get_sigma_block": [h, C.c_int, _ip, C.c_int, _ip, _dp],
@@ -1397,6 +1400,49 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_join_launch_info(self._h, C.byref(tr), C.byref(tc), C.byref(th)))
         return {"tile_rows": tr.value, "tile_cols": tc.value, "threads": th.value}
 
+    def extract_map(self, src, keep=None):
+        """This handle becomes a copy of src's map, or of a submap of it (ekf_dense64_extract_map, include/ekfslam.h): the
+        pose and the landmarks keep[0], keep[1], ... of src (distinct, any order; None: all of them in order, a clone), by
+        Sigma[i][j] = Sigma_src[iota(i)][iota(j)] and state[i] = state_src[iota(i)] with iota(3 + 2 t + c) = 3 + 2 keep[t] + c,
+        every bit kept.  live becomes 3 + 2 len(keep); nothing at an index from it on is touched.  src's pending rows are
+        carried into this handle, not applied, and src is unchanged (an open region on it ends first); this handle's own
+        pending rows are applied and its region is ended first.  Returns elapsed_ms"""
+        src = self._join_source(src)
+        if src is self:
+            raise ValueError("extract_map() is out of place: the source must be another handle")
+        if keep is None:
+            ms = C.c_double()
+            _check(self._lib.ekf_dense64_extract_map(self._h, src._h, -1, None, C.byref(ms)))
+            return ms.value
+        a = np.asarray(keep)
+        if a.ndim != 1 or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("keep must be a list of landmark indices (one dimension, integers)")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a.size and a.min() < 0:
+            raise ValueError("every index of keep must be a landmark of the source, in [0, b)")
+        if np.unique(a).size != a.size:
+            raise ValueError("keep names a landmark twice")
+        if 3 + 2 * a.size > self.N:
+            raise ValueError(f"3 + 2 * {a.size} states do not fit N = {self.N}")
+        if src.region_info()["active"]:   # (the library would end it and take the live dimension behind it: keep could not be checked)
+            raise ValueError("the source is inside a local region: end it before extract_map() with a list")
+        b = (src.live - 3) // 2
+        if a.size and a.max() >= b:
+            raise ValueError(f"every index of keep must be a landmark of the source, in [0, {b})")
+        k = int(a.size)
+        a = np.ascontiguousarray(a if k else [0], dtype=np.int32)   # (an empty list is still a list: never a null pointer)
+        ms = C.c_double()
+        _check(self._lib.ekf_dense64_extract_map(self._h, src._h, k, a.ctypes.data_as(_ip), C.byref(ms)))
+        return ms.value
+
+    def extract_launch_info(self):
+        """{tile_rows, tile_cols, threads}: the tile of extract_map()'s pass over this handle's Sigma[3:Nd, 3:Nd] in states
+        (origins at 3 + a tile_rows, 3 + b tile_cols) and its workgroup size (test hook)"""
+        self._open()
+        tr, tc, th = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_extract_launch_info(self._h, C.byref(tr), C.byref(tc), C.byref(th)))
+        return {"tile_rows": tr.value, "tile_cols": tc.value, "threads": th.value}
+
     def _sparse_operands(self, cols, Hc, R, nu, max_m):
         """the shape and range checks of a sparse correction -> (cols int32, Hc, R, nu or None, m, s), contiguous"""
         cols = self._index_lists(cols, 1)
@@ -1861,6 +1907,7 @@ class DenseEKFSLAM:
         if deferred and joseph:
             raise ValueError("joseph is an eager form: not with deferred")
         self.deferred, self.grow_live, self.params, self.joseph = bool(deferred), bool(grow_live), params, bool(joseph)
+        self._device = device
         self.handle = d = DensePropagator64(3 + 2 * cap, device)
         # the constructor's prior (:27-46): Sigma zero (as created) except 100 I on the landmarks; the state zero
         for first in range(3, d.N, d.MAX_R):
@@ -2026,6 +2073,73 @@ class DenseEKFSLAM:
                 d.live = live
         self._known += other._known
         return ms
+
+    def _copy_target(self, into):
+        """the filter a copy goes into: a new one with this filter's n, capacity, flags and params, or `into` if it has them"""
+        cap = (self.handle.N - 3) // 2
+        if into is None:
+            return DenseEKFSLAM(self.n, cap, self.deferred, self.handle.carry, self.grow_live, self.params, self._device,
+                                self.joseph)
+        if not isinstance(into, DenseEKFSLAM) or into is self:
+            raise ValueError("`into` must be another DenseEKFSLAM")
+        if (into.n, into.handle.N) != (self.n, self.handle.N):
+            raise ValueError(f"`into` must have n = {self.n} and capacity = {cap}")
+        if (into.deferred, into.grow_live, into.joseph) != (self.deferred, self.grow_live, self.joseph):
+            raise ValueError("`into` must have the same deferred, grow_live and joseph flags")
+        if into.handle.carry != self.handle.carry:
+            raise ValueError("`into` must have the same carry flag")
+        into.params = self.params
+        return into
+
+    def clone(self, into=None):
+        """a second DenseEKFSLAM that holds the same filter (DensePropagator64.extract_map, one pass on the device, nothing
+        through the host): the same n, capacity, flags and params, the same known landmarks, init flag, live dimension and
+        -- in a deferred filter -- the same pending rows, which are carried and not applied, so a snapshot in mid-tick costs
+        no flush.  The copy covers the live dimension; beyond it a new filter has the constructor's prior, as this one has,
+        and a reused one keeps what it had (a grow_live filter initialises those states again when its map reaches them).
+        into: a filter of the same shape and flags to overwrite instead of building one.  Snapshot, run data_association()
+        on one and joint_association() on the other, keep one -- or restore()."""
+        t = self._copy_target(into)
+        t.handle.extract_map(self.handle)
+        t._known, t._init_flag = self._known, self._init_flag
+        return t
+
+    def restore(self, snap):
+        """this filter becomes the one `snap` holds (a clone() taken earlier): snap.clone(into=self)"""
+        if not isinstance(snap, DenseEKFSLAM):
+            raise ValueError("restore() takes a DenseEKFSLAM")
+        return snap.clone(into=self)
+
+    def submap(self, keep, into=None):
+        """a DenseEKFSLAM of the same shape that knows the landmarks keep[0], keep[1], ... of this filter (distinct, each in
+        [0, known), any order) as its landmarks 0 .. k - 1, with this filter's pose: the marginal of the filter on them, which
+        for an EKF is the deletion of the other rows and columns and therefore exact.  The inverse of join() (hand the
+        submap to another process, join() it into a fresh global filter), and pruning in bulk (keep the k landmarks worth
+        keeping, go on with the result).  Refused once measurement() has placed all n landmarks, as join() is.  Pending rows
+        are carried.  A target that is not grow_live gets its live dimension back to 3 + 2 n, after coupling() has found
+        the states beyond the submap decoupled from it (which flushes the carried rows): a new target has the
+        constructor's prior there; a reused `into` may not, and is then refused -- with the submap in its first 3 + 2 k
+        states and its live dimension there."""
+        if self._init_flag:
+            raise ValueError("submap() picks among the known landmarks of data_association(); measurement() placed all n")
+        a = np.asarray(keep)
+        if a.ndim != 1 or not (a.size == 0 or np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("keep must be a list of landmark indices (one dimension, integers)")
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self._known):
+            raise ValueError(f"every index of keep must be a known landmark, in [0, {self._known})")
+        if np.unique(a).size != a.size:
+            raise ValueError("keep names a landmark twice")
+        t = self._copy_target(into)
+        t.handle.extract_map(self.handle, a)
+        t._known, t._init_flag = int(a.size), False
+        W, full = 3 + 2 * int(a.size), 3 + 2 * t.n
+        if not t.grow_live and W < full:
+            if t.handle.coupling(W)[0] != 0:
+                raise ValueError(f"`into` holds states beyond {W} that are coupled to the submap (not the constructor's "
+                                 f"prior): its live dimension stays {W}")
+            t.handle.live = full
+        return t
 
     def map_nees(self, truth):
         """(state - truth)^T Sigma^-1 (state - truth) over the live dimension against the last factor(): the NEES of the

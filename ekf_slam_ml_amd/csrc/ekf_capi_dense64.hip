@@ -7,7 +7,8 @@
 // scan of all landmark pairs for duplicates and their merge (ekf_dense64_pairs.hip), the health check of the live corner and its
 // exact symmetrisation (ekf_dense64_health.hip), its Cholesky factor with the substitution against it
 // (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), the
-// map re-expressed in another frame (ekf_dense64_frame.hip), a second handle's map joined onto it (ekf_dense64_join.hip), and
+// map re-expressed in another frame (ekf_dense64_frame.hip), a second handle's map joined onto it (ekf_dense64_join.hip), a map
+// or a submap copied into a second handle (ekf_dense64_extract.hip), and
 // the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
@@ -1210,6 +1211,82 @@ ekf_status ekf_dense64_join_congruence(ekf_dense64_handle dst, ekf_dense64_handl
 
 ekf_status ekf_dense64_join_map(ekf_dense64_handle dst, ekf_dense64_handle src, double* terms_out, double* elapsed_ms) {
     return dense64_join("ekf_dense64_join_map", dst, src, true, nullptr, nullptr, terms_out, elapsed_ms);
+}
+
+// ---- a map or a submap copied into a second handle (ekf_dense64_extract.hip) ------------------------------------------------
+ekf_status ekf_dense64_extract_launch_info(ekf_dense64_handle d, int* tile_rows, int* tile_cols, int* threads) {
+    if (!d || !tile_rows || !tile_cols || !threads)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_extract_launch_info: null argument");
+    *tile_rows = ekf::kDense64ExtractTileRows;
+    *tile_cols = ekf::kDense64ExtractTileCols;
+    *threads = ekf::kDense64ExtractThreads;
+    return EKF_OK;
+}
+
+// The refusals in the header's order (host only: a region that either handle is in stays open when one strikes), the list
+// with its run flags into the workspace from the destination's ledger, the destination's panels if the source has rows
+// pending and the destination has none; then behind the destination's e0 its own region end and pending rows, the source's
+// region end on the source's stream with an event the destination's stream waits on, the launches, and the destination's
+// new live dimension and pending count.  The source's pending rows are neither applied nor counted down.
+ekf_status ekf_dense64_extract_map(ekf_dense64_handle dst, ekf_dense64_handle src, int k, const int* keep, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_extract_map";
+    const std::string fn = fnc;
+    if (!dst) return fail(EKF_ERR_INVALID, fn + ": null destination handle");
+    if (!src) return fail(EKF_ERR_INVALID, fn + ": null source handle");
+    if (dst == src) return fail(EKF_ERR_INVALID, fn + ": the destination and the source are the same handle");
+    if (dst->device != src->device) return fail(EKF_ERR_INVALID, fn + ": the two handles live on different devices");
+    const RegionLeave leaving_dst(dst), leaving_src(src);   // outside a region's terms: it ends behind the checks and e0
+    const int Nb = src->live;
+    if (Nb < 3 || Nb % 2 == 0)
+        return fail(EKF_ERR_INVALID, fn + ": the source's live dimension must be 3 + 2 b (a pose and whole landmarks)");
+    const int b = (Nb - 3) / 2;
+    if (keep ? k < 0 : (k != -1 && k != b))
+        return fail(EKF_ERR_INVALID, fn + ": k must be >= 0, and with a null list b (the source's landmarks) or -1");
+    if (!keep) k = b;
+    if (keep) {
+        for (int t = 0; t < k; t++)
+            if (keep[t] < 0 || keep[t] >= b)
+                return fail(EKF_ERR_INVALID, fn + ": every index of keep must be a landmark of the source, in [0, b)");
+        std::vector<int>& stamp = dst->host_stamp;
+        stamp.assign(b, 0);
+        for (int t = 0; t < k; t++)
+            if (stamp[keep[t]]++) return fail(EKF_ERR_INVALID, fn + ": keep names a landmark twice");
+    }
+    if (3 + 2 * (long long)k > dst->N)
+        return fail(EKF_ERR_INVALID, fn + ": the extracted map (3 + 2 k states) does not fit the destination's N");
+    HIPC(hipSetDevice(dst->device));
+    const ekf::Dense64ExtractPlan pl = ekf::dense64_extract_plan(Nb, src->ld, k, dst->ld);
+    const int p = src->region_leaving ? 0 : src->pend_rows;   // (a region's end applies the rows it finds)
+    EKFC(dst->extract.reserve(dst->mem, sizeof(int) * pl.ints, false, fnc, "the extraction's list"));
+    if (p > 0) EKFC(pend_reserve(dst, fnc));
+    std::vector<int>& up = dst->host_keep;   // the list | per column tile: its landmarks are a contiguous ascending run
+    up.assign(pl.ints, 0);
+    for (int t = 0; t < k; t++) up[pl.off_keep + t] = keep ? keep[t] : t;
+    constexpr int kLc = ekf::kDense64ExtractTileCols / 2;
+    for (int c = 0; c < pl.corner_gx; c++) {
+        const int* first = up.data() + pl.off_keep + (size_t)c * kLc;
+        const int n = std::min(kLc, k - c * kLc);
+        int l = 1;
+        while (l < n && first[l] == first[0] + l) l++;
+        up[pl.off_run + c] = l == n;
+    }
+    int* ws = dst->extract.as<int>();
+    HIPC(hipMemcpyAsync(ws, up.data(), sizeof(int) * pl.ints, hipMemcpyHostToDevice, dst->stream));
+    HIPC(hipEventRecord(dst->e0, dst->stream));
+    dst->flush_pending();   // the destination is overwritten: its region ends, its own rows are applied
+    src->finish_leave();    // (on the source's stream; nothing when no region is open: its rows stay pending)
+    HIPC(hipEventRecord(src->e1, src->stream));
+    HIPC(hipStreamWaitEvent(dst->stream, src->e1, 0));
+    ekf::launch_dense64_extract(pl, dst->S, dst->x, src->S, src->x, ws, dst->stream);
+    if (p > 0) {
+        const PendView from = src->panels(), to = dst->panels();
+        ekf::launch_dense64_extract_panels(pl, to.K, to.T, from.K, from.T, p, ws, dst->stream);
+    }
+    EKFC(finish_timed(dst, elapsed_ms));
+    dst->live = pl.Nd;
+    dst->pl_live = ekf::dense64_live_plan(dst->pl_full, dst->live);
+    dst->pend_rows = p;
+    return EKF_OK;
 }
 
 // ---- duplicate landmarks: the all-pairs scan (ekf_dense64_pairs.hip) and the merge, a layer over the calls above ----------

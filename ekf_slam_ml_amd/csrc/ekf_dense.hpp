@@ -385,6 +385,43 @@ void launch_dense64_join_state(const Dense64JoinPlan& p, double* state_dst, cons
 void launch_dense64_join_congruence(const Dense64JoinPlan& p, double* Sigma_dst, const double* Sigma_src, double* ws,
                                     hipStream_t st);
 
+// ---- a map or a submap copied into a second handle (ekf_dense64_extract.hip; the definition is include/ekfslam.h's,
+// ekf_dense64_extract_map): Sigma_dst[i][j] = Sigma_src[iota(i)][iota(j)], x_dst[i] = x_src[iota(i)] over [0, Nd), bits kept,
+// iota: 0, 1, 2 -> 0, 1, 2 and 3 + 2 t + c -> 3 + 2 keep[t] + c.  Everything runs on the one stream given: the destination's.
+constexpr int kDense64ExtractTileRows = 64;    // the hot pass: tiles of the DESTINATION's Sigma[3:Nd, 3:Nd], origins on odd indices
+constexpr int kDense64ExtractTileCols = 128;
+constexpr int kDense64ExtractThreads = 256;
+// the workspace of a call (from the destination's ledger), offsets in ints: keep [k], zeros up to 64 corner_gx | run [corner_gx], run[b] != 0 where
+// the landmarks of column tile b are a contiguous ascending run of the source (keep[64 b + l] = keep[64 b] + l)
+struct Dense64ExtractPlan {
+    int Nb, Nd, k, ld_src, ld_dst;   // Nd = 3 + 2 k
+    int corner_gx, corner_gy;        // k_ex_corner's grid (0 x 0 at k = 0: not launched)
+    int panel_cols;                  // a carried pending row is written on [0, panel_cols): Nd rounded up to kDenseTile, at most ld_dst
+    size_t off_keep, off_run, ints;
+};
+inline Dense64ExtractPlan dense64_extract_plan(int Nb, int ld_src, int k, int ld_dst) {
+    Dense64ExtractPlan p{};
+    p.Nb = Nb, p.Nd = 3 + 2 * k, p.k = k, p.ld_src = ld_src, p.ld_dst = ld_dst;
+    p.corner_gx = (2 * k + kDense64ExtractTileCols - 1) / kDense64ExtractTileCols;
+    p.corner_gy = (2 * k + kDense64ExtractTileRows - 1) / kDense64ExtractTileRows;
+    const int up = (p.Nd + kDenseTile - 1) / kDenseTile * kDenseTile;
+    p.panel_cols = up < ld_dst ? up : ld_dst;
+    p.off_keep = 0;
+    p.off_run = (size_t)p.corner_gx * (kDense64ExtractTileCols / 2);   // (the list padded with zeros to whole column tiles)
+    p.ints = p.off_run + (size_t)p.corner_gx + 4;                      // (never empty)
+    return p;
+}
+// Two launches: the pass over the destination's Sigma[3:Nd, 3:Nd] (k > 0), and the pose rows and columns, the 3 x 3 corner
+// and the Nd states.  ws: the list and the flags as the plan lays them out.  The source is read only and nothing of it at an
+// index >= Nb is read (every keep[t] < (Nb - 3) / 2: the caller checks); nothing of the destination at an index >= Nd is
+// read or written.
+void launch_dense64_extract(const Dense64ExtractPlan& p, double* Sigma_dst, double* state_dst, const double* Sigma_src,
+                            const double* state_src, const int* ws, hipStream_t st);
+// One launch (none at rows = 0): the first `rows` rows of the source's pending panels through the same index map into the
+// destination's, zero on [Nd, panel_cols).
+void launch_dense64_extract_panels(const Dense64ExtractPlan& p, double* K_dst, double* T_dst, const double* K_src,
+                                   const double* T_src, int rows, const int* ws, hipStream_t st);
+
 // ---- a local region (ekf_dense64_region.hip; plan and layout in ekf_dense64_region.hpp, the definition is
 // include/ekfslam.h's, ekf_dense64_region_begin): the accumulators Phi, Psi, theta of the compressed filter in `acc`
 // (Dense64RegionPlan::acc_bytes), the two panels of the global update in `scratch` (scratch_bytes).

@@ -110,10 +110,12 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf whiten;     // ekf_dense64_whiten: the working copy of B and Y, then d2
     ekfrt::DeviceBuf frame;      // Dense64FramePlan (ekf_dense64_map_congruence, ekf_dense64_reframe_landmarks), a function of ld
     ekfrt::DeviceBuf join;       // Dense64JoinPlan (ekf_dense64_join_congruence, ekf_dense64_join_map) of the DESTINATION, grows with Nb
+    ekfrt::DeviceBuf extract;    // Dense64ExtractPlan (ekf_dense64_extract_map) of the DESTINATION: the list and the run flags, grows with k
     ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads
     std::vector<int> host_stamp; // [N] the duplicate check of the index lists
+    std::vector<int> host_keep;  // ekf_dense64_extract_map: the list and the run flags on their way up
     int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
     int factor_na = 0;           // the live dimension the snapshot was taken at, 0 before the first factor
     int factor_ok = 0;           // the snapshot is a complete factor (the last ekf_dense64_factor ended with ok == 1)

@@ -1076,7 +1076,7 @@ ekf_status ekf_dense64_coupling(ekf_dense64_handle h, int Na,
  * element, as the live launches do.
  * EVERY OTHER CALL ENDS THE REGION FIRST and then runs as it always did, so no result is ever stale: get_sigma, get_state,
  * set, set_state, propagate, correct, score, swap_blocks, health, symmetrize, factor, coupling, map_congruence,
- * reframe_landmarks, join_congruence, join_map (on either handle), score_landmark_pairs, merge_landmarks, score_readings, joint_operands, associate_joint,
+ * reframe_landmarks, join_congruence, join_map, extract_map (on either handle), score_landmark_pairs, merge_landmarks, score_readings, joint_operands, associate_joint,
  * associate_scan, associate_scan_joint, correct_sparse_joseph and EKF_DENSE64_LM_JOSEPH, set_live (also the one inside
  * EKF_DENSE64_LM_GROW_LIVE), and a block readout or state block with an index >= Na.  Such a call checks its arguments
  * first, against the live dimension the region found -- a REFUSED call ends nothing, the region stays open -- and the
@@ -1525,6 +1525,54 @@ ekf_status ekf_dense64_join_congruence(ekf_dense64_handle dst, ekf_dense64_handl
                                        const double* E /* [Nb][3] */, double* elapsed_ms);
 ekf_status ekf_dense64_join_map(ekf_dense64_handle dst, ekf_dense64_handle src, double* terms_out /* [4 + 3 Nb], nullable */,
                                 double* elapsed_ms);
+
+/* A map, or a submap, copied into a second handle: the inverse of the join, and the only copy of a dense filter that does
+ * not go through the host.  Three uses, one operation: a SNAPSHOT before an ambiguous association or a merge (keep == NULL:
+ * a clone; run both branches, keep one, or extract back to restore); a SUBMAP cut out of the global map, the pose plus a
+ * chosen list of landmarks -- the EKF's marginalisation is the deletion of rows and columns, so the submap is exact; and
+ * PRUNING many landmarks at once, k of b kept in one out-of-place pass instead of one swap_blocks / init_block / set_live
+ * per landmark.
+ * THE DEFINITION.  src has the live dimension Nb = 3 + 2 b.  keep [k]: landmarks of src in [0, b), no repeats, any order;
+ * keep == NULL is the identity list of all b (k is then b, or -1 for "whatever b is"); k = 0 copies the pose alone.  With
+ *   iota(0, 1, 2) = 0, 1, 2,   iota(3 + 2 t + c) = 3 + 2 keep[t] + c  (c = 0, 1),   Nd = 3 + 2 k:
+ *   Sigma_dst[i][j] takes the bits of Sigma_src[iota(i)][iota(j)],  x_dst[i] the bits of x_src[iota(i)],  i, j < Nd,
+ * and dst's live dimension becomes Nd.  A PURE COPY: no arithmetic, so a NaN keeps its payload, a zero its sign and a Sigma
+ * that is never symmetrised its asymmetry.  Nothing at a dst index >= Nd is read or written, nothing at a src index >= Nb is
+ * read, whatever either handle's N and ld are.
+ * PENDING ROWS ARE CARRIED, NOT APPLIED.  A pending row is linear in the same index, so when src has p rows pending
+ * (ekf_dense64_pending) dst has the same p afterwards: K_dst[q][i] = K_src[q][iota(i)] and T likewise, zero from Nd up to the
+ * width the calls of that live width keep zero (Nd rounded up to 128, at most ld: ekf_dense64_set_live's convention).  A
+ * snapshot in mid-tick therefore costs no flush, and Sigma_cur of dst (ekf_dense64_get_sigma_block under carry) is Sigma_cur
+ * of src at iota x iota bit for bit.  dst's panels come from its ledger if it has none.  SRC IS UNCHANGED BIT FOR BIT: Sigma,
+ * state, pending rows, their count and the live dimension -- except that an open region on src is ended first, on src's
+ * stream, like every call outside a region's terms (which applies the rows pending inside it: p is then 0).  DST IS THE ONE
+ * OVERWRITTEN: an open region on it is ended and its own pending rows are applied first, as the join does, inside the timed
+ * region; it costs nothing when nothing is pending.  dst's carry flag, factor snapshot and tuning stay as they are.
+ * REFUSALS.  Every refusal returns EKF_ERR_INVALID before the device is looked at and changes nothing in either handle, the
+ * pending rows and an open region included.  THE CHECKS COME IN THIS ORDER: (1) NULL dst; (2) NULL src; (3) dst == src;
+ * (4) the handles live on different devices; (5) src's live dimension not odd or below 3; (6) k < 0, or keep == NULL with k
+ * neither b nor -1; (7) an index of keep outside [0, b); (8) an index of keep repeated; (9) 3 + 2 k > dst's N.  A failed
+ * ledger allocation (the list's workspace, 4 (65 ceil(k / 64) + 4) bytes, or the panels) returns EKF_ERR_NOMEM and leaves
+ * both handles as they were.
+ * STREAMS as the join's: src's region end runs on src's own stream, an event recorded there is waited on by dst's stream,
+ * every extract launch runs on dst's stream, which is synchronised before the call returns.
+ * THE LAUNCHES.  The list goes up once, with one flag per column tile found while it is validated.  The hot kernel makes one
+ * pass over dst's Sigma[3:Nd, 3:Nd] in the frame and join passes' shape: tiles of tile_rows x tile_cols states whose ORIGINS
+ * SIT ON ODD INDICES, a 2 x 2 block per lane, 16-byte loads along src's rows all issued before the first store, stores along
+ * dst's rows, no LDS.  A tile's row landmarks are wave-uniform and come through the scalar cache.  A COLUMN TILE WHOSE
+ * LANDMARKS ARE A CONTIGUOUS ASCENDING RUN OF SRC (a clone, a prefix, any list of runs of 64 on tile boundaries) takes its
+ * columns from the tile's first landmark plus the lane: a wave's load is 1 KiB of one src row, the join kernel's access.  Any
+ * other tile reads its landmarks from the list: the same result from sixty-four separate 16-byte pieces of the row.  A
+ * sibling launch copies the three pose rows and columns, the 3 x 3 corner and the Nd states; one more, when p > 0, the
+ * p x Nd rows of both panels.  NO ATOMICS, NO REDUCTIONS: A RUN REPEATS BIT FOR BIT.  ekf_dense64_extract_launch_info reports
+ * the hot kernel's tile sides in states and its workgroup size.  Bytes: 16 Nd^2 (8 read, 8 written) plus 32 p Nd.
+ * Out of scope: extraction in place (dst == src), across devices, and a general state list that breaks landmark pairs.
+ * Synchronous.  elapsed_ms (nullable) = HIP-event time on dst's stream, dst's own flush and region end included; the upload
+ * of the list is queued in front of it and is not. */
+ekf_status ekf_dense64_extract_launch_info(ekf_dense64_handle h, int* tile_rows, int* tile_cols, int* threads);
+ekf_status ekf_dense64_extract_map(ekf_dense64_handle dst, ekf_dense64_handle src,
+                                   int k, const int* keep /* [k] landmarks of src, any order; NULL = all, in order */,
+                                   double* elapsed_ms);
 
 /* Block readout and state slices: what a caller that publishes the 3 x 3 pose covariance every tick, or wraps the heading
  * after a correction, needs instead of the N^2 doubles of ekf_dense64_get_sigma and the N of get_state / set_state.
