@@ -12,9 +12,7 @@
 //                 of 256 state indices or scores the NEXT reading for 256 landmarks -- see the kernel.
 // Same operations in the same order as k_maha + k_assoc_decide + k_gain + k_rank2 -> decisions, state and covariance
 // bit-identical (tests/test_gpu_forms.py, tests/test_gpu_callfused.py).
-#include "ekf_kernels.hpp"
-
-#include <climits>
+#include "ekf_assoc.hpp"
 
 namespace ekf {
 
@@ -34,7 +32,7 @@ __global__ __launch_bounds__(64) void k_assoc_score(PoolView pv, double mx, doub
     const double* __restrict__ st = pv.state;
     const int M = assoc_in[0].known_count;
     if (i >= pv.n || (i >= M && !blk)) return;
-    double S55[5][5], S[2][2], Si[2][2];
+    double S55[5][5], Si[2][2];
 #pragma unroll
     for (int k = 0; k < 5; k++)
 #pragma unroll
@@ -56,17 +54,10 @@ __global__ __launch_bounds__(64) void k_assoc_score(PoolView pv, double mx, doub
             kr[k][0] = Ub[(size_t)(2 * v) * ld + c]; kr[k][1] = Ub[(size_t)(2 * v + 1) * ld + c];
             gc[k][0] = Vb[(size_t)(2 * v) * ld + c]; gc[k][1] = Vb[(size_t)(2 * v + 1) * ld + c];
         }
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-#pragma unroll
-            for (int l = 0; l < 5; l++) S55[k][l] = S55[k][l] - (kr[k][0] * gc[l][0] + kr[k][1] * gc[l][1]);
+        fold_pair(S55, kr, gc);
     }
-    innovation_cov(S55, m.H, pv.p.r_meas, S);   // sums in the order of k_maha's shuffle folds
-    inv2(S, Si);
-    const double v0 = m.z0 - m.zh0, v1 = m.z1 - m.zh1;   // bearing NOT wrapped, :269
-    const double t0 = v0 * Si[0][0] + v1 * Si[1][0];
-    const double t1 = v0 * Si[0][1] + v1 * Si[1][1];
-    scores[i] = t0 * v0 + t1 * v1;
+    double v0, v1;
+    scores[i] = maha_score(S55, m, pv.p.r_meas, Si, v0, v1);
     // correction terms of every scored landmark, [16][n]: consecutive landmarks are consecutive addresses
     double* tr = terms + i;
     const size_t ts = (size_t)pv.n;
@@ -224,39 +215,23 @@ __global__ __launch_bounds__(kAssocThreads) void k_assoc_reading(
     }
     AR_TR(1);
 
-    // ---- 2. decision, :293-330 ----
+    // ---- 2. decision, :293-330 (ekf_assoc.hpp) ----
     double rd = best;
     int ri = bi;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_down(rd, off, kWave);
-        const int oi = __shfl_down(ri, off, kWave);
-        if (od < rd || (od == rd && oi < ri)) { rd = od; ri = oi; }
-    }
-    if (lane == 0) { sh_d[wave] = rd; sh_i[wave] = ri; }
+    block_argmin_stage(rd, ri, sh_d, sh_i);
     __syncthreads();
     AR_TR(2);
     if (tid == 0) {
-        for (int w = 1; w < kAssocThreads / 64; w++)
-            if (sh_d[w] < rd || (sh_d[w] == rd && sh_i[w] < ri)) { rd = sh_d[w]; ri = sh_i[w]; }
-        const int idx = (ri == INT_MAX) ? M : ri;   // :294 min_maha_idx = known_count
-        int known_count = M, is_new = 0;
-        if (idx == M && idx < n) {                  // :318-327 new landmark
-            const double rr = sqrt(mx * mx + my * my);
-            const double phi = atan2(my, mx);
-            sh_t[0] = x + rr * cos(phi + theta);
-            sh_t[1] = y + rr * sin(phi + theta);
-            known_count = M + 1;
-            rd = 0.0;
-            is_new = 1;
-        }
-        const int active = (rd < pv.p.gate_update) && idx < n;   // :330
-        sh_lm = active ? idx : -1;
-        sh_new = is_new;
-        sh_Mn = known_count;
+        block_argmin_fold(rd, ri, sh_d, sh_i, kAssocThreads / 64);
+        const AssocDecision dec = assoc_decision(rd, ri, M, n, pv.p.gate_update);
+        const int idx = dec.idx, active = dec.active;
+        if (dec.is_new) landmark_from_reading(mx, my, theta, x, y, sh_t[0], sh_t[1]);   // :318-327, parked for step 3
+        sh_lm = dec.lm();
+        sh_new = dec.is_new;
+        sh_Mn = dec.known_count;
         if (lead) {
             AssocRec a;
-            a.known_count = known_count; a.lm = active ? idx : -1; a.active = active; a.pad = 0; a.best = rd;
+            a.known_count = dec.known_count; a.lm = dec.lm(); a.active = active; a.pad = 0; a.best = dec.best;
             assoc_next[0] = a;
             if (assoc_out_j) assoc_out_j[0] = a.lm;
             cnt_out[0] = pc + 1;
@@ -299,10 +274,7 @@ __global__ __launch_bounds__(kAssocThreads) void k_assoc_reading(
                     }
                     kr[3][0] = ua[v][0]; kr[3][1] = ua[v][1]; gc[3][0] = ua[v][2]; gc[3][1] = ua[v][3];
                     kr[4][0] = uv[v][0]; kr[4][1] = uv[v][1]; gc[4][0] = uv[v][2]; gc[4][1] = uv[v][3];
-#pragma unroll
-                    for (int k = 0; k < 5; k++)
-#pragma unroll
-                        for (int l = 0; l < 5; l++) S55[k][l] = S55[k][l] - (kr[k][0] * gc[l][0] + kr[k][1] * gc[l][1]);
+                    fold_pair(S55, kr, gc);
                 }
         }
     };
@@ -395,10 +367,7 @@ __global__ __launch_bounds__(kAssocThreads) void k_assoc_reading(
         for (int k = 0; k < 3; k++) { kr[k][0] = sh_Kp[k][0]; kr[k][1] = sh_Kp[k][1]; gc[k][0] = sh_Gp[k][0]; gc[k][1] = sh_Gp[k][1]; }
         kr[3][0] = sh_KA[lane][0]; kr[3][1] = sh_KA[lane][1]; gc[3][0] = sh_GA[lane][0]; gc[3][1] = sh_GA[lane][1];
         kr[4][0] = k0; kr[4][1] = k1; gc[4][0] = g0; gc[4][1] = g1;
-#pragma unroll
-        for (int k = 0; k < 5; k++)
-#pragma unroll
-            for (int l = 0; l < 5; l++) S55[k][l] = S55[k][l] - (kr[k][0] * gc[l][0] + kr[k][1] * gc[l][1]);
+        fold_pair(S55, kr, gc);
         if (blk) {   // (thread-private entries: the next launch's loads follow this launch in stream order)
 #pragma unroll
             for (int e = 0; e < 25; e++) blk[(size_t)e * n + li] = S55[e / 5][e % 5];
@@ -410,13 +379,8 @@ __global__ __launch_bounds__(kAssocThreads) void k_assoc_reading(
     m.z0 = sh_z[0]; m.z1 = sh_z[1];
     predicted_terms(sh_soA[lane], so, sh_pose[0], sh_pose[1], sh_pose[2], m);   // fresh pose, :219-221
     AR_TR(10);
-    double S[2][2], Si[2][2];
-    innovation_cov(S55, m.H, pv.p.r_meas, S);   // sums in the order of k_maha's shuffle folds
-    inv2(S, Si);
-    const double v0 = m.z0 - m.zh0, v1 = m.z1 - m.zh1;   // bearing NOT wrapped, :269
-    const double t0 = v0 * Si[0][0] + v1 * Si[1][0];
-    const double t1 = v0 * Si[0][1] + v1 * Si[1][1];
-    scores_out[li] = t0 * v0 + t1 * v1;
+    double Si[2][2], v0, v1;
+    scores_out[li] = maha_score(S55, m, pv.p.r_meas, Si, v0, v1);
     double* tr = terms_out + li;   // [16][n]
     const size_t ts = (size_t)n;
 #pragma unroll
@@ -447,7 +411,7 @@ __global__ __launch_bounds__(THREADS) void k_assoc_call(PoolView pv, AssocCallAr
                                                                     int* __restrict__ cnt_out, int zero_upto,
                                                                     long long* __restrict__ trace, char* pub_host,
                                                                     int pub_j0, unsigned pub_seq) {
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     // diagnostics (ekf_phase_trace): thread 0 stamps the 100 MHz wall clock, 16 slots per reading (slot 15 of reading 0: start)
 #define AC_TR(j, k) do { if (trace && tid == 0) trace[(j) * 16 + (k)] = wall_clock64(); } while (0)
     AC_TR(0, 15);
@@ -529,13 +493,8 @@ __global__ __launch_bounds__(THREADS) void k_assoc_call(PoolView pv, AssocCallAr
             MeasTerms m;
             m.z0 = sh_z[j][0]; m.z1 = sh_z[j][1];
             predicted_terms(pos[0], pos[1], theta, x, y, m);
-            double S[2][2], Si[2][2];
-            innovation_cov(S55, m.H, pv.p.r_meas, S);   // sums in the order of k_maha's shuffle folds
-            inv2(S, Si);
-            const double v0 = m.z0 - m.zh0, v1 = m.z1 - m.zh1;   // bearing NOT wrapped, :269
-            const double t0 = v0 * Si[0][0] + v1 * Si[1][0];
-            const double t1 = v0 * Si[0][1] + v1 * Si[1][1];
-            const double sc = t0 * v0 + t1 * v1;
+            double Si[2][2], v0, v1;
+            const double sc = maha_score(S55, m, pv.p.r_meas, Si, v0, v1);
             if (sc < best) { best = sc; bi = t; }   // :305-309 (NaN never wins)
             double* tr = sh_terms[t];
 #pragma unroll
@@ -544,44 +503,26 @@ __global__ __launch_bounds__(THREADS) void k_assoc_call(PoolView pv, AssocCallAr
             tr[14] = v0; tr[15] = v1;
         }
         AC_TR(j, 1);
-        // lexicographic (d, i) minimum = the sequential scan's first strict minimum
         double rd = best;
         int ri = bi;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_down(rd, off, kWave);
-            const int oi = __shfl_down(ri, off, kWave);
-            if (od < rd || (od == rd && oi < ri)) { rd = od; ri = oi; }
-        }
-        if (lane == 0) { sh_d[tid >> 6] = rd; sh_i[tid >> 6] = ri; }
+        block_argmin_stage(rd, ri, sh_d, sh_i);
         __syncthreads();
         AC_TR(j, 2);
-        if (tid == 0) {   // :293-330
-            for (int w = 1; w < (int)blockDim.x / 64; w++)
-                if (sh_d[w] < rd || (sh_d[w] == rd && sh_i[w] < ri)) { rd = sh_d[w]; ri = sh_i[w]; }
-            const int idx = (ri == INT_MAX) ? M : ri;   // :294 min_maha_idx = known_count
-            int Mn = M, is_new = 0;
-            if (idx == M && idx < n) {                  // :318-327 new landmark
-                const double rr = sqrt(mx * mx + my * my);
-                const double phi = atan2(my, mx);
-                sh_t[0] = x + rr * cos(phi + theta);
-                sh_t[1] = y + rr * sin(phi + theta);
-                Mn = M + 1;
-                rd = 0.0;
-                is_new = 1;
-            }
-            const int active = (rd < pv.p.gate_update) && idx < n;   // :330
-            sh_M = Mn;
-            sh_lm = active ? idx : -1;
-            sh_new = is_new;
-            assoc_out[j] = active ? idx : -1;
+        if (tid == 0) {   // :293-330 (ekf_assoc.hpp)
+            block_argmin_fold(rd, ri, sh_d, sh_i, (int)blockDim.x / 64);
+            const AssocDecision dec = assoc_decision(rd, ri, M, n, pv.p.gate_update);
+            if (dec.is_new) landmark_from_reading(mx, my, theta, x, y, sh_t[0], sh_t[1]);   // :318-327, parked for its thread
+            sh_M = dec.known_count;
+            sh_lm = dec.lm();
+            sh_new = dec.is_new;
+            assoc_out[j] = dec.lm();
             // The host's copy (mapped memory, see k_publish_assoc): the decision now, and behind the call's LAST decision the
             // record and the sequence number -- the host goes on while this launch builds the last gain.
             if (pub_host) {
-                reinterpret_cast<int*>(pub_host + kAssocDecOff)[pub_j0 + j] = active ? idx : -1;
+                reinterpret_cast<int*>(pub_host + kAssocDecOff)[pub_j0 + j] = dec.lm();
                 if (pub_seq && j == a.J - 1) {
                     AssocRec rec;
-                    rec.known_count = Mn; rec.lm = active ? idx : -1; rec.active = active; rec.pad = 0; rec.best = 0.0;
+                    rec.known_count = dec.known_count; rec.lm = dec.lm(); rec.active = dec.active; rec.pad = 0; rec.best = 0.0;
                     *reinterpret_cast<AssocRec*>(pub_host) = rec;
                     __threadfence_system();
                     *reinterpret_cast<volatile unsigned*>(pub_host + kAssocSeqOff) = pub_seq;
@@ -746,10 +687,7 @@ __global__ __launch_bounds__(THREADS) void k_assoc_call(PoolView pv, AssocCallAr
             for (int k = 0; k < 3; k++) { kr[k][0] = sh_K5[pc][k][0]; kr[k][1] = sh_K5[pc][k][1]; gc[k][0] = sh_G5[pc][k][0]; gc[k][1] = sh_G5[pc][k][1]; }
 #pragma unroll
             for (int q = 0; q < 2; q++) { kr[3 + q][0] = kq[q][0]; kr[3 + q][1] = kq[q][1]; gc[3 + q][0] = gq[q][0]; gc[3 + q][1] = gq[q][1]; }
-#pragma unroll
-            for (int k = 0; k < 5; k++)
-#pragma unroll
-                for (int l = 0; l < 5; l++) S55[k][l] = S55[k][l] - (kr[k][0] * gc[l][0] + kr[k][1] * gc[l][1]);
+            fold_pair(S55, kr, gc);
         }
         pc++;
         AC_TR(j, 8);

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kJointThreads) void k_djt_resolve(const Dense64LmRe
     if (kind == kDense64LmCorrect) {
         // among the MATCH readings that claim one landmark the smallest (best, j) keeps it
         for (int o = 0; o < J; o++)
-            if (o != j && s_kind[o] == kDense64LmCorrect && s_win[o] == win && lm_less(s_best[o], o, r.best, j)) kind = 0;
+            if (o != j && s_kind[o] == kDense64LmCorrect && s_win[o] == win && score_less(s_best[o], o, r.best, j)) kind = 0;
     } else if (kind == kDense64LmNew) {
         // the NEW readings take the slots known, known + 1, .. in ascending j while there is room
         for (int o = 0; o < j; o++) rank += s_kind[o] == kDense64LmNew;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kJointThreads) void k_djt_resolve(const Dense64LmRe
         }
         if (kind & kDense64LmNew) {
             const pair16 s = reinterpret_cast<const pair16*>(xy)[j];
-            lm_new_position(state[0], state[1], state[2], s.x, s.y, xb + 2 * rank);   // at the pose on entry
+            landmark_from_reading(s.x, s.y, state[0], state[1], state[2], xb[2 * rank], xb[2 * rank + 1]);   // at the pose on entry
         }
     }
     if (j == 0) {

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kLmThreads) void k_dlm_decide(const double* __restr
     double gate = best;
     if (win == known) {
         if (known < n_max) {   // :318-327 -- a new landmark; initialize_landmark (:200-214)
-            lm_new_position(state[0], state[1], state[2], sx, sy, xb);
+            landmark_from_reading(sx, sy, state[0], state[1], state[2], xb[0], xb[1]);
             W[0] = sigma0; W[1] = 0.0; W[2] = 0.0; W[3] = sigma0;
             kind = kDense64LmNew;
             gate = 0.0;

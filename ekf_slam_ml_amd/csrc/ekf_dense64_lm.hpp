@@ -2,11 +2,11 @@
 // joint form (ekf_dense64_joint.hip, a whole scan at once) share, so that neither holds a second copy:
 //   lm_store_terms   the operands of ONE (reading, landmark) candidate where k_dsp_score reads them
 //   Two, lm_insert, lm_merge, lm_block_min   the two smallest (score, index) pairs of a list, ties to the lower index
-//   lm_new_position  initialize_landmark (:200-214)
-// The model itself is measurement_terms of ekf_kernels.hpp.
+//                    (score_less of ekf_assoc.hpp)
+// The model itself is measurement_terms and landmark_from_reading of ekf_kernels.hpp.
 #pragma once
+#include "ekf_assoc.hpp"
 #include "ekf_dense.hpp"
-#include "ekf_kernels.hpp"
 
 namespace ekf {
 namespace lm {
@@ -43,11 +43,10 @@ struct Two {
     double b, r;
     int bi, ri;
 };
-__device__ __forceinline__ bool lm_less(double a, int ai, double b, int bi) { return a < b || (a == b && ai < bi); }
 __device__ __forceinline__ void lm_insert(Two& t, double v, int vi) {
-    if (lm_less(v, vi, t.b, t.bi)) {
+    if (score_less(v, vi, t.b, t.bi)) {
         t.r = t.b; t.ri = t.bi; t.b = v; t.bi = vi;
-    } else if (lm_less(v, vi, t.r, t.ri)) {
+    } else if (score_less(v, vi, t.r, t.ri)) {
         t.r = v; t.ri = vi;
     }
 }
@@ -81,14 +80,6 @@ __device__ __forceinline__ Two lm_block_min(const double* __restrict__ nis, int 
     if (tid == 0)
         for (int w = 1; w < kLmThreads / 64; w++) lm_merge(t, sh[w]);
     return t;
-}
-
-// initialize_landmark (:200-214): the reading (sx, sy) seen from the pose (theta, x, y)
-__device__ __forceinline__ void lm_new_position(double theta, double x, double y, double sx, double sy, double* xb) {
-    const double ri = sqrt(sx * sx + sy * sy);
-    const double phii = atan2(sy, sx);
-    xb[0] = x + ri * cos(phii + theta);
-    xb[1] = y + ri * sin(phii + theta);
 }
 
 }  // namespace lm

@@ -1,10 +1,8 @@
 // ekf_kernels.hip -- hand-written gfx950 kernels for the rigid2d::EKF_SLAM hot path.
 // See ekf_kernels.hpp for the HBM layout.  Reference line numbers are rigid2d/src/ekf_slam.cpp.
-#include "ekf_kernels.hpp"
+#include "ekf_assoc.hpp"
 
 #include <mutex>
-
-#include <limits.h>
 
 namespace ekf {
 
@@ -276,10 +274,7 @@ __global__ __launch_bounds__(256) void k_measure_begin(PoolView pv, const double
         if (i < pv.n) {
             const double sx = init_xy[(size_t)b * 2 * pv.n + 2 * i];
             const double sy = init_xy[(size_t)b * 2 * pv.n + 2 * i + 1];
-            const double ri = sqrt(sx * sx + sy * sy);
-            const double phii = atan2(sy, sx);
-            st[2 * i + 3] = x + ri * cos(phii + theta);
-            st[2 * i + 3 + 1] = y + ri * sin(phii + theta);
+            landmark_from_reading(sx, sy, theta, x, y, st[2 * i + 3], st[2 * i + 3 + 1]);
         }
     }
 }
@@ -887,11 +882,9 @@ __global__ __launch_bounds__(256) void k_maha(PoolView pv, MeasSrc ms, double* s
     S[1][1] += pv.p.r_meas;
     double Si[2][2];
     inv2(S, Si);
-    const double v0 = m.z0 - m.zh0, v1 = m.z1 - m.zh1;
-    const double t0 = v0 * Si[0][0] + v1 * Si[1][0];
-    const double t1 = v0 * Si[0][1] + v1 * Si[1][1];
+    const double sc = maha_quad(Si, m.z0 - m.zh0, m.z1 - m.zh1);
     if (lane == 0) {
-        scores[(size_t)b * pv.n + i] = t0 * v0 + t1 * v1;
+        scores[(size_t)b * pv.n + i] = sc;
     }
 }
 
@@ -905,10 +898,8 @@ __global__ void k_assoc_begin(PoolView pv, const int* known_count_dev, int known
 }
 
 // ---------------------------------------------------------------------------------------------
-// Decision step of data_association() for one measurement, ekf_slam.cpp:293-330: sequential-scan
-// semantics (first index attaining the strict minimum below gate_new) as a lexicographic (d, i)
-// min-reduction; NaN scores never win (`d < min` is false).  New landmark initialisation
-// (:200-214, :318-327) and the gate_update test (:330) run on one lane.  grid (B), 256 threads.
+// Decision step of data_association() for one measurement, ekf_slam.cpp:293-330 (the rule itself: ekf_assoc.hpp), from
+// the scores k_maha left.  grid (B), 256 threads.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_assoc_decide(PoolView pv, MeasSrc ms, const double* scores,
                                                       int* assoc_out, int out_stride, int j,
@@ -933,42 +924,21 @@ __global__ __launch_bounds__(256) void k_assoc_decide(PoolView pv, MeasSrc ms, c
         const double d = scores[(size_t)b * pv.n + i];
         if (d < best) { best = d; bi = i; }  // :305-309
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double od = __shfl_down(best, off, kWave);
-        const int oi = __shfl_down(bi, off, kWave);
-        if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-    }
-    if ((tid & 63) == 0) { sh_d[tid >> 6] = best; sh_i[tid >> 6] = bi; }
-    __syncthreads();
+    block_argmin(best, bi, sh_d, sh_i, 4);
     if (tid == 0) {
-        for (int w = 1; w < 4; w++)
-            if (sh_d[w] < best || (sh_d[w] == best && sh_i[w] < bi)) { best = sh_d[w]; bi = sh_i[w]; }
-        int idx = (bi == INT_MAX) ? M : bi;  // :294 min_maha_idx = known_count
-        int known_count = M;
+        const AssocDecision dec = assoc_decision(best, bi, M, pv.n, pv.p.gate_update);
         double* st = pv.state + (size_t)b * pv.ld;
-        if (idx == M && idx < pv.n) {  // :318-327 new landmark
-            const double theta = st[0], x = st[1], y = st[2];
-            const double sx = meas[0], sy = meas[1];
-            const double ri = sqrt(sx * sx + sy * sy);
-            const double phii = atan2(sy, sx);
-            st[2 * idx + 3] = x + ri * cos(phii + theta);
-            st[2 * idx + 3 + 1] = y + ri * sin(phii + theta);
-            known_count = M + 1;
-            best = 0.0;
-        }
-        // :330.  idx == n (map full, no match) can only pass the gate with non-reference
-        // parameters (gate_new < gate_update); the reference would index out of bounds there.
-        const int active = (best < pv.p.gate_update) && idx < pv.n;
+        if (dec.is_new)  // :318-327
+            landmark_from_reading(meas[0], meas[1], st[0], st[1], st[2], st[2 * dec.idx + 3], st[2 * dec.idx + 3 + 1]);
         AssocRec a;
-        a.known_count = known_count;
-        a.lm = active ? idx : -1;
-        a.active = active;
+        a.known_count = dec.known_count;
+        a.lm = dec.lm();
+        a.active = dec.active;
         a.pad = 0;
-        a.best = best;
+        a.best = dec.best;
         pv.assoc[b] = a;
         if (assoc_out) assoc_out[(size_t)b * out_stride + j] = a.lm;
-        if (corr_counter && active) atomicAdd(corr_counter, 1ull);
+        if (corr_counter && dec.active) atomicAdd(corr_counter, 1ull);
     }
 }
 

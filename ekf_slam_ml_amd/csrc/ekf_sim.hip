@@ -8,7 +8,7 @@
 // Every random number is a pure function of (seed, global filter id, step, kind, k) through
 // splitmix64 + Box-Muller, the same addressing as the host generator ekf_slam_ml_amd/synth.py: integer
 // parts are bit-identical, transcendental parts (log/cos/sqrt) agree to rounding.
-#include "ekf_kernels.hpp"
+#include "ekf_assoc.hpp"
 #include "ekf_sim.hpp"
 
 namespace ekf {
@@ -89,6 +89,38 @@ __global__ void k_sim_trajectory(SimParams p, int B, int T, double* __restrict__
     }
 }
 
+// The kmax nearest landmarks within the visibility radius of pose (c, s, px, py), by repeated lexicographic
+// (d2, index) minimum over the workgroup (block_argmin of ekf_assoc.hpp): chosen[0..n_chosen) in ascending distance.
+// 256 threads.
+__device__ __forceinline__ void select_nearest(int n, int kmax, double lim2, const double* __restrict__ world, double c,
+                                               double s, double px, double py, int* chosen, int* n_chosen, int* exhausted,
+                                               double* sh_d, int* sh_i) {
+    const int tid = threadIdx.x;
+    if (tid == 0) { *n_chosen = 0; *exhausted = 0; }
+    __syncthreads();
+    for (int pass = 0; pass < kmax; pass++) {
+        double best = 1.0e300;
+        int bi = 0x7fffffff;
+        const int nch = *n_chosen;
+        for (int i = tid; i < n; i += 256) {
+            bool taken = false;
+            for (int q = 0; q < nch; q++) taken |= (chosen[q] == i);
+            if (taken) continue;
+            const double dx = world[2 * i] - px, dy = world[2 * i + 1] - py;
+            const double rx = c * dx + s * dy, ry = -s * dx + c * dy;
+            const double d2 = rx * rx + ry * ry;
+            if (score_less(d2, i, best, bi)) { best = d2; bi = i; }
+        }
+        block_argmin(best, bi, sh_d, sh_i, 4);
+        if (tid == 0) {
+            if (bi != 0x7fffffff && best <= lim2) chosen[(*n_chosen)++] = bi;
+            else *exhausted = 1;  // nothing left within the radius
+        }
+        __syncthreads();
+        if (*exhausted) break;  // uniform
+    }
+}
+
 // One workgroup per (filter, step): readings of the vmax nearest landmarks within the visibility radius,
 // in ascending landmark order (publishFakeSensor, tube_world.cpp:369-414).  Step 0 instead fills init_xy
 // with ALL n readings and leaves the slots empty (state_update_flag is still false, slam.cpp:315-327).
@@ -118,39 +150,8 @@ __global__ __launch_bounds__(256) void k_sim_readings(SimParams p, int B, int n,
     __shared__ int chosen[64];
     __shared__ int n_chosen;
     __shared__ int exhausted;
-    const int kmax = vmax < 64 ? vmax : 64;
-    if (tid == 0) { n_chosen = 0; exhausted = 0; }
-    __syncthreads();
-    const double lim2 = p.max_visible_dis * p.max_visible_dis;
-    for (int pass = 0; pass < kmax; pass++) {
-        // nearest not-yet-chosen landmark (lexicographic (d2, i) minimum)
-        double best = 1.0e300;
-        int bi = 0x7fffffff;
-        for (int i = tid; i < n; i += 256) {
-            bool taken = false;
-            for (int q = 0; q < n_chosen; q++) taken |= (chosen[q] == i);
-            if (taken) continue;
-            const double dx = world[2 * i] - px, dy = world[2 * i + 1] - py;
-            const double rx = c * dx + s * dy, ry = -s * dx + c * dy;
-            const double d2 = rx * rx + ry * ry;
-            if (d2 < best || (d2 == best && i < bi)) { best = d2; bi = i; }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_down(best, off, kWave);
-            const int oi = __shfl_down(bi, off, kWave);
-            if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-        }
-        if ((tid & 63) == 0) { sh_d[tid >> 6] = best; sh_i[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; w++)
-                if (sh_d[w] < best || (sh_d[w] == best && sh_i[w] < bi)) { best = sh_d[w]; bi = sh_i[w]; }
-            if (bi != 0x7fffffff && best <= lim2) chosen[n_chosen++] = bi;
-            else exhausted = 1;  // nothing left within the radius
-        }
-        __syncthreads();
-        if (exhausted) break;  // uniform
-    }
+    select_nearest(n, vmax < 64 ? vmax : 64, p.max_visible_dis * p.max_visible_dis, world, c, s, px, py, chosen, &n_chosen,
+                   &exhausted, sh_d, sh_i);
     if (tid == 0) {
         const int m = n_chosen;
         for (int a = 1; a < m; a++) {  // ascending landmark index = loop order of ekf_slam.cpp:132
@@ -171,45 +172,6 @@ __global__ __launch_bounds__(256) void k_sim_readings(SimParams p, int B, int n,
                 slots[v] = -1; zz[2 * v] = 0.0; zz[2 * v + 1] = 0.0;
             }
         }
-    }
-}
-
-// The kmax nearest landmarks within the visibility radius of pose (c, s, px, py), by repeated lexicographic
-// (d2, index) minimum over the workgroup: chosen[0..n_chosen) in ascending distance.  256 threads.
-__device__ void select_nearest(int n, int kmax, double lim2, const double* __restrict__ world, double c, double s,
-                               double px, double py, int* chosen, int* n_chosen, int* exhausted, double* sh_d,
-                               int* sh_i) {
-    const int tid = threadIdx.x;
-    if (tid == 0) { *n_chosen = 0; *exhausted = 0; }
-    __syncthreads();
-    for (int pass = 0; pass < kmax; pass++) {
-        double best = 1.0e300;
-        int bi = 0x7fffffff;
-        const int nch = *n_chosen;
-        for (int i = tid; i < n; i += 256) {
-            bool taken = false;
-            for (int q = 0; q < nch; q++) taken |= (chosen[q] == i);
-            if (taken) continue;
-            const double dx = world[2 * i] - px, dy = world[2 * i + 1] - py;
-            const double rx = c * dx + s * dy, ry = -s * dx + c * dy;
-            const double d2 = rx * rx + ry * ry;
-            if (d2 < best || (d2 == best && i < bi)) { best = d2; bi = i; }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_down(best, off, kWave);
-            const int oi = __shfl_down(bi, off, kWave);
-            if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-        }
-        if ((tid & 63) == 0) { sh_d[tid >> 6] = best; sh_i[tid >> 6] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; w++)
-                if (sh_d[w] < best || (sh_d[w] == best && sh_i[w] < bi)) { best = sh_d[w]; bi = sh_i[w]; }
-            if (bi != 0x7fffffff && best <= lim2) chosen[(*n_chosen)++] = bi;
-            else *exhausted = 1;  // nothing left within the radius
-        }
-        __syncthreads();
-        if (*exhausted) break;  // uniform
     }
 }
 

@@ -12,9 +12,7 @@
 // one launch per API call instead of 2V + 1.  The arithmetic (gather order, summation order, update
 // expression) is that of k_gain / k_rank2, so the result is bit-identical to the multi-kernel path.
 // LDS rows use an odd stride so that the column gather Sigma(r, c5) is bank-conflict-free.
-#include "ekf_kernels.hpp"
-
-#include <climits>
+#include "ekf_assoc.hpp"
 
 namespace ekf {
 
@@ -118,11 +116,7 @@ __device__ __forceinline__ void small_measure_body(const PoolView& pv, int b, co
     if (do_init) {                                     // :113-128, all n landmarks regardless of visibility
         __syncthreads();                               // everybody holds the pose before the map is rewritten
         for (int i = tid; i < n; i += THREADS) {
-            const double sx = sens[2 * i], sy = sens[2 * i + 1];
-            const double ri = sqrt(sx * sx + sy * sy);
-            const double phii = atan2(sy, sx);
-            st[2 * i + 3] = x + ri * cos(phii + theta);
-            st[2 * i + 3 + 1] = y + ri * sin(phii + theta);
+            landmark_from_reading(sens[2 * i], sens[2 * i + 1], theta, x, y, st[2 * i + 3], st[2 * i + 3 + 1]);
         }
         __syncthreads();
     }
@@ -209,8 +203,8 @@ __global__ __launch_bounds__(THREADS) void k_small_measure_inline(PoolView pv, S
 // ---------------------------------------------------------------------------------------------
 // data_association() of a small map in ONE launch (ekf_slam.cpp:278-402): for every measurement, in order,
 // the Mahalanobis scores of the known landmarks (one landmark per LANE here -- everything a score needs is in
-// LDS, and innovation_cov() sums in the order of k_maha's shuffle folds), the sequential-scan decision with its two gates and the
-// new-landmark initialisation (k_assoc_decide), and the correction with the fresh pose (k_gain + k_rank2).
+// LDS), the decision (score and rule: ekf_assoc.hpp; wave 0 alone reduces), and the correction with the fresh pose
+// (k_gain + k_rank2).
 // Same arithmetic as the multi-kernel chain -> bit-identical results and decisions.
 // ---------------------------------------------------------------------------------------------
 // N: the filter's active dimension (the leading N x N block of Sigma is all these J measurements can touch);
@@ -252,47 +246,24 @@ __device__ int small_associate_body(const PoolView& pv, int b, int N, const doub
         if (tid < M) {
             const int i = tid;
             measurement_terms(st[2 * i + 3], st[2 * i + 4], mx, my, st[0], st[1], st[2], m);  // fresh pose, :219-221
-            double S55[5][5], Sm[2][2];
+            double S55[5][5];
 #pragma unroll
             for (int k = 0; k < 5; k++)
 #pragma unroll
                 for (int l = 0; l < 5; l++) S55[k][l] = S[idx5(k, i) * ldS + idx5(l, i)];
-            innovation_cov(S55, m.H, pv.p.r_meas, Sm);   // same summation order as k_maha's shuffle folds
-            inv2(Sm, Si);
-            v0 = m.z0 - m.zh0; v1 = m.z1 - m.zh1;        // bearing NOT wrapped, :269
-            const double t0 = v0 * Si[0][0] + v1 * Si[1][0];
-            const double t1 = v0 * Si[0][1] + v1 * Si[1][1];
-            const double sc = t0 * v0 + t1 * v1;
+            const double sc = maha_score(S55, m, pv.p.r_meas, Si, v0, v1);
             if (sc < d) { d = sc; di = i; }              // :305-309 (NaN never wins)
         }
-        if (tid < kWave) {  // sequential-scan semantics = lexicographic (d, i) minimum, as in k_assoc_decide
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const double od = __shfl_down(d, off, kWave);
-                const int oi = __shfl_down(di, off, kWave);
-                if (od < d || (od == d && oi < di)) { d = od; di = oi; }
-            }
-        }
-        if (tid == 0) {                                  // :293-330
-            double best = d;
-            const int idx = (di == INT_MAX) ? M : di;
-            int Mn = M, is_new = 0;
-            if (idx == M && idx < n) {                   // :318-327 new landmark
-                const double theta = st[0], x = st[1], y = st[2];
-                const double ri = sqrt(mx * mx + my * my);
-                const double phii = atan2(my, mx);
-                st[2 * idx + 3] = x + ri * cos(phii + theta);
-                st[2 * idx + 3 + 1] = y + ri * sin(phii + theta);
-                Mn = M + 1;
-                best = 0.0;
-                is_new = 1;
-            }
-            const int active = (best < pv.p.gate_update) && idx < n;
-            sh_M = Mn;
-            sh_lm = active ? idx : -1;
-            sh_new = is_new;
+        if (tid < kWave) wave_argmin(d, di);             // wave 0 holds every score
+        if (tid == 0) {                                  // :293-330 (ekf_assoc.hpp)
+            const AssocDecision dec = assoc_decision(d, di, M, n, pv.p.gate_update);
+            if (dec.is_new)                              // :318-327
+                landmark_from_reading(mx, my, st[0], st[1], st[2], st[2 * dec.idx + 3], st[2 * dec.idx + 3 + 1]);
+            sh_M = dec.known_count;
+            sh_lm = dec.lm();
+            sh_new = dec.is_new;
             assoc_out[j] = sh_lm;
-            if (active) { sh_applied++; sh_touch[idx] = 1; }
+            if (dec.active) { sh_applied++; sh_touch[dec.idx] = 1; }
         }
         __syncthreads();
         const int lm = sh_lm;
@@ -476,11 +447,7 @@ __global__ __launch_bounds__(THREADS) void k_pool_run_known(PoolView pv, const d
             __syncthreads();
             const double* sens = init_xy + (size_t)b * 2 * n;
             for (int i = tid; i < n; i += THREADS) {
-                const double sx = sens[2 * i], sy = sens[2 * i + 1];
-                const double ri = sqrt(sx * sx + sy * sy);
-                const double phii = atan2(sy, sx);
-                st[2 * i + 3] = x + ri * cos(phii + theta);
-                st[2 * i + 3 + 1] = y + ri * sin(phii + theta);
+                landmark_from_reading(sens[2 * i], sens[2 * i + 1], theta, x, y, st[2 * i + 3], st[2 * i + 3 + 1]);
             }
             do_init = 0;
             __syncthreads();

@@ -11,15 +11,13 @@
 //                 minus the pending pairs of this step, applied in order with the rank-2 kernel's own expression --
 //                 the values the per-reading path would have read; the fresh pose and landmark come from the state,
 //                 which IS updated after every reading (:219-221, :331-333)
-//     decision    lexicographic (d, i) minimum, the two gates, landmark initialisation (:293-330)
+//     decision    :293-330, the rule of ekf_assoc.hpp
 //     gain        K = Sigma H^T S^-1 and G = H Sigma over the filter's prefix from the same reconstruction of the five
 //                 rows / columns; appended as pair `pc`; state += K nu (:376-385)
 //   then ONE pass over the prefix applies the pairs to every element in order: x <- (x - K_0 G_0) - K_1 G_1 ...
 // Everything is the arithmetic of k_maha / k_assoc_decide / k_gain / k_rank2 in the same order -> decisions, state and
 // covariance are bit-identical to the four-launch path (tests/test_gpu_batch_unknown.py).
-#include "ekf_kernels.hpp"
-
-#include <climits>
+#include "ekf_assoc.hpp"
 
 namespace ekf {
 
@@ -173,16 +171,13 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
                 // the entries as they stand NOW: minus the pending pairs, in order (k_rank2's expression).  The pairs' values at
                 // the landmark's two indices come from memory: two pairs are requested together (in delayed mode up to 64
                 // pairs are pending, and one round trip per pair was most of the step)
-                auto fold_pair = [&](int v, const double (&ku)[2][2], const double (&gu)[2][2]) {
+                auto fold_pending = [&](int v, const double (&ku)[2][2], const double (&gu)[2][2]) {
                     double kr[5][2], gc[5][2];
     #pragma unroll
                     for (int k = 0; k < 3; k++) { kr[k][0] = sh_K5[v][k][0]; kr[k][1] = sh_K5[v][k][1]; gc[k][0] = sh_G5[v][k][0]; gc[k][1] = sh_G5[v][k][1]; }
     #pragma unroll
                     for (int q = 0; q < 2; q++) { kr[3 + q][0] = ku[q][0]; kr[3 + q][1] = ku[q][1]; gc[3 + q][0] = gu[q][0]; gc[3 + q][1] = gu[q][1]; }
-    #pragma unroll
-                    for (int k = 0; k < 5; k++)
-    #pragma unroll
-                        for (int l = 0; l < 5; l++) S55[k][l] = S55[k][l] - (kr[k][0] * gc[l][0] + kr[k][1] * gc[l][1]);
+                    fold_pair(S55, kr, gc);
                 };
                 auto load_pair = [&](int v, double (&ku)[2][2], double (&gu)[2][2]) {
     #pragma unroll
@@ -197,20 +192,20 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
     #pragma unroll
                     for (int w = 0; w < 2; w++) load_pair(v + w, ku[w], gu[w]);
     #pragma unroll
-                    for (int w = 0; w < 2; w++) fold_pair(v + w, ku[w], gu[w]);
+                    for (int w = 0; w < 2; w++) fold_pending(v + w, ku[w], gu[w]);
                 }
                 for (; v < pc; v++) {
                     double ku[2][2], gu[2][2];
                     load_pair(v, ku, gu);
-                    fold_pair(v, ku, gu);
+                    fold_pending(v, ku, gu);
                 }
             }
+            // (maha_score's three steps one by one: with S inside a helper this kernel, which lives at the edge of its
+            // register budget, spills 32 to 56 bytes per lane more)
             innovation_cov(S55, m.H, pv.p.r_meas, S);   // sums in the order of k_maha's shuffle folds
             inv2(S, Si);
             const double v0 = m.z0 - m.zh0, v1 = m.z1 - m.zh1;   // bearing NOT wrapped, :269
-            const double t0 = v0 * Si[0][0] + v1 * Si[1][0];
-            const double t1 = v0 * Si[0][1] + v1 * Si[1][1];
-            const double sc = t0 * v0 + t1 * v1;
+            const double sc = maha_quad(Si, v0, v1);
             if (sc < best) {   // :305-309 (ascending i within the thread: the first minimum is kept; NaN never wins)
                 best = sc; bi = i;
 #pragma unroll
@@ -219,34 +214,15 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
                 bnu[0] = v0; bnu[1] = v1;
             }
         }
-        // lexicographic (d, i) minimum = the sequential scan's first strict minimum
         double rd = best;
         int ri = bi;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double od = __shfl_down(rd, off, kWave);
-            const int oi = __shfl_down(ri, off, kWave);
-            if (od < rd || (od == rd && oi < ri)) { rd = od; ri = oi; }
-        }
-        if ((tid & 63) == 0) { sh_d[tid >> 6] = rd; sh_i[tid >> 6] = ri; }
-        __syncthreads();
-        if (tid == 0) {   // :293-330 (k_assoc_decide)
-            for (int w = 1; w < kStepThreads / 64; w++)
-                if (sh_d[w] < rd || (sh_d[w] == rd && sh_i[w] < ri)) { rd = sh_d[w]; ri = sh_i[w]; }
-            const int idx = (ri == INT_MAX) ? M : ri;   // :294 min_maha_idx = known_count
-            int Mn = M, is_new = 0;
-            if (idx == M && idx < n) {                  // :318-327 new landmark
-                const double rr = sqrt(mx * mx + my * my);
-                const double phi = atan2(my, mx);
-                st[2 * idx + 3] = x + rr * cos(phi + theta);
-                st[2 * idx + 3 + 1] = y + rr * sin(phi + theta);
-                Mn = M + 1;
-                rd = 0.0;
-                is_new = 1;
-            }
-            const int active = (rd < pv.p.gate_update) && idx < n;   // :330
-            sh_M = Mn;
-            sh_lm = active ? idx : -1;
+        block_argmin(rd, ri, sh_d, sh_i, kStepThreads / 64);
+        if (tid == 0) {   // :293-330 (ekf_assoc.hpp)
+            const AssocDecision dec = assoc_decision(rd, ri, M, n, pv.p.gate_update);
+            const int idx = dec.idx, active = dec.active, is_new = dec.is_new;
+            if (is_new) landmark_from_reading(mx, my, theta, x, y, st[2 * idx + 3], st[2 * idx + 3 + 1]);   // :318-327
+            sh_M = dec.known_count;
+            sh_lm = dec.lm();
             sh_new = is_new;
             out[j] = sh_lm;
             if (active) sh_applied++;
