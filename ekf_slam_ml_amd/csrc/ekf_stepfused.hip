@@ -88,7 +88,8 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
     // pair), kept current by folding each new pair in.  A score then reads 25 consecutive-in-i values instead of 25 scattered
     // entries of Sigma plus 8 values per pending pair (up to 64 pairs are pending).  (Re)built from Sigma when nothing is
     // pending; carried across steps, where this step's prediction() is applied to it first (the 5 x 5 block is closed under At . At^T + Q: rows /
-    // columns 0, 1, 2 are inside it; k_predict's arithmetic).  Landmark i is always handled by thread i mod 512.
+    // columns 0, 1, 2 are inside it; k_predict's arithmetic).  Which thread handles landmark i differs between the phases (the pose-only
+    // fold behind a new pair starts at the active dimension): the barriers around every phase order them, nothing else does.
     double* blk = DELAYED ? blocks_all + (size_t)b * 25 * n : nullptr;
     if (!DELAYED) {
     } else if (p0 == 0) {
@@ -358,8 +359,21 @@ __global__ __launch_bounds__(kStepThreads) void k_pool_step_unknown(PoolView pv,
         }
         __threadfence_block();
         __syncthreads();
-        if constexpr (DELAYED) {   // the cached blocks take the new pair (k_rank2's expression); beyond the active dimension K = G = 0
+        if constexpr (DELAYED) {   // the cached blocks take the new pair (k_rank2's expression)
+            // Beyond the active dimension K = G = 0 at the landmark's own two indices, but the POSE part of its block is the
+            // pose block of Sigma, which every pair changes: a landmark discovered later, while pairs are still pending, is
+            // initialised and scored from this block (:318-327, :331-381), so its nine pose entries take the pair too.
             const int nfold = min(n, (Nb - 3) >> 1);
+            for (int i = nfold + tid; i < n; i += kStepThreads) {
+#pragma unroll
+                for (int e = 0; e < 15; e++) {
+                    const int k = e / 5, l = e % 5;
+                    if (l < 3) {
+                        const double xv = blk[(size_t)e * n + i];
+                        blk[(size_t)e * n + i] = xv - (sh_K5[pc][k][0] * sh_G5[pc][l][0] + sh_K5[pc][k][1] * sh_G5[pc][l][1]);
+                    }
+                }
+            }
             for (int i = tid; i < nfold; i += kStepThreads) {
                 const int ia = 3 + 2 * i;
                 double kr[5][2], gc[5][2];

@@ -62,12 +62,16 @@ def _all_visible_meas(n, pose, world, rng, vis=None):
     return ("M", rf.reshape(-1), np.ones(n, dtype=np.uint8) if vis is None else np.asarray(vis, dtype=np.uint8))
 
 
-def _dead_reckon(pose, dth, dx):
+def dead_reckon(pose, dth, dx):
+    """the true pose after a twist: prediction()'s own two branches (ekf_slam.cpp:79-94) on a 3-vector (theta, x, y)"""
     if abs(dth) < 1e-6:
         return np.array([pose[0], pose[1] + dx * math.cos(pose[0]), pose[2] + dx * math.sin(pose[0])])
     r = dx / dth
     return np.array([pose[0] + dth, pose[1] - r * math.sin(pose[0]) + r * math.sin(pose[0] + dth),
                      pose[2] + r * math.cos(pose[0]) - r * math.cos(pose[0] + dth)])
+
+
+_dead_reckon = dead_reckon   # (the name the older tests use)
 
 
 def straight_threshold():
