@@ -61,6 +61,7 @@ SYMBOLS = [
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
+    "ekf_dense64_solve_launch_info", "ekf_dense64_solve", "ekf_dense64_color",
     "ekf_dense64_frame_launch_info", "ekf_dense64_map_congruence", "ekf_dense64_reframe_landmarks",
     "ekf_dense64_join_launch_info", "ekf_dense64_join_congruence", "ekf_dense64_join_map",
     "ekf_dense64_extract_launch_info", "ekf_dense64_extract_map",
@@ -287,6 +288,9 @@ def load():
         "ekf_dense64_factor": [h, C.POINTER(FactorReport), _dp],
         "ekf_dense64_get_factor": [h, _dp],
         "ekf_dense64_whiten": [h, C.c_int, _dp, _dp, _dp, _dp],
+        "ekf_dense64_solve_launch_info": [h, _ip, _ip, _ip],
+        "ekf_dense64_solve": [h, C.c_int, _dp, _dp, _dp, _dp, _dp],
+        "ekf_dense64_color": [h, C.c_int, _dp, C.c_int, _dp, _dp],
         "ekf_dense64_frame_launch_info": [h, _ip, _ip, _ip],
         "ekf_dense64_map_congruence": [h, _dp, _dp, _dp],
         "ekf_dense64_reframe_landmarks": [h, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp],
@@ -1281,16 +1285,51 @@ class DensePropagator64(_DensePropagatorBase):
         """Y[r] = L^-1 B[r] by forward substitution against the last factor() and d2[r] = |Y[r]|^2 for the rows of B
         (nrhs x live, or one vector), up to WHITEN_MAX_RHS at once; with B = state - truth d2 is the NEES of the whole map.
         Does not read Sigma and does not flush the pending rows.  Returns {Y (None unless want_Y), d2, ms}."""
+        B = self._rhs(B, "B")
+        Y = np.empty_like(B) if want_Y else None
+        d2, ms = np.empty(B.shape[0]), C.c_double()
+        _check(self._lib.ekf_dense64_whiten(self._h, B.shape[0], _d(B), _d(Y) if want_Y else None, _d(d2), C.byref(ms)))
+        return {"Y": Y, "d2": d2, "ms": ms.value}
+
+    def _rhs(self, B, name):
+        """the argument checks of whiten(), solve() and color(): nrhs x live (or one vector), C-contiguous float64"""
         self._open()
         B = np.ascontiguousarray(B, dtype=np.float64)
         if B.ndim == 1:
             B = B[None, :]
         if B.ndim != 2 or not 1 <= B.shape[0] <= self.WHITEN_MAX_RHS or B.shape[1] != self.live:
-            raise ValueError(f"B must be nrhs x live with 1 <= nrhs <= {self.WHITEN_MAX_RHS}")
+            raise ValueError(f"{name} must be nrhs x live with 1 <= nrhs <= {self.WHITEN_MAX_RHS}")
+        return B
+
+    def solve(self, B, want_Y=False):
+        """X[r] = Sigma^-1 B[r] = L^-T (L^-1 B[r]) against the last factor(), for the rows of B (nrhs x live, or one
+        vector), up to WHITEN_MAX_RHS at once: whiten()'s forward substitution as it stands (Y and d2 are whiten()'s bit
+        for bit), then the backward substitution, descending, divisions by L[i][i].  Does not read Sigma and does not flush
+        the pending rows.  Returns {X, Y (None unless want_Y), d2, ms}."""
+        B = self._rhs(B, "B")
+        X = np.empty_like(B)
         Y = np.empty_like(B) if want_Y else None
         d2, ms = np.empty(B.shape[0]), C.c_double()
-        _check(self._lib.ekf_dense64_whiten(self._h, B.shape[0], _d(B), _d(Y) if want_Y else None, _d(d2), C.byref(ms)))
-        return {"Y": Y, "d2": d2, "ms": ms.value}
+        _check(self._lib.ekf_dense64_solve(self._h, B.shape[0], _d(B), _d(X), _d(Y) if want_Y else None, _d(d2), C.byref(ms)))
+        return {"X": X, "Y": Y, "d2": d2, "ms": ms.value}
+
+    def color(self, Z, add_state=False):
+        """X[r] = L Z[r] against the last factor(), for the rows of Z (nrhs x live, or one vector), up to WHITEN_MAX_RHS at
+        once; with add_state X[r] = fl(L Z[r] + state[:live]), the CURRENT state: rows of unit normal draws become maps
+        drawn from N(state, Sigma of the last factor()).  The heading of a sample is not wrapped.  Does not read Sigma and
+        does not flush the pending rows.  Returns {X, ms}."""
+        Z = self._rhs(Z, "Z")
+        X, ms = np.empty_like(Z), C.c_double()
+        _check(self._lib.ekf_dense64_color(self._h, Z.shape[0], _d(Z), 1 if add_state else 0, _d(X), C.byref(ms)))
+        return {"X": X, "ms": ms.value}
+
+    def solve_launch_info(self):
+        """{block, threads_back, threads_color}: the block side of solve() and color() in states and the workgroup sizes of
+        the backward step and of the colouring kernel (test hook)"""
+        self._open()
+        block, tb, tc = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_solve_launch_info(self._h, C.byref(block), C.byref(tb), C.byref(tc)))
+        return {"block": block.value, "threads_back": tb.value, "threads_color": tc.value}
 
     def factor_launch_info(self):
         """{block, threads}: the block side of factor() in states and the workgroup size (test hook)"""
@@ -2153,6 +2192,38 @@ class DenseEKFSLAM:
         e = d.state_block(0, live) - truth
         e[0] = normalize_angles(e[:1])[0]
         return float(d.whiten(e, want_Y=False)["d2"][0])
+
+    def map_solve(self, e=None, truth=None):
+        """Sigma^-1 e over the live dimension against the last factor(): half the gradient of map_nees with respect to the
+        state.  Give the error vector e itself, or truth (the live states) for e = state - truth with the heading
+        difference wrapped as map_nees wraps it."""
+        d = self.handle
+        live = d.live
+        if (e is None) == (truth is None):
+            raise ValueError("give e or truth")
+        v = np.ascontiguousarray(truth if e is None else e, dtype=np.float64).reshape(-1)
+        if v.shape != (live,):
+            raise ValueError("e / truth must hold the live states")
+        if e is None:
+            v = d.state_block(0, live) - v
+            v[0] = normalize_angles(v[:1])[0]
+        return d.solve(v)["X"][0]
+
+    def sample_maps(self, k, rng=None, Z=None):
+        """k <= 64 maps drawn from N(state, Sigma of the last factor()), k x live: state + L z for rows z of unit normal
+        draws -- Z (k x live) if given, rng.standard_normal((k, live)) otherwise (rng: a numpy Generator, default_rng() if
+        None).  The state is the current one and the factor a snapshot: call factor() after the last correction.  The
+        heading of a sample is not wrapped."""
+        d = self.handle
+        live = d.live
+        if not 1 <= k <= d.WHITEN_MAX_RHS:
+            raise ValueError(f"1 <= k <= {d.WHITEN_MAX_RHS}")
+        if Z is None:
+            Z = (np.random.default_rng() if rng is None else rng).standard_normal((k, live))
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        if Z.shape != (k, live):
+            raise ValueError("Z must be k x live")
+        return d.color(Z, add_state=True)["X"]
 
     @property
     def state(self):

@@ -1084,6 +1084,67 @@ ekf_status ekf_dense64_whiten(ekf_dense64_handle d, int nrhs, const double* B, d
     return EKF_OK;
 }
 
+ekf_status ekf_dense64_solve_launch_info(ekf_dense64_handle d, int* block, int* threads_back, int* threads_color) {
+    if (!d || !block || !threads_back || !threads_color) return fail(EKF_ERR_INVALID, "ekf_dense64_solve_launch_info: null argument");
+    *block = ekf::kDense64FactorNB;
+    *threads_back = *threads_color = ekf::kDense64FactorThreads;
+    return EKF_OK;
+}
+
+// ekf_dense64_whiten as it stands on the first two panels, then Y into a third one and the descending walk; X lands where
+// the working copy of B was.
+ekf_status ekf_dense64_solve(ekf_dense64_handle d, int nrhs, const double* B, double* X_out, double* Y_out, double* d2_out,
+                             double* elapsed_ms) {
+    const char* fn = "ekf_dense64_solve";
+    constexpr int kMaxRhs = ekf::kDense64WhitenMaxRhs;
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!B) return fail(EKF_ERR_INVALID, std::string(fn) + ": null B");
+    if (nrhs < 1 || nrhs > kMaxRhs) return fail(EKF_ERR_INVALID, std::string(fn) + ": 1 <= nrhs <= EKF_DENSE64_WHITEN_MAX_RHS");
+    if (!X_out && !Y_out && !d2_out) return fail(EKF_ERR_INVALID, std::string(fn) + ": X_out, Y_out and d2_out are all NULL");
+    EKFC(factor_usable(d, fn, true));
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->factor_na);
+    const size_t Na = pl.Na, count = kMaxRhs * (size_t)pl.rows, panel = sizeof(double) * count, pitch = sizeof(double) * pl.rows;
+    EKFC(d->whiten.reserve(d->mem, 3 * panel + sizeof(double) * kMaxRhs, false, fn, "the right-hand sides"));
+    double* rhs = d->whiten.as<double>();   // B, then X | Y | the working copy of Y | d2
+    double* d2 = rhs + 3 * count;
+    HIPC(hipMemsetAsync(rhs, 0, panel, d->stream));
+    HIPC(hipMemcpy2DAsync(rhs, pitch, B, sizeof(double) * Na, sizeof(double) * Na, nrhs, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_whiten(pl, d->factor.as<double>(), rhs, d2, d->stream);
+    if (X_out) {
+        HIPC(hipMemcpyAsync(rhs + 2 * count, rhs + count, panel, hipMemcpyDeviceToDevice, d->stream));
+        ekf::launch_dense64_back(pl, d->factor.as<double>(), rhs + 2 * count, rhs, d->stream);
+    }
+    EKFC(finish_timed(d, elapsed_ms, {{d2_out, d2, sizeof(double) * nrhs}}));
+    if (Y_out) HIPC(hipMemcpy2D(Y_out, sizeof(double) * Na, rhs + count, pitch, sizeof(double) * Na, nrhs, hipMemcpyDeviceToHost));
+    if (X_out) HIPC(hipMemcpy2D(X_out, sizeof(double) * Na, rhs, pitch, sizeof(double) * Na, nrhs, hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
+// Z goes up into a zeroed panel of the snapshot's row stride, one launch, X comes back.
+ekf_status ekf_dense64_color(ekf_dense64_handle d, int nrhs, const double* Z, int add_state, double* X_out, double* elapsed_ms) {
+    const char* fn = "ekf_dense64_color";
+    constexpr int kMaxRhs = ekf::kDense64WhitenMaxRhs;
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fn) + ": null handle");
+    if (!Z) return fail(EKF_ERR_INVALID, std::string(fn) + ": null Z");
+    if (nrhs < 1 || nrhs > kMaxRhs) return fail(EKF_ERR_INVALID, std::string(fn) + ": 1 <= nrhs <= EKF_DENSE64_WHITEN_MAX_RHS");
+    if (!X_out) return fail(EKF_ERR_INVALID, std::string(fn) + ": null X_out");
+    EKFC(factor_usable(d, fn, true));
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64FactorPlan pl = ekf::dense64_factor_plan(d->factor_na);
+    const size_t Na = pl.Na, count = kMaxRhs * (size_t)pl.ldf, panel = sizeof(double) * count, pitch = sizeof(double) * pl.ldf;
+    EKFC(d->whiten.reserve(d->mem, 2 * panel, false, fn, "the draws"));
+    double* zin = d->whiten.as<double>();   // Z | X
+    HIPC(hipMemsetAsync(zin, 0, panel, d->stream));
+    HIPC(hipMemcpy2DAsync(zin, pitch, Z, sizeof(double) * Na, sizeof(double) * Na, nrhs, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_color(pl, d->factor.as<double>(), zin, add_state ? d->x : nullptr, zin + count, d->stream);
+    EKFC(finish_timed(d, elapsed_ms));
+    HIPC(hipMemcpy2D(X_out, sizeof(double) * Na, zin + count, pitch, sizeof(double) * Na, nrhs, hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
 // ---- the map in another frame (ekf_dense64_frame.hip) ---------------------------------------------------------------------
 ekf_status ekf_dense64_frame_launch_info(ekf_dense64_handle d, int* tile_rows, int* tile_cols, int* threads) {
     if (!d || !tile_rows || !tile_cols || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_frame_launch_info: null argument");

@@ -349,6 +349,16 @@ void launch_dense64_factor(const Dense64FactorPlan& p, const double* Sigma, int 
 // solves the diagonal block for all right-hand sides, the first one stores it into Y, the others take it out of their NB
 // rows of the working copy), then d2 [kDense64WhitenMaxRhs] = the squared norms, a fixed fold.
 void launch_dense64_whiten(const Dense64FactorPlan& p, const double* factor, double* rhs, double* d2, hipStream_t st);
+// X = L^-T Y: work and X are [kDense64WhitenMaxRhs][p.rows], the working copy = Y as launch_dense64_whiten leaves it (a copy:
+// it is consumed).  One launch per block column, descending (every workgroup solves the transposed diagonal block for all
+// right-hand sides, the first one stores it into X, the others take it out of the NB entries of the working copy that
+// belong to their block column).  Every entry of X is written, 0.0 from Na on.
+void launch_dense64_back(const Dense64FactorPlan& p, const double* factor, double* work, double* X, hipStream_t st);
+// X = Z L^T (+ state): Z and X are [kDense64WhitenMaxRhs][p.ldf] -- the snapshot's row stride, so that the three operands of
+// the shared GEMM tile have one -- Z zero beyond Na and in the rows not in use; state (nullable) holds at least Na entries.
+// One launch, a workgroup per NB states; columns [0, p.rows) of every row of X are written.
+void launch_dense64_color(const Dense64FactorPlan& p, const double* factor, const double* Z, const double* state, double* X,
+                          hipStream_t st);
 
 // ---- the map in another frame (ekf_dense64_frame.hip; the definition is include/ekfslam.h's, ekf_dense64_map_congruence):
 // Sigma <- J Sigma J^T on the live corner for J = blockdiag(1, G, ..., G) + [C | 0], in place, one pass over tiles of

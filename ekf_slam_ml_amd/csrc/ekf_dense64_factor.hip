@@ -1,5 +1,6 @@
-// ekf_dense64_factor.hip -- the Cholesky factor of the dense fp64 handle's live corner, Sigma[0:Na, 0:Na] = L L^T, and the
-// forward substitution Y = L^-1 B against it (gfx950, wave64).  The definitions are include/ekfslam.h's.  A blocked
+// ekf_dense64_factor.hip -- the Cholesky factor of the dense fp64 handle's live corner, Sigma[0:Na, 0:Na] = L L^T, and what
+// is done against it: the forward substitution Y = L^-1 B, the backward substitution X = L^-T Y and the colouring product
+// X = Z L^T (+ state) (gfx950, wave64).  The definitions are include/ekfslam.h's.  A blocked
 // right-looking factorisation with block side NB = kDense64FactorNB = 64 in a snapshot buffer of the handle's own, so Sigma
 // is only read.  The snapshot is `rows` x ldf, rows = Na rounded up to NB, ldf = rows + NB, zero wherever the corner is
 // not: no tile of it is ragged, and the only masked accesses are those of Sigma itself (k_df_copy).
@@ -23,6 +24,16 @@
 //                diagonal block (the substitution of k_df_panel); workgroup 0 stores Y's NB entries, workgroup g > 0 takes
 //                L[rows of tile g, block] y out of its NB entries of the working copy, each wave a quarter of the rows.
 //   k_dw_norm    d2[r] = sum_i Y[r][i]^2: strided partial sums and a binary fold in LDS.
+//   k_ds_back    X = L^-T Y, the mirror of k_dw_step, one launch per block column, descending: a thread per right-hand side
+//                solves L_bb^T x = y (descending, divisions by L[i][i]; columns >= Na are not divided); workgroup 0 stores
+//                X's NB entries, workgroup g > 0 takes L[block b, block b - g]^T x_b out of its NB entries of the working
+//                copy.  That tile is a row tile of L: it comes in along memory rows, and the transposition is the index of
+//                the (broadcast) LDS read.
+//   k_dc_color   X = Z L^T (+ state), ONE launch, a workgroup per NB states (the longest rows first).  The block columns
+//                left of the diagonal are one gemm_tile<double, BT> with A = Z, B = the NB rows of L, K = NB * tile -- an
+//                fp64 MFMA chain per element, ascending in k; the diagonal block continues each chain with plain
+//                multiply-adds over k <= i out of the packed block, so nothing above the diagonal is taken from memory;
+//                the state is added last.
 // Every kernel of a block column starts with a read of the verdict word and returns on a failed pivot before its first
 // store.  Three dependent launches per block column, no waits inside a kernel, no atomics at all: the order of every sum is
 // a function of (Na, NB) alone and a run repeats bit for bit.
@@ -74,6 +85,17 @@ __device__ __forceinline__ void forward_substitute(const double* Lp, double (&x)
 #pragma unroll
         for (int k = 0; k < j; k++) s -= x[k] * row[k];
         x[j] = j < nb ? s / row[j] : 0.0;
+    }
+}
+
+// x <- L^-T x for the packed block, descending; entries from nb on are not divided: they become 0.0
+__device__ __forceinline__ void backward_substitute(const double* Lp, double (&x)[kNB], int nb) {
+#pragma unroll
+    for (int j = kNB - 1; j >= 0; j--) {
+        double s = x[j];
+#pragma unroll
+        for (int k = kNB - 1; k > j; k--) s -= Lp[k * (k + 1) / 2 + j] * x[k];
+        x[j] = j < nb ? s / Lp[j * (j + 1) / 2 + j] : 0.0;
     }
 }
 
@@ -243,6 +265,78 @@ __global__ __launch_bounds__(kThreads) void k_dw_norm(const double* __restrict__
     if (t == 0) d2[blockIdx.x] = part[0];
 }
 
+// block column b of the backward substitution; workgroup g: the tile of columns NB (b - g), 0 <= g <= b
+__global__ __launch_bounds__(kThreads) void k_ds_back(const double* __restrict__ F, int ldf, int Na, int rows, int b,
+                                                      double* __restrict__ work, double* __restrict__ X) {
+    __shared__ double Lp[kPacked];
+    __shared__ double Lt[kNB * kNB];
+    const int t = threadIdx.x, r = t & (kNB - 1), w = t / kNB;
+    const int j0 = kNB * b, nb = min(kNB, Na - j0), g = blockIdx.x;
+    const int c0 = j0 - kNB * g;
+    load_packed(F + (size_t)j0 * ldf + j0, ldf, Lp, t, kThreads);
+    if (g > 0)   // L[j0 + i][c0 + k] at Lt[i][k]: rows of the snapshot
+        for (int e = t; e < kNB * kNB; e += kThreads) Lt[e] = F[(size_t)(j0 + e / kNB) * ldf + c0 + e % kNB];
+    double x[kNB];
+    const double* src = work + (size_t)r * rows + j0;
+#pragma unroll
+    for (int j = 0; j < kNB; j++) x[j] = src[j];
+    __syncthreads();
+    backward_substitute(Lp, x, nb);
+    if (g == 0) {
+        if (w == 0) {
+            double* dst = X + (size_t)r * rows + j0;
+#pragma unroll
+            for (int j = 0; j < kNB; j++) dst[j] = x[j];
+        }
+        return;
+    }
+    constexpr int kPerWave = kNB / (kThreads / kNB);
+    double* mine = work + (size_t)r * rows + c0 + kPerWave * w;
+    for (int u = 0; u < kPerWave; u++) {
+        const double* col = Lt + kPerWave * w + u;
+        double s = mine[u];
+#pragma unroll
+        for (int i = 0; i < kNB; i++) s -= col[i * kNB] * x[i];
+        mine[u] = s;
+    }
+}
+
+constexpr size_t kColorLdsBytes = UpdateTile::kLdsBytes + sizeof(double) * kPacked;   // the GEMM tile's image | the packed block
+static_assert(UpdateTile::kLdsBytes % 16 == 0, "the packed block sits on a 16-byte boundary of the dynamic region");
+
+// row tile `tile` of X = Z L^T: Z and X are [kNB right-hand sides][ldf], the snapshot's own row stride
+__global__ __launch_bounds__(kThreads) void k_dc_color(const double* __restrict__ F, int ldf, int Na, int blocks,
+                                                       const double* __restrict__ Z, const double* __restrict__ state,
+                                                       double* X) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dc_smem[];
+    double* Lp = reinterpret_cast<double*>(dc_smem + UpdateTile::kLdsBytes);
+    const int tile = blocks - 1 - (int)blockIdx.x;   // the longest rows start first
+    const int t = threadIdx.x, r = t & (kNB - 1);
+    const int w = __builtin_amdgcn_readfirstlane(t / kNB);
+    const int j0 = kNB * tile;
+    load_packed(F + (size_t)j0 * ldf + j0, ldf, Lp, t, kThreads);
+    if (tile > 0)   // X[:, tile] = Z[:, 0 : j0] L[tile rows, 0 : j0]^T
+        gemm_tile<double, true, UpdateTile::NBUF, UpdateTile::WTM, UpdateTile::WTN>(Z, F, X, nullptr, ldf, 0, j0,
+                                                                                   reinterpret_cast<double*>(dc_smem), j0);
+    __syncthreads();   // Lp, and the tile of X that other lanes wrote
+    double z[kNB];
+    const double* src = Z + (size_t)r * ldf + j0;
+#pragma unroll
+    for (int k = 0; k < kNB; k++) z[k] = src[k];
+    constexpr int kPerWave = kNB / (kThreads / kNB);
+    double* mine = X + (size_t)r * ldf + j0 + kPerWave * w;
+    for (int u = 0; u < kPerWave; u++) {
+        const int i = kPerWave * w + u;   // (the same in every lane of a wave)
+        const double* row = Lp + i * (i + 1) / 2;
+        double s = tile > 0 ? mine[u] : 0.0;
+#pragma unroll
+        for (int k = 0; k < kNB; k++)
+            if (k <= i) s += row[k] * z[k];
+        if (state && j0 + i < Na) s += state[j0 + i];
+        mine[u] = s;
+    }
+}
+
 }  // namespace
 
 Dense64FactorPlan dense64_factor_plan(int Na) {
@@ -281,6 +375,17 @@ void launch_dense64_whiten(const Dense64FactorPlan& p, const double* factor, dou
     for (int b = 0; b < p.blocks; b++)
         hipLaunchKernelGGL(k_dw_step, dim3(p.blocks - b), dim3(kThreads), 0, st, factor, p.ldf, p.Na, p.rows, b, rhs, Y);
     hipLaunchKernelGGL(k_dw_norm, dim3(kDense64WhitenMaxRhs), dim3(kThreads), 0, st, Y, p.rows, d2);
+}
+
+void launch_dense64_back(const Dense64FactorPlan& p, const double* factor, double* work, double* X, hipStream_t st) {
+    for (int b = p.blocks - 1; b >= 0; b--)
+        hipLaunchKernelGGL(k_ds_back, dim3(b + 1), dim3(kThreads), 0, st, factor, p.ldf, p.Na, p.rows, b, work, X);
+}
+
+void launch_dense64_color(const Dense64FactorPlan& p, const double* factor, const double* Z, const double* state, double* X,
+                          hipStream_t st) {
+    hipLaunchKernelGGL(k_dc_color, dim3(p.blocks), dim3(kThreads), kColorLdsBytes, st, factor, p.ldf, p.Na, p.blocks, Z,
+                       state, X);
 }
 
 }  // namespace ekf

@@ -1376,6 +1376,39 @@ ekf_status ekf_dense64_whiten(ekf_dense64_handle h, int nrhs, const double* B /*
                               double* Y_out /* [nrhs][Na], nullable */, double* d2_out /* [nrhs], nullable */,
                               double* elapsed_ms);
 
+/* The other two things a Cholesky factor is for, against the same snapshot: the full solve X = Sigma^-1 B (the information
+ * form of the map, the weights of a full-state fusion, conditional means, the gradient of the whole-map NEES) and the
+ * colouring product that turns unit normal draws Z into maps drawn from N(state, Sigma).  Opt-in and read-only on the
+ * snapshot: no other entry point calls these or launches anything different because they exist.
+ * ekf_dense64_solve: X[r] = L^-T (L^-1 B[r]) for 1 <= nrhs <= EKF_DENSE64_WHITEN_MAX_RHS right-hand sides at once.
+ * THE FORWARD HALF IS ekf_dense64_whiten's launches as they stand: Y_out and d2_out are bit for bit what ekf_dense64_whiten
+ * returns for the same B.  The backward half, IEEE binary64, i descending from Na - 1:
+ *   x_i = (y_i - sum_{k>i} L[k][i] x_k) / L[i][i]
+ * Every quotient is a correctly rounded division by L[i][i]: no reciprocal and no inverse of a diagonal block, so the
+ * componentwise bounds |L^T x - y|_i <= gamma_Na (|L^T| |x|)_i and |Sigma x - b|_i <= gamma_{3 Na + 1} (|L| |L^T| |x|)_i hold.
+ * The association of each sum is the implementation's (block columns of 64 states, descending) and depends on (Na, block
+ * side) alone; no atomics: a run repeats bit for bit, and a right-hand side gives the same bits alone and at any position
+ * of a batch.  With X_out NULL the backward half is not run.
+ * ekf_dense64_color: X[r][i] = sum_{k<=i} L[i][k] Z[r][k], and with add_state != 0 X[r][i] = fl(that sum + state[i]), the
+ * addition coming last.  Nothing above the diagonal of the snapshot is taken as L.  The sums run in ascending k in a fixed
+ * association (fused multiply-adds on the matrix cores left of the diagonal block, plain multiply-adds inside it), no
+ * atomics, the same bits at any position of a batch: |x - L z|_i <= gamma_Na (|L| |z|)_i.
+ * THE FACTOR IS A SNAPSHOT, THE STATE IS THE CURRENT ONE (state[0 .. Na), read the way ekf_dense64_get_state_block reads it,
+ * pending rows or not): keeping the two in step is the caller's business -- call ekf_dense64_factor after the last
+ * correction.  THE HEADING OF A SAMPLE (X[r][0]) IS NOT WRAPPED.
+ * Both: EKF_ERR_INVALID before the device is looked at, in this order: a NULL handle, a NULL B / Z, nrhs out of range,
+ * X_out, Y_out and d2_out all NULL (solve) or a NULL X_out (color).  EKF_ERR_STATE where ekf_dense64_whiten returns it: no
+ * complete factor, or the snapshot's Na differs from the live dimension.
+ * Neither reads Sigma, neither flushes the pending rows, neither ends an open region; a refusal changes nothing.
+ * Synchronous, on the handle's stream; elapsed_ms (nullable) = HIP-event time of the launches.
+ * ekf_dense64_solve_launch_info reports the block side in states and the workgroup sizes of the two kernels. */
+ekf_status ekf_dense64_solve(ekf_dense64_handle h, int nrhs, const double* B /* [nrhs][Na] */,
+                             double* X_out /* [nrhs][Na], nullable */, double* Y_out /* [nrhs][Na], nullable */,
+                             double* d2_out /* [nrhs], nullable */, double* elapsed_ms);
+ekf_status ekf_dense64_color(ekf_dense64_handle h, int nrhs, const double* Z /* [nrhs][Na] */, int add_state,
+                             double* X_out /* [nrhs][Na] */, double* elapsed_ms);
+ekf_status ekf_dense64_solve_launch_info(ekf_dense64_handle h, int* block, int* threads_back, int* threads_color);
+
 /* The map in another frame.  A SLAM map is defined up to the frame it was started in; these calls change that frame on the
  * device: Sigma <- J Sigma J^T in place, one streaming pass over the live corner (16 Na^2 bytes, what a correction moves),
  * instead of ekf_dense64_get_sigma, a host product and ekf_dense64_set.  Opt-in: no other entry point calls these or
