@@ -60,6 +60,7 @@ SYMBOLS = [
     "ekf_dense64_get_padded",
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
+    "ekf_dense64_value_launch_info", "ekf_dense64_value_operands", "ekf_dense64_rank_landmarks",
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
     "ekf_dense64_solve_launch_info", "ekf_dense64_solve", "ekf_dense64_color",
     "ekf_dense64_frame_launch_info", "ekf_dense64_map_congruence", "ekf_dense64_reframe_landmarks",
@@ -101,6 +102,34 @@ class HealthReport(C.Structure):
     _fields_ = [("n_nonfinite", C.c_longlong), ("n_asym", C.c_longlong), ("n_diag_bad", C.c_longlong),
                 ("n_minor", C.c_longlong), ("max_asym", C.c_double), ("min_diag", C.c_double),
                 ("asym_i", C.c_int), ("asym_j", C.c_int), ("min_diag_i", C.c_int), ("reserved", C.c_int)]
+
+
+class ValueBest(C.Structure):
+    """ekf_dense64_value_best (include/ekfslam.h)"""
+    _fields_ = [("i_trace", C.c_int), ("i_pose", C.c_int), ("i_det", C.c_int), ("reserved", C.c_int),
+                ("v_trace", C.c_double), ("v_pose", C.c_double), ("v_det", C.c_double)]
+
+
+class ObservationValue:
+    """What value_operands() / rank_landmarks() return: per landmark dtrace, dtrace_pose, detS, S (count, 2, 2), flags,
+    in_view, Hc (count, 2, 5); info_gain = 0.5 * log(detS / det R), formed on the host; best = {i_trace, i_pose, i_det,
+    v_trace, v_pose, v_det} (index -1: nothing eligible); first_lm; ms."""
+
+    def __init__(self, first_lm, dtrace, dtrace_pose, detS, S, flags, in_view, Hc, R, best, ms):
+        self.first_lm, self.dtrace, self.dtrace_pose, self.detS, self.S, self.flags = first_lm, dtrace, dtrace_pose, detS, S, flags
+        self.in_view, self.Hc, self.R, self.ms = in_view, Hc, R, ms
+        with np.errstate(all="ignore"):
+            self.info_gain = 0.5 * np.log(detS / (R[0, 0] * R[1, 1] - R[0, 1] * R[1, 0]))
+        self.best = {name: getattr(best, name) for name, _ in ValueBest._fields_ if name != "reserved"}
+
+    def order(self, by="trace"):
+        """the indices j in [0, count) of the eligible landmarks (flag 0, in view, value not a NaN), best first; a stable
+        sort, so the lower index comes first among equal values"""
+        if by not in ("trace", "pose", "info"):
+            raise ValueError('by: "trace", "pose" or "info"')
+        v = {"trace": self.dtrace, "pose": self.dtrace_pose, "info": self.info_gain}[by]
+        ok = np.flatnonzero((self.flags == 0) & (self.in_view != 0) & ~np.isnan(v))
+        return ok[np.argsort(-v[ok], kind="stable")]
 
 
 class RegionReport(C.Structure):
@@ -284,6 +313,10 @@ def load():
         "ekf_dense64_health_launch_info": [h, _ip, _ip],
         "ekf_dense64_health": [h, C.POINTER(HealthReport), _dp],
         "ekf_dense64_symmetrize": [h, C.POINTER(C.c_longlong), _dp, _dp],
+        "ekf_dense64_value_launch_info": [h, _ip, _ip, _ip],
+        "ekf_dense64_value_operands": [h, C.c_int, C.c_int, _dp, _dp, _bp, _dp, _dp, _dp, _dp, _ip, C.POINTER(ValueBest), _dp],
+        "ekf_dense64_rank_landmarks": [h, C.POINTER(Params), C.c_int, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip,
+                                       C.POINTER(ValueBest), _bp, _dp, _dp],
         "ekf_dense64_factor_launch_info": [h, _ip, _ip],
         "ekf_dense64_factor": [h, C.POINTER(FactorReport), _dp],
         "ekf_dense64_get_factor": [h, _dp],
@@ -1255,6 +1288,65 @@ class DensePropagator64(_DensePropagatorBase):
         _check(self._lib.ekf_dense64_health_launch_info(self._h, C.byref(tile), C.byref(th)))
         return {"tile": tile.value, "threads": th.value}
 
+    def value_launch_info(self):
+        """{tile_rows, tile_lm, threads}: the tile of value_operands()' and rank_landmarks()' pass over Sigma -- tile_rows
+        fixes the order of their sums -- and its workgroup size (test hook)"""
+        self._open()
+        tr, tl, th = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_value_launch_info(self._h, C.byref(tr), C.byref(tl), C.byref(th)))
+        return {"tile_rows": tr.value, "tile_lm": tl.value, "threads": th.value}
+
+    def _value_range(self, first_lm, count):
+        first_lm = int(first_lm)
+        if count is None:
+            count = (self.live - 3) // 2 - first_lm
+        return first_lm, int(count)
+
+    def value_operands(self, Hc, R, first_lm=0, in_view=None):
+        """What one observation of each landmark in [first_lm, first_lm + count) would gain, for Jacobians given by the
+        caller: Hc (count, 2, 5) on the columns {0, 1, 2, 3 + 2 i, 4 + 2 i}, R (2, 2) shared; in_view (count,) or None
+        (all) gates the winners only.  One read-only pass over Sigma[:live, :live] for all of them (ekf_dense64_value_operands,
+        include/ekfslam.h); flushes the pending rows first.  Returns an ObservationValue."""
+        self._open()
+        Hc = np.ascontiguousarray(Hc, dtype=np.float64)
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if Hc.ndim != 3 or Hc.shape[1:] != (2, 5) or R.shape != (2, 2):
+            raise ValueError("Hc must be count x 2 x 5 and R 2 x 2")
+        first_lm, count = self._value_range(first_lm, Hc.shape[0])
+        if in_view is not None:
+            in_view = np.ascontiguousarray(in_view, dtype=np.uint8)
+            if in_view.shape != (count,):
+                raise ValueError("in_view must hold count entries")
+        n = max(count, 0)
+        dt, dp, det = (np.empty(n, dtype=np.float64) for _ in range(3))
+        S, flags = np.empty((n, 2, 2), dtype=np.float64), np.empty(n, dtype=np.int32)
+        best, ms = ValueBest(), C.c_double()
+        _check(self._lib.ekf_dense64_value_operands(
+            self._h, first_lm, count, _d(Hc), _d(R), in_view.ctypes.data_as(_bp) if in_view is not None else None,
+            _d(dt), _d(dp), _d(det), _d(S), flags.ctypes.data_as(_ip), C.byref(best), C.byref(ms)))
+        view = in_view if in_view is not None else np.ones(n, dtype=np.uint8)
+        return ObservationValue(first_lm, dt, dp, det, S, flags, view, Hc, R, best, ms.value)
+
+    def rank_landmarks(self, first_lm=0, count=None, range_max=None, params=None):
+        """value_operands() with the reference's measurement model on the handle's own state [theta, x, y, m1x, m1y, ...]:
+        Hc is Hj of measurement() for each landmark (score_landmarks()' Hc, bit for bit), R = r_meas I, and in_view =
+        (predicted range <= range_max), everything in view with range_max None.  count None: every landmark from first_lm
+        that lies inside the live dimension.  Nothing goes up and only the results come down.  Returns an
+        ObservationValue."""
+        self._open()
+        first_lm, count = self._value_range(first_lm, count)
+        n = max(count, 0)
+        dt, dp, det = (np.empty(n, dtype=np.float64) for _ in range(3))
+        S, flags = np.empty((n, 2, 2), dtype=np.float64), np.empty(n, dtype=np.int32)
+        view, Hc = np.empty(n, dtype=np.uint8), np.empty((n, 2, 5), dtype=np.float64)
+        best, ms = ValueBest(), C.c_double()
+        _check(self._lib.ekf_dense64_rank_landmarks(
+            self._h, C.byref(params) if params is not None else None, first_lm, count,
+            0.0 if range_max is None else float(range_max), _d(dt), _d(dp), _d(det), _d(S), flags.ctypes.data_as(_ip),
+            C.byref(best), view.ctypes.data_as(_bp), _d(Hc), C.byref(ms)))
+        r = (params if params is not None else default_params()).r_meas
+        return ObservationValue(first_lm, dt, dp, det, S, flags, view, Hc, r * np.eye(2), best, ms.value)
+
     WHITEN_MAX_RHS = 64   # EKF_DENSE64_WHITEN_MAX_RHS
 
     def factor(self):
@@ -2043,6 +2135,23 @@ class DenseEKFSLAM:
     def symmetrize(self):
         """DensePropagator64.symmetrize(): both halves of the live corner equal again, at the caller's cadence"""
         return self.handle.symmetrize()
+
+    def _mapped(self):
+        return self.n if self._init_flag else self._known
+
+    def observation_value(self, range_max=None):
+        """DensePropagator64.rank_landmarks() over the landmarks the map has (all n after measurement(), the known ones of
+        data_association() otherwise): what looking at each of them next would take off tr Sigma, off the pose variances
+        and off the entropy.  range_max: the sensor's reach, None = unlimited."""
+        k = self._mapped()
+        if k < 1:
+            raise ValueError("the map has no landmark yet")
+        return self.handle.rank_landmarks(0, k, range_max, self.params)
+
+    def best_view(self, k, by="trace", range_max=None):
+        """the k landmarks most worth observing next, best first: by="trace" (drop of tr Sigma), "pose" (drop of the pose
+        variances) or "info" (drop of the entropy); the lower index first among equal values.  -> int array (<= k)"""
+        return self.observation_value(range_max).order(by)[:int(k)]
 
     def factor(self):
         """DensePropagator64.factor() of the live corner: definiteness and log det Sigma"""

@@ -8,7 +8,8 @@
 // exact symmetrisation (ekf_dense64_health.hip), its Cholesky factor with the substitution against it
 // (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), the
 // map re-expressed in another frame (ekf_dense64_frame.hip), a second handle's map joined onto it (ekf_dense64_join.hip), a map
-// or a submap copied into a second handle (ekf_dense64_extract.hip), and
+// or a submap copied into a second handle (ekf_dense64_extract.hip), what observing each landmark would gain
+// (ekf_dense64_value.hip), and
 // the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
@@ -978,6 +979,94 @@ ekf_status ekf_dense64_symmetrize(ekf_dense64_handle d, long long* n_changed, do
     if (n_changed) *n_changed = (long long)w[ekf::kDense64HealthAsym];
     if (max_asym) std::memcpy(max_asym, &w[ekf::kDense64HealthMaxBits], sizeof(double));
     return EKF_OK;
+}
+
+// ---- what observing each landmark would gain (ekf_dense64_value.hip) --------------------------------------------------------
+ekf_status ekf_dense64_value_launch_info(ekf_dense64_handle d, int* tile_rows, int* tile_lm, int* threads) {
+    if (!d || !tile_rows || !tile_lm || !threads) return fail(EKF_ERR_INVALID, "ekf_dense64_value_launch_info: null argument");
+    *tile_rows = ekf::kDense64ValueTileRows;
+    *tile_lm = ekf::kDense64ValueTileLm;
+    *threads = ekf::kDense64ValueThreads;
+    return EKF_OK;
+}
+
+namespace {
+static_assert(sizeof(ekf_dense64_value_best) == sizeof(ekf::Dense64ValueBest), "ekfslam.h and ekf_dense.hpp");
+
+struct ValueOut {
+    double *dtrace, *dtrace_pose, *detS, *S;
+    int* flag;
+    ekf_dense64_value_best* best;
+    bool none() const { return !dtrace && !dtrace_pose && !detS && !S && !flag && !best; }
+};
+
+// The checks both calls share, in the documented order behind the NULL handle; the caller holds the RegionLeave.
+ekf_status value_checks(ekf_dense64_s* d, const std::string& fn, int first_lm, int count, bool any_out) {
+    if (!any_out) return fail(EKF_ERR_INVALID, fn + ": every output is NULL");
+    if (count < 1 || first_lm < 0) return fail(EKF_ERR_INVALID, fn + ": count >= 1 and first_lm >= 0");
+    if (3 + 2 * ((long long)first_lm + count) > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the landmarks must lie inside the live dimension");
+    return EKF_OK;
+}
+
+// The pending rows applied, four launches on operands that sit in the workspace, everything asked for back behind the one
+// synchronisation; behind e0.
+ekf_status value_run(ekf_dense64_s* d, const ekf::Dense64ValuePlan& pl, const ValueOut& o, unsigned char* in_view_out,
+                     double* Hc_out, double* elapsed_ms) {
+    char* ws = d->value.as<char>();
+    const size_t n = (size_t)pl.count;
+    d->flush_pending();
+    ekf::launch_dense64_value(pl, d->S, d->ld, ws, d->stream);
+    return finish_timed(d, elapsed_ms, {{o.dtrace, ws + pl.off_dtrace, sizeof(double) * n},
+                                        {o.dtrace_pose, ws + pl.off_dpose, sizeof(double) * n},
+                                        {o.detS, ws + pl.off_det, sizeof(double) * n},
+                                        {o.S, ws + pl.off_S, sizeof(double) * 4 * n},
+                                        {o.flag, ws + pl.off_flag, sizeof(int) * n},
+                                        {o.best, ws + pl.off_best, sizeof(ekf_dense64_value_best)},
+                                        {in_view_out, ws + pl.off_view, n},
+                                        {Hc_out, ws + pl.off_Hc, sizeof(double) * 10 * n}});
+}
+}  // namespace
+
+ekf_status ekf_dense64_value_operands(ekf_dense64_handle d, int first_lm, int count, const double* Hc, const double* R,
+                                      const unsigned char* in_view, double* dtrace, double* dtrace_pose, double* detS,
+                                      double* S_out, int* flag_out, ekf_dense64_value_best* best, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_value_operands";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    const ValueOut o{dtrace, dtrace_pose, detS, S_out, flag_out, best};
+    EKFC(value_checks(d, fnc, first_lm, count, !o.none()));
+    if (!Hc || !R) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null Hc or R");
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64ValuePlan pl = ekf::dense64_value_plan(d->live, first_lm, count);
+    EKFC(d->value.reserve(d->mem, pl.bytes, false, fnc, "the observation values' workspace"));
+    char* ws = d->value.as<char>();
+    HIPC(hipMemcpyAsync(ws + pl.off_Hc, Hc, sizeof(double) * 10 * count, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipMemcpyAsync(ws + pl.off_R, R, sizeof(double) * 4, hipMemcpyHostToDevice, d->stream));
+    if (in_view) HIPC(hipMemcpyAsync(ws + pl.off_view, in_view, (size_t)count, hipMemcpyHostToDevice, d->stream));
+    else HIPC(hipMemsetAsync(ws + pl.off_view, 1, (size_t)count, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    ekf::launch_dense64_value_cols(pl, ws, d->stream);
+    return value_run(d, pl, o, nullptr, nullptr, elapsed_ms);
+}
+
+ekf_status ekf_dense64_rank_landmarks(ekf_dense64_handle d, const ekf_params* params, int first_lm, int count,
+                                      double range_max, double* dtrace, double* dtrace_pose, double* detS, double* S_out,
+                                      int* flag_out, ekf_dense64_value_best* best, unsigned char* in_view_out,
+                                      double* Hc_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_rank_landmarks";
+    if (!d) return fail(EKF_ERR_INVALID, std::string(fnc) + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    const ValueOut o{dtrace, dtrace_pose, detS, S_out, flag_out, best};
+    EKFC(value_checks(d, fnc, first_lm, count, !o.none() || in_view_out || Hc_out));
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64ValuePlan pl = ekf::dense64_value_plan(d->live, first_lm, count);
+    EKFC(d->value.reserve(d->mem, pl.bytes, false, fnc, "the observation values' workspace"));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here: its global update moves the state the terms are built from)
+    ekf::launch_dense64_value_terms(pl, d->x, p.r_meas, range_max, d->value.p, d->stream);
+    return value_run(d, pl, o, in_view_out, Hc_out, elapsed_ms);
 }
 
 // ---- the Cholesky factor of the live corner and the substitution against it (ekf_dense64_factor.hip) ----------------------

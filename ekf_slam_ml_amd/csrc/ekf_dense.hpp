@@ -453,4 +453,34 @@ void launch_dense64_region_rowmap(const Dense64RegionPlan& p, void* acc, const d
 // below Na is read or written; the padding of Sigma and of the state is neither.
 void launch_dense64_region_end(const Dense64RegionPlan& p, double* Sigma, double* state, const void* acc, void* scratch,
                                hipStream_t st);
+
+// ---- what observing each landmark would gain (ekf_dense64_value.hip; the definitions of every figure are
+// include/ekfslam.h's, ekf_dense64_value_operands): for `count` landmarks from first_lm on, with U = Sigma H^T over the live
+// corner, G = U^T U (all rows) and P = U^T U (rows 0 .. 2) in ONE read of Sigma[0:Na, 0:Na] along rows, S by the sparse
+// scoring's own launch, then the trace drops tr(S^-1 G), tr(S^-1 P), det S and the three winners.
+constexpr int kDense64ValueTileRows = 128;   // rows of Sigma a workgroup of the pass sums, in ascending order
+constexpr int kDense64ValueTileLm = 128;     // landmarks of a workgroup of the pass: one per lane
+constexpr int kDense64ValueThreads = 128;
+// what the call leaves for the host; the layout of ekf_dense64_value_best (ekfslam.h)
+struct Dense64ValueBest {
+    int i_trace, i_pose, i_det, reserved;
+    double v_trace, v_pose, v_det;
+};
+// the workspace of a call, byte offsets: Hc [count][2][5] | R [4] | S [count][4] | dtrace, dpose, detS [count] each | best |
+// the records [row_tiles][6][count] | cols [count][5] | flag [count] | in_view [count]
+struct Dense64ValuePlan {
+    int Na, first_lm, count, row_tiles, lm_tiles;
+    size_t off_Hc, off_R, off_S, off_dtrace, off_dpose, off_det, off_best, off_rec, off_cols, off_flag, off_view, bytes;
+};
+Dense64ValuePlan dense64_value_plan(int Na, int first_lm, int count);
+// One launch, the model call's: Hc (measurement_terms of ekf_kernels.hpp on the state's own pose and landmarks), cols, the
+// shared R = r_meas I and in_view = (predicted range <= range_max), or 1 when range_max <= 0.
+void launch_dense64_value_terms(const Dense64ValuePlan& p, const double* state, double r_meas, double range_max, void* ws,
+                                hipStream_t st);
+// One launch, the operands call's: cols alone (Hc, R and in_view came up from the caller).
+void launch_dense64_value_cols(const Dense64ValuePlan& p, void* ws, hipStream_t st);
+// Four launches on operands that sit in ws: the sparse scoring (S, flag; eager: nothing may be pending), the pass over
+// the corner, the fold per landmark, the winners.  Nothing at a row or column index >= Na is read (3 + 2 (first_lm +
+// count) <= Na <= the dimension: the launcher does not check).  Sigma is not written.
+void launch_dense64_value(const Dense64ValuePlan& p, const double* Sigma, int ld, void* ws, hipStream_t st);
 }  // namespace ekf

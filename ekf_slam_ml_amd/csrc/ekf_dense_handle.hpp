@@ -105,6 +105,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf joint;      // JointLayout (ekf_dense64_associate_joint, ekf_dense64_joint_operands)
     ekfrt::DeviceBuf pairs;      // Dense64PairsPlan (ekf_dense64_score_landmark_pairs), grows with n_lm
     ekfrt::DeviceBuf health;     // Dense64HealthPlan (ekf_dense64_health, ekf_dense64_symmetrize), grows with live
+    ekfrt::DeviceBuf value;      // Dense64ValuePlan (ekf_dense64_value_operands, ekf_dense64_rank_landmarks), grows with count and live
     ekfrt::DeviceBuf factor;     // the snapshot of ekf_dense64_factor: L of the live corner, Dense64FactorPlan::factor_bytes
     ekfrt::DeviceBuf factor_ws;  // Dense64FactorPlan: the verdict word, the per-block records, the diagonal of L
     ekfrt::DeviceBuf whiten;     // ekf_dense64_whiten: the working copy of B and Y, then d2

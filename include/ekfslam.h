@@ -1314,6 +1314,81 @@ ekf_status ekf_dense64_health_launch_info(ekf_dense64_handle h, int* tile, int* 
 ekf_status ekf_dense64_health(ekf_dense64_handle h, ekf_dense64_health_report* out, double* elapsed_ms);
 ekf_status ekf_dense64_symmetrize(ekf_dense64_handle h, long long* n_changed, double* max_asym, double* elapsed_ms);
 
+/* Which landmark is worth looking at next, and what would that buy?  Every call above reacts to a reading that has
+ * arrived; these two answer before it has: for each of `count` landmarks from first_lm on, what ONE hypothetical
+ * observation of it with the m = 2 Jacobian H (non-zero in the five columns cols = {0, 1, 2, 3 + 2 i, 4 + 2 i}: H[:, cols[k]]
+ * = Hc[:, k]) and the noise R would take off the trace of Sigma, off the three pose variances and off the entropy of the
+ * state.  With U = Sigma H^T (Na x 2) and S = H Sigma H^T + R:
+ *   drop of tr Sigma                 tr(S^-1 U^T U)
+ *   drop of Sigma[0][0] + [1][1] + [2][2]   tr(S^-1 U_p^T U_p), U_p the first three rows of U
+ *   drop of the entropy              0.5 (log det S - log det R)
+ * Row r of U for landmark i needs Sigma[r][0 .. 2] and Sigma[r][3 + 2 i .. 4 + 2 i] only, so all landmarks together read
+ * every element of the live corner ONCE, along rows: 8 Na^2 bytes, the traffic of ekf_dense64_health, instead of one clone
+ * and one correction per landmark.  Read-only and opt-in: no other entry point launches anything different because they
+ * exist.  Structured calls: they run on the live corner Sigma[0:Na, 0:Na], Na = live, and nothing at a row or column index
+ * >= Na is read.  Both need Sigma in memory, so they FLUSH THE PENDING ROWS FIRST, after their own argument checks, exactly
+ * as ekf_dense64_health does, and inside an open region they behave as that call does: the region ends first, and
+ * ekf_dense64_rank_landmarks builds its Jacobians and ranges from the state the region's end leaves.  Sigma after the flush,
+ * the state and the factor snapshot are untouched.
+ * DEFINITIONS, for landmark i = first_lm + j, every operation in IEEE binary64, round to nearest even, each rounded on its
+ * own (fl; no fused operation except where S says so), with x (+) y = fl(x + y):
+ *   u_a[r]  = ((((+0 (+) fl(Sigma[r][cols[0]] Hc[a][0])) (+) fl(Sigma[r][cols[1]] Hc[a][1])) (+) ..) (+) fl(Sigma[r][cols[4]]
+ *             Hc[a][4])), a = 0, 1, r < Na: row r of U, taken from ROW r of Sigma (Sigma is never symmetrised)
+ *   G00, G01, G11 = sum over r < Na of fl(u_0 u_0), fl(u_0 u_1), fl(u_1 u_1).  THE ORDER OF THE SUM is a function of Na and
+ *             tile_rows (ekf_dense64_value_launch_info) alone: from +0 in ascending r inside each block of tile_rows rows
+ *             [k tile_rows, (k + 1) tile_rows), then the blocks' sums from +0 in ascending k.  So a landmark's figures are the
+ *             same bits for any first_lm / count it is batched in, for any capacity N >= Na of the handle, on every run.
+ *   P00, P01, P11 = the same over r = 0, 1, 2 (from +0, ascending)
+ *   S, flag = S_out and flag_out of ekf_dense64_score_sparse(J = count, m = 2, s = 5, cols, Hc, R, r_shared = 1) bit for
+ *             bit -- the same kernel is launched -- and S^-1 = A is that call's Gauss-Jordan inverse of S
+ *   dtrace      = ((fl(A00 G00) (+) fl(A01 G01)) (+) fl(A10 G01)) (+) fl(A11 G11)
+ *   dtrace_pose = the same on P
+ *   detS        = fl(fl(S00 S11) - fl(S01 S10)).  No logarithm is taken on the device: the entropy drop is
+ *             0.5 log(detS / det R), the caller's to form.
+ * A landmark with flag 1 (S not finite, singular, or its inverse not finite) has dtrace = dtrace_pose = detS = NaN; S_out
+ * holds S as summed.
+ * WHAT dtrace MEANS: it is the trace drop of the update on U = Sigma H^T alone.  It equals tr Sigma - tr Sigma+ of
+ * ekf_dense64_correct_sparse (nu = 0) up to rounding when the two halves of Sigma hold the same bits, e.g. after
+ * ekf_dense64_symmetrize; that call forms Sigma+ = Sigma - U S^-1 T with T = H Sigma from rows, so otherwise the two differ by
+ * a term bounded through max_asym of ekf_dense64_health.
+ * *best (nullable): the winners among the landmarks with flag = 0 and in_view = 1 -- i_trace, i_pose, i_det are the indices
+ * j in [0, count) of the largest dtrace, dtrace_pose and detS, v_* their values; the lowest index wins a tie, a NaN never
+ * wins; with nothing eligible the index is -1 and the value a NaN.
+ * ekf_dense64_value_operands: model-free, the kernels' own entry point.  Hc [count][2][5] and R [2][2] (shared) are the
+ * caller's; in_view [count] (nullable = all 1) only gates the winners.
+ * ekf_dense64_rank_landmarks: the reference's model on the handle's own state [theta, x, y, m1x, m1y, ..]: Hc is Hj of
+ * measurement() (ekf_slam.cpp:158-166), which depends on pose and landmark alone, bit for bit the Hc_out of
+ * ekf_dense64_score_landmarks for any reading; R = params->r_meas I (NULL: the reference's constants); in_view =
+ * (predicted range sqrt(dx^2 + dy^2) <= range_max), or 1 for every landmark when range_max <= 0 or a NaN.  in_view_out
+ * [count] and Hc_out [count][2][5] (nullable) return what was used.
+ * The outputs dtrace, dtrace_pose, detS [count], S_out [count][2][2], flag_out [count] and best are nullable, not all of them
+ * (rank_landmarks: in_view_out and Hc_out count as outputs).
+ * ARGUMENT CHECKS, before the device is looked at, in this order: a NULL handle; every output NULL; count < 1 or
+ * first_lm < 0; 3 + 2 (first_lm + count) > live; a NULL Hc or R (value_operands).  Each returns EKF_ERR_INVALID and changes
+ * nothing, the pending rows included.
+ * Four launches behind the operands: the sparse scoring, the pass (a workgroup per tile of tile_rows rows x tile_lm
+ * landmarks, lane = landmark, 16-byte loads along the rows, one record of six doubles per row tile and landmark), the fold
+ * per landmark, the winners.  No floating-point atomics: a run repeats bit for bit.  The workspace (48 count ceil(Na /
+ * tile_rows) bytes of records and about 170 bytes per landmark, 19 MB for 5000 landmarks at Na = 10003) is allocated by the
+ * first call and grows with use; a failure there returns EKF_ERR_NOMEM and leaves the handle as it was.
+ * Synchronous, on the handle's stream.  elapsed_ms (nullable) = HIP-event time of the launches, the flush included. */
+typedef struct ekf_dense64_value_best {
+    int i_trace, i_pose, i_det;
+    int reserved;   /* 0 */
+    double v_trace, v_pose, v_det;
+} ekf_dense64_value_best;
+ekf_status ekf_dense64_value_launch_info(ekf_dense64_handle h, int* tile_rows, int* tile_lm, int* threads);
+ekf_status ekf_dense64_value_operands(ekf_dense64_handle h, int first_lm, int count,
+                                      const double* Hc /* [count][2][5] */, const double* R /* [2][2] */,
+                                      const unsigned char* in_view /* [count], nullable = all */,
+                                      double* dtrace, double* dtrace_pose, double* detS, double* S_out /* [count][2][2] */,
+                                      int* flag_out, ekf_dense64_value_best* best, double* elapsed_ms);
+ekf_status ekf_dense64_rank_landmarks(ekf_dense64_handle h, const ekf_params* params, int first_lm, int count,
+                                      double range_max, double* dtrace, double* dtrace_pose, double* detS,
+                                      double* S_out /* [count][2][2] */, int* flag_out, ekf_dense64_value_best* best,
+                                      unsigned char* in_view_out /* [count] */, double* Hc_out /* [count][2][5] */,
+                                      double* elapsed_ms);
+
 /* The Cholesky factor of Sigma on the device: is Sigma positive definite (the sufficient test that n_minor above is not),
  * log det Sigma (the entropy of the map; its change across a correction is the information gain), and through the forward
  * substitution of ekf_dense64_whiten the Mahalanobis distance e^T Sigma^-1 e of the WHOLE map (its NEES against ground
