@@ -53,6 +53,8 @@ SYMBOLS = [
     "ekf_dense64_fit_scan", "ekf_dense64_associate_scan",
     "ekf_dense64_score_readings", "ekf_dense64_joint_operands", "ekf_dense64_associate_joint",
     "ekf_dense64_associate_scan_joint",
+    "ekf_dense64_jcbb_launch_info", "ekf_dense64_jcbb_candidates", "ekf_dense64_jcbb_search", "ekf_dense64_associate_jcbb",
+    "ekf_dense64_associate_scan_jcbb",
     "ekf_dense64_predict_landmarks", "ekf_dense64_measure_landmarks",
     "ekf_dense64_set_carry", "ekf_dense64_get_carry",
     "ekf_dense64_set_live", "ekf_dense64_get_live", "ekf_dense64_coupling",
@@ -130,6 +132,15 @@ class ObservationValue:
         v = {"trace": self.dtrace, "pose": self.dtrace_pose, "info": self.info_gain}[by]
         ok = np.flatnonzero((self.flags == 0) & (self.in_view != 0) & ~np.isnan(v))
         return ok[np.argsort(-v[ok], kind="stable")]
+
+
+class JcbbReport(C.Structure):
+    """ekf_dense64_jcbb_report (include/ekfslam.h)"""
+    _fields_ = [("n_cand", C.c_int), ("n_pairs", C.c_int), ("n_new", C.c_int), ("n_drop", C.c_int), ("exhausted", C.c_int),
+                ("nodes", C.c_longlong), ("d2", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class RegionReport(C.Structure):
@@ -294,6 +305,14 @@ def load():
         "ekf_dense64_associate_joint": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, _ip, C.c_uint, _ip, _dp, _ip, _dp],
         "ekf_dense64_associate_scan_joint": [h, C.POINTER(Params), _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_uint, _ip, _dp,
                                              _ip, _dp, _dp],
+        "ekf_dense64_jcbb_launch_info": [h, _ip, _ip],
+        "ekf_dense64_jcbb_candidates": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, C.c_double, C.c_int, _ip, _ip, _dp, _dp,
+                                        _ip, _ip, _dp, _dp, _dp],
+        "ekf_dense64_jcbb_search": [C.c_int, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, C.c_longlong, _ip, C.POINTER(JcbbReport)],
+        "ekf_dense64_associate_jcbb": [h, C.POINTER(Params), C.c_int, _dp, C.c_int, _ip, C.c_double, _dp, C.c_longlong,
+                                       C.c_uint, _ip, _dp, C.POINTER(JcbbReport), _ip, _dp],
+        "ekf_dense64_associate_scan_jcbb": [h, C.POINTER(Params), _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_double, _dp,
+                                            C.c_longlong, C.c_uint, _ip, _dp, _ip, _dp, C.POINTER(JcbbReport), _dp],
         "ekf_dense64_predict_landmarks": [h, C.POINTER(Params), C.c_double, C.c_double, _dp, _dp, _dp],
         "ekf_dense64_measure_landmarks": [h, C.POINTER(Params), C.c_int, _dp, _bp, _ip, C.c_uint, _ip, _dp, _dp, _dp],
         "ekf_dense64_set_carry": [h, C.c_int],
@@ -941,6 +960,7 @@ class DensePropagator64(_DensePropagatorBase):
     JOSEPH_MAX_M = 32   # EKF_DENSE64_JOSEPH_MAX_M
     SCAN_MAX_BEAMS, SCAN_MAX_CIRCLES = 1024, 128   # EKF_DENSE64_SCAN_MAX_BEAMS, EKF_DENSE64_SCAN_MAX_CIRCLES
     JOINT_MAX_READINGS, JOINT_MAX_PAIRS = 128, 30   # EKF_DENSE64_JOINT_MAX_READINGS, EKF_DENSE64_JOINT_MAX_PAIRS
+    JCBB_MAX_READINGS, JCBB_MAX_CAND, JCBB_MAX_NODES = 32, 4, 1 << 22   # EKF_DENSE64_JCBB_*
 
     _PREFIX, _DTYPE, _PTR = "ekf_dense64_", np.float64, _dp
 
@@ -1834,6 +1854,120 @@ class DensePropagator64(_DensePropagatorBase):
             raise
         return k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
 
+    def jcbb_launch_info(self):
+        """(tile, threads) of the cross-block kernel: a workgroup computes tile x tile blocks W[p][q], a thread each"""
+        tile, threads = C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_jcbb_launch_info(self._h, C.byref(tile), C.byref(threads)))
+        return tile.value, threads.value
+
+    def _gate_ic(self, gate_ic, params):
+        return float(gate_ic if gate_ic is not None else (params.gate_update if params is not None else 1.0))
+
+    def jcbb_candidates(self, readings, known, gate_ic=None, max_cand=4, params=None):
+        """The device half of the joint compatibility association, read-only (pending rows are applied first): per reading
+        the up to max_cand lowest (score, landmark) pairs under gate_ic (None: gate_update) in ascending order, and the
+        cross blocks between all P candidates.  Returns a dict: cand_count (J,), cand_lm (J, max_cand; -1 beyond the count),
+        cand_nis (J, max_cand; inf beyond it), best (J,), is_new (J,), P, reading_of (P,), lm_of (P,), nis (P,), W (2P, 2P)
+        whose diagonal blocks are score_landmarks()' S bit for bit, nu (P, 2) raw, elapsed_ms -- what jcbb_search() takes."""
+        z = self._readings(readings, self.JCBB_MAX_READINGS)
+        J, max_cand = z.shape[0], int(max_cand)
+        if not 1 <= max_cand <= self.JCBB_MAX_CAND:
+            raise ValueError(f"1 <= max_cand <= {self.JCBB_MAX_CAND}")
+        cap = min(J * max_cand, self.JCBB_MAX_READINGS * self.JCBB_MAX_CAND)
+        count, is_new = np.zeros(J, dtype=np.int32), np.zeros(J, dtype=np.int32)
+        lm, nis = np.full((J, max_cand), -1, dtype=np.int32), np.full((J, max_cand), np.inf)
+        best, W, nu = np.zeros(J), np.zeros(4 * cap * cap), np.zeros((cap, 2))
+        P, ms = C.c_int(0), C.c_double()
+        _check(self._lib.ekf_dense64_jcbb_candidates(
+            self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(known),
+            self._gate_ic(gate_ic, params), max_cand, count.ctypes.data_as(_ip), lm.ctypes.data_as(_ip),
+            nis.ctypes.data_as(_dp), best.ctypes.data_as(_dp), is_new.ctypes.data_as(_ip), C.byref(P), W.ctypes.data_as(_dp),
+            nu.ctypes.data_as(_dp), C.byref(ms)))
+        n = P.value
+        pick = [(j, c) for j in range(J) for c in range(count[j])]
+        return {"cand_count": count, "cand_lm": lm, "cand_nis": nis, "best": best, "is_new": is_new, "P": n,
+                "reading_of": np.array([j for j, _ in pick], dtype=np.int32),
+                "lm_of": np.array([lm[j, c] for j, c in pick], dtype=np.int32),
+                "nis": np.array([nis[j, c] for j, c in pick], dtype=np.float64),
+                "W": W[:4 * n * n].reshape(2 * n, 2 * n).copy(), "nu": nu[:n].copy(), "elapsed_ms": ms.value}
+
+    @staticmethod
+    def jcbb_search(J, reading_of, lm_of, nis, W, nu, gate_joint, max_nodes=1 << 16):
+        """The host half: the bounded branch and bound of ekf_dense64_jcbb_search over candidates in (reading, rank) order.
+        Needs no handle and no device.  gate_joint (J,): the gate of a hypothesis of k pairings at [k - 1].  Returns (assign
+        (J,) int32: candidate number or -1, report dict: n_cand, n_pairs, n_new, n_drop, exhausted, nodes, d2)."""
+        r = np.ascontiguousarray(reading_of, dtype=np.int32)
+        l = np.ascontiguousarray(lm_of, dtype=np.int32)
+        P = r.shape[0]
+        s = np.ascontiguousarray(nis if nis is not None else np.zeros(P), dtype=np.float64)
+        Wm = np.ascontiguousarray(W, dtype=np.float64)
+        v = np.ascontiguousarray(nu, dtype=np.float64).reshape(-1)
+        g = np.ascontiguousarray(gate_joint, dtype=np.float64)
+        if l.shape != (P,) or s.shape != (P,) or Wm.size != 4 * P * P or v.shape != (2 * P,) or g.shape != (int(J),):
+            raise ValueError("reading_of, lm_of, nis (P,), W (2P, 2P), nu (P, 2), gate_joint (J,)")
+        assign, rep = np.full(int(J), -1, dtype=np.int32), JcbbReport()
+        _check(load().ekf_dense64_jcbb_search(int(J), P, r.ctypes.data_as(_ip), l.ctypes.data_as(_ip), s.ctypes.data_as(_dp),
+                                              Wm.ctypes.data_as(_dp), v.ctypes.data_as(_dp), g.ctypes.data_as(_dp),
+                                              int(max_nodes), assign.ctypes.data_as(_ip), C.byref(rep)))
+        return assign, rep.as_dict()
+
+    def associate_jcbb(self, readings, known, n_max, gate_ic=None, gate_joint=None, max_nodes=1 << 16, deferred=False,
+                       grow_live=False, params=None):
+        """A whole scan associated by joint compatibility (JCBB): the largest set of pairings whose stacked innovation
+        passes one gate against its joint covariance, found by a bounded search over the device's candidates and cross
+        blocks; unpaired readings under no landmark's gate_new become new landmarks, the rest drop; initialisation and
+        stacked corrections exactly as associate_joint().  gate_ic None: gate_update; gate_joint None: k * gate_ic.
+        Returns (known, assoc (J,) int32, best (J,), report dict, n_groups, elapsed_ms); the exception of a refused call or
+        a singular S carries .known, .assoc, .best and .report as they stood."""
+        z = self._readings(readings, self.JCBB_MAX_READINGS)
+        J = z.shape[0]
+        k, ng, rep = C.c_int(int(known)), C.c_int(0), JcbbReport()
+        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
+        g = None if gate_joint is None else np.ascontiguousarray(gate_joint, dtype=np.float64)
+        if g is not None and g.shape != (J,):
+            raise ValueError("gate_joint must hold one gate per reading")
+        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        ms = C.c_double()
+        try:
+            _check(self._lib.ekf_dense64_associate_jcbb(
+                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
+                self._gate_ic(gate_ic, params), g.ctypes.data_as(_dp) if g is not None else None, int(max_nodes), flags,
+                assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), C.byref(rep), C.byref(ng), C.byref(ms)))
+        except EkfError as e:
+            e.known, e.assoc, e.best, e.report = k.value, assoc, best, rep.as_dict()
+            raise
+        return k.value, assoc, best, rep.as_dict(), ng.value, ms.value
+
+    def associate_scan_jcbb(self, ranges, known, n_max, max_readings=32, gate_ic=None, gate_joint=None, max_nodes=1 << 16,
+                            deferred=False, grow_live=False, params=None, want_report=False):
+        """fit_scan(ranges, max_readings <= 32) followed by associate_jcbb's path on the circles it finds, in one call.
+        Returns (known, centres (k, 2), assoc (k,) int32, best (k,)) as associate_scan does, with want_report also the
+        report dict (all zero for a scan without a circle); the exception carries .report too."""
+        r = self._scan(ranges)
+        max_readings = int(max_readings)
+        if not 1 <= max_readings <= self.JCBB_MAX_READINGS:
+            raise ValueError(f"1 <= max_readings <= {self.JCBB_MAX_READINGS}")
+        k, cnt = C.c_int(int(known)), C.c_int(0)
+        cen = np.zeros((max_readings, 2), dtype=np.float64)
+        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
+        g = None if gate_joint is None else np.ascontiguousarray(gate_joint, dtype=np.float64)
+        if g is not None and g.shape != (max_readings,):
+            raise ValueError("gate_joint must hold one gate per reading of max_readings")
+        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
+        rep = JcbbReport()
+        try:
+            _check(self._lib.ekf_dense64_associate_scan_jcbb(
+                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
+                int(n_max), C.byref(k), self._gate_ic(gate_ic, params), g.ctypes.data_as(_dp) if g is not None else None,
+                int(max_nodes), flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
+                best.ctypes.data_as(_dp), C.byref(rep), None))
+        except EkfError as e:
+            e.known, e.centres, e.assoc, e.best = k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+            e.report = rep.as_dict()
+            raise
+        out = (k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy())
+        return out + (rep.as_dict(),) if want_report else out
+
     def predict_landmarks(self, dtheta, dx, want_terms=False, params=None):
         """prediction() (ekf_slam.cpp:55-106) for the twist (dtheta, dx) on the handle's own state: Fr = I + A, Qr = q_pose I
         and the pose update are built on the device from state[0] (both branches of :79, |dtheta| < straight_eps is the
@@ -2047,6 +2181,7 @@ class DenseEKFSLAM:
         d.carry = bool(carry)
         d.live = 3 if self.grow_live else 3 + 2 * self.n
         self._known, self._init_flag = 0, False
+        self.jcbb_report = None   # the report of the last jcbb_association() / scan_association(joint="jcbb")
 
     def close(self):
         self.handle.close()
@@ -2090,9 +2225,33 @@ class DenseEKFSLAM:
             raise
         return assoc
 
+    def jcbb_association(self, meas_xy, gate_ic=None, gate_joint=None, max_nodes=1 << 16):
+        """the readings of one scan associated by joint compatibility (DensePropagator64.associate_jcbb): the largest
+        jointly compatible set of pairings, then joint_association()'s initialisation and stacked corrections; returns
+        assoc (J,) int32 as data_association() does.  The report of the last call is .jcbb_report."""
+        try:
+            self._known, assoc, _, self.jcbb_report, _, _ = self.handle.associate_jcbb(
+                meas_xy, self._known, self.n, gate_ic, gate_joint, max_nodes, self.deferred, self.grow_live, self.params)
+        except EkfError as e:
+            self._known = e.known
+            raise
+        return assoc
+
     def scan_association(self, ranges, joint=False):
         """one LaserScan through the landmarks node (circle fitting) into data_association() -- or, with joint=True, into
-        joint_association() -- in one call; returns (centres (k, 2), assoc (k,) int32) of the k circles found"""
+        joint_association(), with joint="jcbb" into jcbb_association() (at most 32 circles, the default gates) -- in one
+        call; returns (centres (k, 2), assoc (k,) int32) of the k circles found"""
+        if isinstance(joint, str):
+            if joint != "jcbb":
+                raise ValueError('joint must be False, True or "jcbb"')
+            try:
+                self._known, centres, assoc, _, self.jcbb_report = self.handle.associate_scan_jcbb(
+                    ranges, self._known, self.n, deferred=self.deferred, grow_live=self.grow_live, params=self.params,
+                    want_report=True)
+            except EkfError as e:
+                self._known = e.known
+                raise
+            return centres, assoc
         call = self.handle.associate_scan_joint if joint else self.handle.associate_scan
         try:
             self._known, centres, assoc, _ = call(ranges, self._known, self.n, deferred=self.deferred,

@@ -17,6 +17,7 @@
 // cut for it, and nothing at an index from it on is read or written; ekf_dense64_coupling (ekf_dense64_live.hip) measures
 // what ties the live corner to the rest.  Where an operand sits in its buffer is ekf_dense64_layout.hpp's business; the
 // entry points see the typed views of ekf_dense_handle.hpp only.
+#include "ekf_dense64_jcbb.hpp"
 #include "ekf_dense_handle.hpp"
 
 using namespace ekfrt;
@@ -413,44 +414,30 @@ void joint_correct_launch(ekf_dense64_s* d, const ekf::Params& p, const JointVie
     ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
 }
 
-// The joint rule on J readings (include/ekfslam.h).  [upload | per launch: terms | score | argmin | resolve] and the record
-// back (the FIRST synchronisation); the live dimension once; [init per 32 new landmarks | per 30 pairs: operands | correction
-// | heading wrap] with each correction's own synchronisation.  *elapsed_ms as in associate_readings.
-ekf_status associate_joint(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, int J, const double* meas_xy, int n_max,
-                           int* known, unsigned flags, int* assoc_out, double* best_out, int* n_groups_out,
-                           double* elapsed_ms) {
+// the legs of a call with several synchronisations: behind each one the time between its events (0 when it failed before
+// reading them) joins the total, which *out (nullable; on entry the time of what ran before) follows
+struct LegTimer {
+    double* out;
+    double total, ms = 0.0;
+    explicit LegTimer(double* elapsed_ms) : out(elapsed_ms), total(elapsed_ms ? *elapsed_ms : 0.0) {}
+    double* pms() { return out ? &ms : nullptr; }
+    ekf_status operator()(ekf_status st) { total += ms; ms = 0.0; if (out) *out = total; return st; }
+};
+
+// Steps 4 LIVE, 5 INIT and 6 CORRECT of THE JOINT RULE (include/ekfslam.h) on a decision that is made: rec [J] the final
+// records (kind, win) on the host, n_new and n_pairs their counts, and on the device what k_djt_resolve leaves (jv.xb,
+// pair_lm, pair_j, W_full, W_last).  queue_resolve runs behind this leg's e0 and in front of its first launch: nothing for
+// a caller whose resolve launch is behind it already.  The live dimension once; [init per 32 new landmarks | per 30 pairs:
+// operands | correction | heading wrap] with each correction's own synchronisation.
+template <class Queue>
+ekf_status joint_apply(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, const JointView& jv, int k,
+                       const ekf::Dense64LmRecord* rec, int n_new, int n_pairs, int* known, unsigned flags, int* assoc_out,
+                       int* n_groups_out, LegTimer& leg, Queue&& queue_resolve) {
     const std::string fn = fnc;
     const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
-    const L::JointLayout jl = L::joint_layout();
-    const JointView jv = view(d->joint.p, jl);
-    double total = elapsed_ms ? *elapsed_ms : 0.0, ms = 0.0;
-    double* pms = elapsed_ms ? &ms : nullptr;
-    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
-    const int k = *known;
-    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
-    HIPC(hipEventRecord(d->e0, d->stream));
-    d->finish_leave();   // (a region that is being left ends here)
-    if (k > 0)
-        // (cut as for the full map, whatever is known: the launches stay inside the buffer reserved for it)
-        score_readings_launch(d, p, jv, J, 0, k, joint_chunk(J, n_max), true, [&](int j0, int nr, const SpsView& v) {
-            ekf::launch_dense64_joint_argmin(v.nis, nr, k, p.gate_new, p.gate_update, jv.pre + j0, d->stream);
-        });
-    else
-        ekf::launch_dense64_joint_argmin(nullptr, J, 0, p.gate_new, p.gate_update, jv.pre, d->stream);
-    ekf::launch_dense64_joint_resolve(jv.pre, J, k, n_max, p.gate_update, p.sigma0_landmark, d->x, jv.xy, jv.head, jv.rec,
-                                      jv.pair_lm, jv.pair_j, jv.xb, jv.W_full, jv.W_last, d->stream);
-    struct { int n_match, n_new, n_pairs, zero; ekf::Dense64LmRecord rec[kJointReadings]; double xb[2 * kJointReadings]; } down;
-    static_assert(sizeof(down) == sizeof(int) * 4 + 32 * kJointReadings + 16 * kJointReadings, "the record of one copy");
-    EKFC(leg(finish_timed(d, pms, {{&down, jv.head, jl.record_bytes}})));
-    const int n_new = down.n_new, n_pairs = down.n_pairs;
-    if (n_new < 0 || k + n_new > n_max || n_pairs < 0 || n_pairs > J || down.n_match < 0 || down.n_match + n_new > J)
-        return fail(EKF_ERR_HIP, fn + ": the resolve kernel left an impossible record");
+    double* pms = leg.pms();
     const int n_groups = (n_pairs + kJointPairs - 1) / kJointPairs;
     if (n_groups_out) *n_groups_out = n_groups;
-    for (int j = 0; j < J; j++) {
-        if (best_out) best_out[j] = down.rec[j].best;
-        if (assoc_out) assoc_out[j] = (down.rec[j].kind & ekf::kDense64LmCorrect) ? -2 : -1;
-    }
     if (n_new == 0 && n_pairs == 0) return EKF_OK;   // every reading dropped: nothing at all is written
     if (3 + 2 * (k + n_new) > d->live) {
         if (!(flags & EKF_DENSE64_LM_GROW_LIVE))
@@ -459,6 +446,7 @@ ekf_status associate_joint(ekf_dense64_s* d, const char* fnc, const ekf::Params&
         EKFC(ekf_dense64_set_live(d, 3 + 2 * (k + n_new)));
     }
     HIPC(hipEventRecord(d->e0, d->stream));
+    EKFC(queue_resolve());
     for (int g0 = 0; g0 < n_new; g0 += kJointInit) {   // s = 0, W = sigma0 I, the group's xb
         const int n = std::min(kJointInit, n_new - g0);
         init_block_launch(d, 3 + 2 * (k + g0), 2 * n, 0, n == kJointInit ? jv.W_full : jv.W_last, jv.xb + 2 * g0);
@@ -477,13 +465,49 @@ ekf_status associate_joint(ekf_dense64_s* d, const char* fnc, const ekf::Params&
         const ekf_status st = leg(correct_sparse_finish(d, fnc, deferred, 2 * V, nullptr, pms));
         if (g == 0 && (st == EKF_OK || st == EKF_ERR_STATE)) *known = k + n_new;   // the initialisations stand
         for (int v = 0; v < V; j_next++) {
-            if (!(down.rec[j_next].kind & ekf::kDense64LmCorrect)) continue;
-            if (assoc_out) assoc_out[j_next] = st == EKF_OK ? down.rec[j_next].win : -1;
+            if (!(rec[j_next].kind & ekf::kDense64LmCorrect)) continue;
+            if (assoc_out) assoc_out[j_next] = st == EKF_OK ? rec[j_next].win : -1;
             v++;
         }
         if (st != EKF_OK) return st;
     }
     return EKF_OK;
+}
+
+// The joint rule on J readings (include/ekfslam.h).  [upload | per launch: terms | score | argmin | resolve] and the record
+// back (the FIRST synchronisation); then joint_apply.  *elapsed_ms as in associate_readings.
+ekf_status associate_joint(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, int J, const double* meas_xy, int n_max,
+                           int* known, unsigned flags, int* assoc_out, double* best_out, int* n_groups_out,
+                           double* elapsed_ms) {
+    const std::string fn = fnc;
+    const L::JointLayout jl = L::joint_layout();
+    const JointView jv = view(d->joint.p, jl);
+    LegTimer leg(elapsed_ms);
+    const int k = *known;
+    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here)
+    if (k > 0)
+        // (cut as for the full map, whatever is known: the launches stay inside the buffer reserved for it)
+        score_readings_launch(d, p, jv, J, 0, k, joint_chunk(J, n_max), true, [&](int j0, int nr, const SpsView& v) {
+            ekf::launch_dense64_joint_argmin(v.nis, nr, k, p.gate_new, p.gate_update, jv.pre + j0, d->stream);
+        });
+    else
+        ekf::launch_dense64_joint_argmin(nullptr, J, 0, p.gate_new, p.gate_update, jv.pre, d->stream);
+    ekf::launch_dense64_joint_resolve(jv.pre, J, k, n_max, p.gate_update, p.sigma0_landmark, d->x, jv.xy, jv.head, jv.rec,
+                                      jv.pair_lm, jv.pair_j, jv.xb, jv.W_full, jv.W_last, d->stream);
+    struct { int n_match, n_new, n_pairs, zero; ekf::Dense64LmRecord rec[kJointReadings]; double xb[2 * kJointReadings]; } down;
+    static_assert(sizeof(down) == sizeof(int) * 4 + 32 * kJointReadings + 16 * kJointReadings, "the record of one copy");
+    EKFC(leg(finish_timed(d, leg.pms(), {{&down, jv.head, jl.record_bytes}})));
+    const int n_new = down.n_new, n_pairs = down.n_pairs;
+    if (n_new < 0 || k + n_new > n_max || n_pairs < 0 || n_pairs > J || down.n_match < 0 || down.n_match + n_new > J)
+        return fail(EKF_ERR_HIP, fn + ": the resolve kernel left an impossible record");
+    for (int j = 0; j < J; j++) {
+        if (best_out) best_out[j] = down.rec[j].best;
+        if (assoc_out) assoc_out[j] = (down.rec[j].kind & ekf::kDense64LmCorrect) ? -2 : -1;
+    }
+    return joint_apply(d, fnc, p, jv, k, down.rec, n_new, n_pairs, known, flags, assoc_out, n_groups_out, leg,
+                       [] { return EKF_OK; });
 }
 
 // what the joint path needs in memory: the buffer of its own, the pending panels, the scoring buffer once for the full map
@@ -492,6 +516,157 @@ ekf_status associate_joint_reserve(ekf_dense64_s* d, const char* fnc, int J, int
     if (deferred) EKFC(pend_reserve(d, fnc));
     if (n_max > 0) EKFC(sps_reserve(d, L::sps_layout(joint_chunk(J, n_max) * n_max, 2, 5, true, false).bytes, fnc));
     return EKF_OK;
+}
+
+// ---- joint compatibility (ekf_dense64_jcbb.hip, ekf_dense64_jcbb.hpp), shared by ekf_dense64_jcbb_candidates,
+// ekf_dense64_associate_jcbb and ekf_dense64_associate_scan_jcbb ------------------------------------------------------------
+constexpr int kJcbbReadings = ekf::kDense64JcbbMaxReadings, kJcbbCand = ekf::kDense64JcbbMaxCand;
+constexpr int kJcbbP = kJcbbReadings * kJcbbCand;
+static_assert(kJcbbReadings == EKF_DENSE64_JCBB_MAX_READINGS && kJcbbCand == EKF_DENSE64_JCBB_MAX_CAND &&
+                  kJcbbReadings == ekf::kJcbbMaxReadings && kJcbbCand == ekf::kJcbbMaxCand &&
+                  ekf::kJcbbMaxNodes == EKF_DENSE64_JCBB_MAX_NODES,
+              "ekfslam.h, ekf_dense64_layout.hpp and ekf_dense64_jcbb.hpp");
+
+// what comes down in one copy (JcbbLayout from head to cols)
+struct JcbbDown {
+    int head[4], cand_count[kJcbbReadings], offset[kJcbbReadings], is_new[kJcbbReadings], cand_lm[kJcbbP], reading_of[kJcbbP],
+        lm_of[kJcbbP];
+    double best[kJcbbReadings], cand_nis[kJcbbP], nu[2 * kJcbbP];
+};
+static_assert(sizeof(JcbbDown) == 5264, "the record of one copy: JcbbLayout::record_bytes");
+
+ekf_status jcbb_reserve(ekf_dense64_s* d, const char* fnc) {
+    const L::JcbbLayout l = L::jcbb_layout();
+    if (l.record_bytes != sizeof(JcbbDown)) return fail(EKF_ERR_HIP, std::string(fnc) + ": JcbbLayout and JcbbDown disagree");
+    EKFC(d->jcbb.reserve(d->mem, l.bytes, true, fnc, "the joint compatibility buffer"));
+    const size_t n = (l.bytes - l.W) / sizeof(double);   // the host's copy of W, behind the device buffer: 512 KB once
+    if (d->jcbb_W.size() < n) {
+        try {
+            d->jcbb_W.assign(n, 0.0);
+        } catch (const std::bad_alloc&) {
+            return fail(EKF_ERR_NOMEM, std::string(fnc) + ": out of host memory for the cross blocks");
+        }
+    }
+    return EKF_OK;
+}
+
+// gate_ic, the joint gates (nullable) and the node budget: the checks the jcbb calls make behind their own
+ekf_status jcbb_gates_ok(const std::string& fn, const ekf::Params& p, int J, double gate_ic, const double* gate_joint,
+                         long long max_nodes) {
+    if (!(std::isfinite(gate_ic) && gate_ic > 0.0 && gate_ic <= p.gate_new))
+        return fail(EKF_ERR_INVALID, fn + ": gate_ic must be finite and lie in (0, gate_new]");
+    for (int k = 0; gate_joint && k < J; k++)
+        if (!(std::isfinite(gate_joint[k]) && gate_joint[k] > 0.0))
+            return fail(EKF_ERR_INVALID, fn + ": every joint gate must be finite and > 0");
+    if (max_nodes < 1 || max_nodes > EKF_DENSE64_JCBB_MAX_NODES)
+        return fail(EKF_ERR_INVALID, fn + ": max_nodes must lie in [1, 2^22]");
+    return EKF_OK;
+}
+
+// The device half on J readings that sit in jv.xy, behind e0: the pending rows applied, [per launch: terms | score | select]
+// against landmarks 0 .. k - 1 cut into launches of `chunk` readings, then [terms of the candidates | cross blocks]; the
+// record and (want_W) the blocks come down behind ONE synchronisation, and the record is checked.
+ekf_status jcbb_device(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, const JointView& jv, int J, int k, int chunk,
+                       double gate_ic, int max_cand, bool want_W, JcbbDown* down, double* elapsed_ms) {
+    const L::JcbbLayout ql = L::jcbb_layout();
+    const JcbbView q = view(d->jcbb.p, ql);
+    const int p_cap = std::min(J * max_cand, kJcbbP);
+    d->flush_pending();   // the scores, the selection and W see one Sigma in memory (a region that is being left ends here)
+    auto select = [&](const double* nis, int j0, int nr) {
+        ekf::launch_dense64_jcbb_select(nis, nr, k, j0, max_cand, gate_ic, p.gate_new, q.cand_count, q.cand_lm, q.cand_nis,
+                                        q.best, q.is_new, d->stream);
+    };
+    if (k > 0)
+        score_readings_launch(d, p, jv, J, 0, k, chunk, true, [&](int j0, int nr, const SpsView& v) { select(v.nis, j0, nr); });
+    else
+        select(nullptr, 0, J);
+    ekf::launch_dense64_jcbb_terms(d->x, jv.xy, J, q.cand_count, q.cand_lm, q.head, q.offset, q.reading_of, q.lm_of, q.cols,
+                                   q.Hc, q.nu, d->stream);
+    if (k > 0)   // (nothing known: no candidate, P = 0, no block)
+        ekf::launch_dense64_jcbb_cross(d->S, d->ld, q.head, q.cols, q.Hc, p.r_meas, p_cap, q.W, d->stream);
+    // W sits at stride P, which the host does not know yet: the copy takes the 4 p_cap^2 doubles the call could fill (32 KB at
+    // J = 8, 512 KB at J = 32), all inside the buffer cut for P = 128; what lies beyond 4 P^2 is never read
+    EKFC(finish_timed(d, elapsed_ms, {{down, q.head, ql.record_bytes},
+                                      {want_W && k > 0 ? d->jcbb_W.data() : nullptr, q.W, sizeof(double) * 4 * p_cap * p_cap}}));
+    const int P = down->head[0];
+    bool ok = P >= 0 && P <= p_cap;
+    int sum = 0;
+    for (int j = 0; j < J && ok; j++) {
+        const int n = down->cand_count[j];
+        ok = n >= 0 && n <= max_cand && down->offset[j] == sum;
+        for (int c = 0; c < n && ok; c++) {
+            const int i = down->cand_lm[j * kJcbbCand + c];
+            ok = i >= 0 && i < k && sum + c < P && down->reading_of[sum + c] == j && down->lm_of[sum + c] == i;
+        }
+        sum += n;
+    }
+    if (!ok || sum != P) return fail(EKF_ERR_HIP, std::string(fnc) + ": the selection kernels left an impossible record");
+    return EKF_OK;
+}
+
+// W [P][P][2][2] as it came down -> out [2P][2P] row-major in candidate order
+void jcbb_unpack_W(const double* blocks, int P, double* out) {
+    const size_t n = 2 * (size_t)P;
+    for (int pp = 0; pp < P; pp++)
+        for (int qq = 0; qq < P; qq++)
+            for (int e = 0; e < 4; e++)
+                out[(2 * (size_t)pp + e / 2) * n + 2 * qq + e % 2] = blocks[((size_t)pp * P + qq) * 4 + e];
+}
+
+// The whole rule on J readings (include/ekfslam.h): the device half and its one synchronisation, the search, the records
+// k_djt_resolve turns into slots, positions and the pair list, then steps 4 - 6 of THE JOINT RULE through joint_apply.
+ekf_status associate_jcbb(ekf_dense64_s* d, const char* fnc, const ekf::Params& p, int J, const double* meas_xy, int n_max,
+                          int* known, double gate_ic, const double* gate_joint, long long max_nodes, unsigned flags,
+                          int* assoc_out, double* best_out, ekf_dense64_jcbb_report* report, int* n_groups_out,
+                          double* elapsed_ms) {
+    const JointView jv = view(d->joint.p, L::joint_layout());
+    LegTimer leg(elapsed_ms);
+    const int k = *known;
+    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    JcbbDown down;
+    // (cut as for the full map, whatever is known: the launches stay inside the buffer reserved for it)
+    EKFC(leg(jcbb_device(d, fnc, p, jv, J, k, n_max > 0 ? joint_chunk(J, n_max) : J, gate_ic, kJcbbCand, true, &down,
+                         leg.pms())));
+    const int P = down.head[0];
+    std::vector<double> W(4 * (size_t)P * P);
+    jcbb_unpack_W(d->jcbb_W.data(), P, W.data());
+    double gates[kJcbbReadings];
+    for (int m = 0; m < J; m++) gates[m] = gate_joint ? gate_joint[m] : (double)(m + 1) * gate_ic;
+    int assign[kJcbbReadings];
+    ekf::JcbbSearch search(J, P, down.reading_of, down.lm_of, W.data(), down.nu, gates, max_nodes);
+    const ekf::JcbbResult res = search.run(assign);
+    // the records: what k_djt_argmin would have left (pre), and what k_djt_resolve makes of them (fin) -- no conflicts, the
+    // NEW readings in ascending j while slot < n_max
+    ekf::Dense64LmRecord pre[kJcbbReadings], fin[kJcbbReadings];
+    int n_new = 0, n_pairs = 0, rank = 0;
+    for (int j = 0; j < J; j++) {
+        ekf::Dense64LmRecord r{-1, 0, down.best[j], 0.0, 0, 0};
+        if (assign[j] >= 0) r.win = down.lm_of[assign[j]], r.kind = ekf::kDense64LmCorrect;
+        else if (down.is_new[j]) r.win = k, r.kind = ekf::kDense64LmNew;
+        pre[j] = fin[j] = r;
+        if (r.kind == ekf::kDense64LmNew) {
+            fin[j].win = k + rank++;
+            if (fin[j].win >= n_max) fin[j].win = -1, fin[j].kind = 0;
+            else if (0.0 < p.gate_update) fin[j].kind |= ekf::kDense64LmCorrect;
+        }
+        n_new += (fin[j].kind & ekf::kDense64LmNew) != 0;
+        n_pairs += (fin[j].kind & ekf::kDense64LmCorrect) != 0;
+        if (best_out) best_out[j] = down.best[j];
+        if (assoc_out) assoc_out[j] = (fin[j].kind & ekf::kDense64LmCorrect) ? -2 : -1;
+    }
+    if (report) *report = ekf_dense64_jcbb_report{P, res.n_pairs, n_new, J - res.n_pairs - n_new, res.exhausted, res.nodes, res.d2};
+    return joint_apply(d, fnc, p, jv, k, fin, n_new, n_pairs, known, flags, assoc_out, n_groups_out, leg, [&]() -> ekf_status {
+        HIPC(hipMemcpyAsync(jv.pre, pre, sizeof(ekf::Dense64LmRecord) * J, hipMemcpyHostToDevice, d->stream));
+        ekf::launch_dense64_joint_resolve(jv.pre, J, k, n_max, p.gate_update, p.sigma0_landmark, d->x, jv.xy, jv.head, jv.rec,
+                                          jv.pair_lm, jv.pair_j, jv.xb, jv.W_full, jv.W_last, d->stream);
+        return EKF_OK;
+    });
+}
+
+ekf_status associate_jcbb_reserve(ekf_dense64_s* d, const char* fnc, int J, int n_max, bool deferred) {
+    EKFC(associate_joint_reserve(d, fnc, J, n_max, deferred));
+    return jcbb_reserve(d, fnc);
 }
 
 }  // namespace
@@ -1752,6 +1927,139 @@ ekf_status ekf_dense64_associate_scan_joint(ekf_dense64_handle d, const ekf_para
     std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
     if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
     return associate_joint(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, nullptr, elapsed_ms);
+}
+
+// ---- joint compatibility: the candidates and their cross blocks on the device, the search on the host -------------------
+ekf_status ekf_dense64_jcbb_launch_info(ekf_dense64_handle d, int* tile, int* threads) {
+    if (!d) return fail(EKF_ERR_INVALID, "ekf_dense64_jcbb_launch_info: null handle");
+    if (tile) *tile = ekf::kDense64JcbbTile;
+    if (threads) *threads = ekf::kDense64JcbbTile * ekf::kDense64JcbbTile;
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_jcbb_candidates(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy, int known,
+                                       double gate_ic, int max_cand, int* cand_count_out, int* cand_lm_out,
+                                       double* cand_nis_out, double* best_out, int* is_new_out, int* P_out, double* W_out,
+                                       double* nu_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_jcbb_candidates";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    if (!meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (J < 1 || J > kJcbbReadings) return fail(EKF_ERR_INVALID, fn + ": J must lie in [1, 32]");
+    if (known < 0 || known > kSparseRows / 2 || 3 + 2 * (long long)known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks (at most 32768) must lie inside the live dimension");
+    const ekf::Params p = landmark_params(params);
+    EKFC(jcbb_gates_ok(fn, p, J, gate_ic, nullptr, 1));
+    if (max_cand < 1 || max_cand > kJcbbCand) return fail(EKF_ERR_INVALID, fn + ": max_cand must lie in [1, 4]");
+    if (!cand_count_out && !cand_lm_out && !cand_nis_out && !best_out && !is_new_out && !P_out && !W_out && !nu_out)
+        return fail(EKF_ERR_INVALID, fn + ": every output is NULL");
+    HIPC(hipSetDevice(d->device));
+    EKFC(joint_reserve(d, fnc));
+    EKFC(jcbb_reserve(d, fnc));
+    const int chunk = known > 0 ? joint_chunk(J, known) : J;
+    if (known > 0) EKFC(sps_reserve(d, L::sps_layout(chunk * known, 2, 5, true, false).bytes, fnc));
+    const JointView jv = view(d->joint.p, L::joint_layout());
+    HIPC(hipMemcpyAsync(jv.xy, meas_xy, sizeof(double) * 2 * J, hipMemcpyHostToDevice, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    JcbbDown down;
+    EKFC(jcbb_device(d, fnc, p, jv, J, known, chunk, gate_ic, max_cand, W_out != nullptr, &down, elapsed_ms));
+    const int P = down.head[0];
+    for (int j = 0; j < J; j++) {
+        if (cand_count_out) cand_count_out[j] = down.cand_count[j];
+        if (best_out) best_out[j] = down.best[j];
+        if (is_new_out) is_new_out[j] = down.is_new[j];
+        for (int c = 0; c < max_cand; c++) {
+            if (cand_lm_out) cand_lm_out[j * max_cand + c] = down.cand_lm[j * kJcbbCand + c];
+            if (cand_nis_out) cand_nis_out[j * max_cand + c] = down.cand_nis[j * kJcbbCand + c];
+        }
+    }
+    if (P_out) *P_out = P;
+    if (nu_out) std::memcpy(nu_out, down.nu, sizeof(double) * 2 * P);
+    if (W_out) jcbb_unpack_W(d->jcbb_W.data(), P, W_out);
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_jcbb_search(int J, int P, const int* reading_of, const int* lm_of, const double* nis, const double* W,
+                                   const double* nu, const double* gate_joint, long long max_nodes, int* assign_out,
+                                   ekf_dense64_jcbb_report* report) {
+    const std::string fn = "ekf_dense64_jcbb_search";
+    (void)nis;   // the candidates come ranked: their scores are the caller's record, no decision reads them
+    if (!gate_joint || !assign_out || (P > 0 && (!reading_of || !lm_of || !W || !nu)))
+        return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (ekf::jcbb_arguments_bad(J, P, reading_of, lm_of, gate_joint, max_nodes))
+        return fail(EKF_ERR_INVALID, fn + ": bad argument (1 <= J <= 32, 0 <= P <= 128, reading_of ascending with at most 4 "
+                                          "candidates a reading, every gate finite and > 0, 1 <= max_nodes <= 2^22)");
+    ekf::JcbbSearch search(J, P, reading_of, lm_of, W, nu, gate_joint, max_nodes);
+    const ekf::JcbbResult res = search.run(assign_out);
+    if (report) *report = ekf_dense64_jcbb_report{P, res.n_pairs, 0, J - res.n_pairs, res.exhausted, res.nodes, res.d2};
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_associate_jcbb(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy, int n_max,
+                                      int* known, double gate_ic, const double* gate_joint, long long max_nodes,
+                                      unsigned flags, int* assoc_out, double* best_out, ekf_dense64_jcbb_report* report,
+                                      int* n_groups_out, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_associate_jcbb";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (J < 1 || J > kJcbbReadings) return fail(EKF_ERR_INVALID, fn + ": J must lie in [1, 32]");
+    EKFC(associate_checks(d, fn, n_max, known, flags));
+    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
+    const ekf::Params p = landmark_params(params);
+    EKFC(jcbb_gates_ok(fn, p, J, gate_ic, gate_joint, max_nodes));
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (n_groups_out) *n_groups_out = 0;
+    if (report) *report = ekf_dense64_jcbb_report{0, 0, 0, 0, 0, 0, 0.0};
+    for (int j = 0; j < J; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+    }
+    HIPC(hipSetDevice(d->device));
+    EKFC(associate_jcbb_reserve(d, fnc, J, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
+    return associate_jcbb(d, fnc, p, J, meas_xy, n_max, known, gate_ic, gate_joint, max_nodes, flags, assoc_out, best_out, report,
+                          n_groups_out, elapsed_ms);
+}
+
+// ekf_dense64_fit_scan, then the path of ekf_dense64_associate_jcbb on the first min(count, max_readings) centres
+ekf_status ekf_dense64_associate_scan_jcbb(ekf_dense64_handle d, const ekf_params* params, const double* ranges, int n_beams,
+                                           int max_readings, int n_max, int* known, double gate_ic, const double* gate_joint,
+                                           long long max_nodes, unsigned flags, int* count_out, double* centres_out,
+                                           int* assoc_out, double* best_out, ekf_dense64_jcbb_report* report,
+                                           double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_associate_scan_jcbb";
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kJcbbReadings)
+        return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 32]");
+    EKFC(associate_checks(d, fn, n_max, known, flags));
+    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
+    const ekf::Params p = landmark_params(params);
+    EKFC(jcbb_gates_ok(fn, p, max_readings, gate_ic, gate_joint, max_nodes));
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    *count_out = 0;
+    if (report) *report = ekf_dense64_jcbb_report{0, 0, 0, 0, 0, 0, 0.0};
+    for (int j = 0; j < max_readings; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
+    }
+    HIPC(hipSetDevice(d->device));
+    EKFC(associate_jcbb_reserve(d, fnc, max_readings, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
+    ScanRecord rec{};
+    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
+    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
+    *count_out = J;
+    if (J == 0) return EKF_OK;
+    double xy[2 * kJcbbReadings];
+    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
+    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
+    return associate_jcbb(d, fnc, p, J, xy, n_max, known, gate_ic, gate_joint, max_nodes, flags, assoc_out, best_out, report,
+                          nullptr, elapsed_ms);
 }
 
 // ---- the reference's prediction() and measurement() on the handle's own state ------------------------------------------

@@ -237,6 +237,24 @@ void launch_dense64_joint_resolve(const Dense64LmRecord* pre, int J, int known, 
 void launch_dense64_joint_operands(const double* state, const double* xy, const int* lm, const int* rj, int V, double r_meas,
                                    int* cols, double* Hc, double* R, double* nu, hipStream_t st);
 
+// ---- joint compatibility association (ekf_dense64_jcbb.hip; the search is ekf_dense64_jcbb.hpp's, the definitions are
+// include/ekfslam.h's, ekf_dense64_jcbb_candidates).  The arrays are JcbbLayout's, cut for 32 readings of 4 candidates.
+// One workgroup per reading over nis [n_readings][count] (count = 0: nis unread), reading j0 + b: the up to max_cand lowest
+// (score, index) pairs below gate_ic in ascending order into cand_lm / cand_nis [j][4] (-1 / +inf beyond cand_count [j]),
+// best [j] and is_new [j] as launch_dense64_joint_argmin defines best and NEW.
+void launch_dense64_jcbb_select(const double* nis, int n_readings, int count, int j0, int max_cand, double gate_ic,
+                                double gate_new, int* cand_count, int* cand_lm, double* cand_nis, double* best, int* is_new,
+                                hipStream_t st);
+// One workgroup: offset [J] (the exclusive scan of cand_count), head [0] = P, and per candidate p = offset [j] + rank:
+// reading_of, lm_of and the operands cols [p][5], Hc [p][2][5], nu [p][2] (bearing raw) of launch_dense64_joint_terms.
+void launch_dense64_jcbb_terms(const double* state, const double* xy, int J, const int* cand_count, const int* cand_lm,
+                               int* head, int* offset, int* reading_of, int* lm_of, int* cols, double* Hc, double* nu,
+                               hipStream_t st);
+// W [P][P][2][2], P = head [0] <= p_cap (the grid is cut for p_cap): W[p][q] = Hc_p Sigma[cols_p, cols_q] Hc_q^T in the order
+// of the sparse scoring kernel, + r_meas I where p == q.  A thread per block, a workgroup per kDense64JcbbTile^2 of them.
+void launch_dense64_jcbb_cross(const double* Sigma, int ld, const int* head, const int* cols, const double* Hc, double r_meas,
+                               int p_cap, double* W, hipStream_t st);
+
 // ---- the reference's motion model and the top of its measurement() on the handle's state (ekf_dense64_model.hip).
 // One thread: Fr [3][3] = eye + A, Qr [3][3] = q_pose I, upd [3] of prediction() (:67-96) for the heading state[0] and the
 // twist (dtheta, dx); |dtheta| < straight_eps takes the straight branch.  Fr, Qr, upd: where propagate_block's operands go.

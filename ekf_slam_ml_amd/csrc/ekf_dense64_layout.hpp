@@ -20,6 +20,9 @@ constexpr int kDense64ScanMaxClusters = 128;         // clusters of one scan, an
 constexpr int kDense64JointMaxReadings = 128;        // readings of one joint association (= kDense64ScanMaxClusters)
 constexpr int kDense64JointMaxPairs = 30;            // pairs of one stacked correction: m = 2 V <= 64 and s = 3 + 2 V <= 64
 constexpr int kDense64JointInitGroup = 32;           // new landmarks of one initialisation: r = 2 n <= 64
+constexpr int kDense64JcbbMaxReadings = 32;          // readings of one joint compatibility association
+constexpr int kDense64JcbbMaxCand = 4;               // candidates of a reading: P <= 128, W <= 256 x 256
+constexpr int kDense64JcbbTile = 16;                 // k_jc_cross: a workgroup computes 16 x 16 blocks W[p][q]
 
 namespace d64 {
 constexpr size_t kF = sizeof(double), kI = sizeof(int), kM = kDense64MaxM, kR = kDense64MaxR, kS = kDense64MaxS;
@@ -85,6 +88,18 @@ inline JointLayout joint_layout() {
                  xb = rec + rb * nj, pair_lm = xb + 2 * kF * nj, pair_j = pair_lm + kI * nj, W_full = pair_j + kI * nj,
                  W_last = W_full + kF * kR * kR;
     return {0, pre, head, rec, xb, pair_lm, pair_j, W_full, W_last, W_last + kF * kR * kR, pair_lm - head};
+}
+// the joint compatibility association (ekf_dense64_jcbb.hip), cut for its maxima (32 readings, 4 candidates each, P <= 128):
+// what comes down in one copy: head (ints: P, 0, 0, 0) | cand_count [32] | offset [32] | is_new [32] | cand_lm [32][4] |
+// reading_of [128] | lm_of [128] (ints) | best [32] | cand_nis [32][4] | nu [128][2]; then what stays on the device: cols
+// [128][5] (ints) | Hc [128][2][5]; then W [P][P][2][2] at the call's own P (512 KB at P = 128), on a 32-byte boundary
+struct JcbbLayout { size_t head, cand_count, offset, is_new, cand_lm, reading_of, lm_of, best, cand_nis, nu, cols, Hc, W, bytes, record_bytes; };
+inline JcbbLayout jcbb_layout() {
+    const size_t nj = 32, nc = 4, np = nj * nc, cand_count = 4 * kI, offset = cand_count + kI * nj, is_new = offset + kI * nj,
+                 cand_lm = is_new + kI * nj, reading_of = cand_lm + kI * np, lm_of = reading_of + kI * np,
+                 best = lm_of + kI * np, cand_nis = best + kF * nj, nu = cand_nis + kF * np, cols = nu + 2 * kF * np,
+                 Hc = cols + kI * 5 * np, W = (Hc + 10 * kF * np + 31) / 32 * 32;
+    return {0, cand_count, offset, is_new, cand_lm, reading_of, lm_of, best, cand_nis, nu, cols, Hc, W, W + 4 * kF * np * np, cols};
 }
 }  // namespace d64
 

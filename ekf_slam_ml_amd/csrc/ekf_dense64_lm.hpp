@@ -57,14 +57,17 @@ __device__ __forceinline__ void lm_merge(Two& t, const Two& o) {
 }
 
 // One workgroup of kLmThreads: the two smallest of nis [count] with NaNs skipped (a NaN -- a flagged candidate -- never
-// wins and disturbs nobody).  The result is thread 0's; sh: one Two per wave.  Every thread of the block calls it.
-__device__ __forceinline__ Two lm_block_min(const double* __restrict__ nis, int count, Two* sh) {
+// wins and disturbs nobody); with `bounded`, of the pairs strictly above (after, after_i) in that order only.  The result is
+// thread 0's; sh: one Two per wave.  Every thread of the block calls it, and a second call waits for a barrier behind the
+// first (thread 0 reads sh).
+__device__ __forceinline__ Two lm_block_min_after(const double* __restrict__ nis, int count, Two* sh, bool bounded,
+                                                  double after, int after_i) {
     const int tid = threadIdx.x;
     const double inf = __builtin_huge_val();
     Two t{inf, inf, 0x7fffffff, 0x7fffffff};
     for (int j = tid; j < count; j += kLmThreads) {
         const double v = nis[j];
-        if (v == v) lm_insert(t, v, j);
+        if (v == v && (!bounded || score_less(after, after_i, v, j))) lm_insert(t, v, j);
     }
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -80,6 +83,9 @@ __device__ __forceinline__ Two lm_block_min(const double* __restrict__ nis, int 
     if (tid == 0)
         for (int w = 1; w < kLmThreads / 64; w++) lm_merge(t, sh[w]);
     return t;
+}
+__device__ __forceinline__ Two lm_block_min(const double* __restrict__ nis, int count, Two* sh) {
+    return lm_block_min_after(nis, count, sh, false, 0.0, 0);
 }
 
 }  // namespace lm

@@ -62,6 +62,11 @@ inline JointView view(void* b, const L::JointLayout& l) {
             reinterpret_cast<ekf::Dense64LmRecord*>(f64(b, l.rec)), f64(b, l.xb), i32(b, l.pair_lm), i32(b, l.pair_j),
             f64(b, l.W_full), f64(b, l.W_last)};
 }
+struct JcbbView { int *head, *cand_count, *offset, *is_new, *cand_lm, *reading_of, *lm_of; double *best, *cand_nis, *nu; int* cols; double *Hc, *W; };
+inline JcbbView view(void* b, const L::JcbbLayout& l) {
+    return {i32(b, l.head), i32(b, l.cand_count), i32(b, l.offset), i32(b, l.is_new), i32(b, l.cand_lm), i32(b, l.reading_of),
+            i32(b, l.lm_of), f64(b, l.best), f64(b, l.cand_nis), f64(b, l.nu), i32(b, l.cols), f64(b, l.Hc), f64(b, l.W)};
+}
 
 // The end of a timed entry point: e1 behind the launches, the launch error, the copies back to the host (a null dst is
 // skipped), ONE synchronisation, the time between the handle's events.
@@ -103,6 +108,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf lm_rec;     // ekf::Dense64LmRecord, the decision record of one reading (the landmark front end)
     ekfrt::DeviceBuf scan;       // ScanLayout (ekf_dense64_fit_scan, ekf_dense64_associate_scan)
     ekfrt::DeviceBuf joint;      // JointLayout (ekf_dense64_associate_joint, ekf_dense64_joint_operands)
+    ekfrt::DeviceBuf jcbb;       // JcbbLayout (ekf_dense64_jcbb_candidates, ekf_dense64_associate_jcbb), reserved once for its maxima
     ekfrt::DeviceBuf pairs;      // Dense64PairsPlan (ekf_dense64_score_landmark_pairs), grows with n_lm
     ekfrt::DeviceBuf health;     // Dense64HealthPlan (ekf_dense64_health, ekf_dense64_symmetrize), grows with live
     ekfrt::DeviceBuf value;      // Dense64ValuePlan (ekf_dense64_value_operands, ekf_dense64_rank_landmarks), grows with count and live
@@ -116,6 +122,7 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads
     std::vector<int> host_stamp; // [N] the duplicate check of the index lists
+    std::vector<double> jcbb_W;  // the cross blocks of a joint compatibility call as they came down, [P][P][2][2]
     std::vector<int> host_keep;  // ekf_dense64_extract_map: the list and the run flags on their way up
     int pend_rows = 0;           // rows of the two panels that wait for the flush, 0 .. 64
     int factor_na = 0;           // the live dimension the snapshot was taken at, 0 before the first factor

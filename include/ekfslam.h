@@ -911,6 +911,100 @@ ekf_status ekf_dense64_associate_scan_joint(ekf_dense64_handle h, const ekf_para
                                             int* assoc_out /* [max_readings] nullable */,
                                             double* best_out /* [max_readings] nullable */, double* elapsed_ms);
 
+/* JOINT COMPATIBILITY (JCBB, Neira & Tardos 2001) for a scan.  Both rules above are nearest neighbour: they decide per
+ * reading and never look at the correlation between pairings.  With a pose error common to all readings and a map that is
+ * tight in relative terms, a reading is individually compatible with its neighbour's landmark, and the per-reading argmin
+ * pairs it there or loses a conflict and drops it.  The joint rule accepts the LARGEST set of pairings whose stacked
+ * innovation passes ONE gate against its joint covariance S_H = H_H Sigma H_H^T + R.
+ * THE DEVICE HALF is whatever touches Sigma: the scores (as ekf_dense64_score_readings), the candidates of each reading, their
+ * operands, and the cross blocks between different candidate pairings, which no other call produces.
+ *   CANDIDATES of reading j: the up to max_cand lowest (score, index) pairs with score < gate_ic in ascending lexicographic
+ *   order; a NaN is never a candidate, ties go to the lower index, a score equal to gate_ic is not one.  best[j]: the overall
+ *   minimum, gate_new when nothing lies below it; is_new[j] = (no landmark has score < gate_new).  The P candidates of a call
+ *   are numbered in ascending (j, rank).
+ *   W [2P][2P], row-major in candidate order; its 2 x 2 block (p, q) is, with cols_p = {0, 1, 2, 3 + 2 i_p, 4 + 2 i_p} and
+ *   Hc_p, nu_p the operands of ekf_dense64_score_landmarks (bearing RAW),
+ *     G[k][b]  = Sigma[cols_p[k]][cols_q[b]]                 (Sigma as stored, never symmetrised)
+ *     T'[a][b] = sum_k fma(Hc_p[a][k], G[k][b], .)           from +0, k ascending, rounded to fp64
+ *     W[a][b]  = sum_k fma(T'[a][k], Hc_q[b][k], .)          from +0, k ascending;  p == q: + r_meas delta_ab by one plain addition
+ *   the order of the sparse scoring kernel: the diagonal block (p, p) is bit for bit the S_out of ekf_dense64_score_landmarks
+ *   for that reading and landmark.  Blocks (p, q) and (q, p)^T may differ in bits, as Sigma[i][j] and Sigma[j][i] do.  A
+ *   block's bits depend on its two candidates alone.  No atomics; the same inputs give the same bits on every run.
+ * THE HOST HALF is the search (sequential, O(k^2) per node, on at most 512 KB).  Depth first over the readings in ascending
+ *   j; at reading j its candidates in ascending rank, skipping a landmark the hypothesis uses already, then the branch "j
+ *   unpaired".  An extension to k pairings is accepted only when its joint d2 < gate_joint[k - 1].  The incumbent starts as
+ *   "nothing paired"; better means more pairings, then a smaller d2, then found first.  A node is pruned when pairings so far
+ *   + readings still to come that have a candidate < the incumbent's pairings.  d2 comes from an incremental Cholesky factor
+ *   along the path (pair number m owns rows 2m, 2m + 1; the block (new pair, earlier pair) = W[p_new][p_old], the lower
+ *   triangle only): per new row r, columns c ascending, every product rounded and subtracted in turn, t ascending,
+ *     v = W[r][c];  v = v - L[r][t] L[c][t] (t < c);  L[r][c] = v / L[c][c]
+ *     d = W[r][r];  d = d - L[r][t]^2 (t < r);  not (finite and > 0): the extension is incompatible;  L[r][r] = sqrt(d)
+ *     s = nu[r];  s = s - L[r][t] z[t] (t < r);  z[r] = s / L[r][r];  d2 = d2 + z[r]^2
+ *   (the library is built with -ffp-contract=off; this order is part of the contract).  Every visit of a (reading, hypothesis)
+ *   is one node; after max_nodes nodes the incumbent stands and exhausted = 1.  A function of its inputs.
+ * ekf_dense64_jcbb_candidates: the read-only hook for the device half.  Pending rows are applied first (inside elapsed_ms,
+ *   behind the argument checks) so that the scores, the selection and W see one Sigma in memory; nothing else is written.
+ *   [terms | score | select] per scoring launch, [candidate terms | cross blocks], ONE synchronisation.  cand_lm_out and
+ *   cand_nis_out are [J][max_cand] (-1 and +inf beyond cand_count_out[j]; cand_nis bit for bit ekf_dense64_score_readings');
+ *   W_out must hold (2 min(J max_cand, 128))^2 doubles and receives [2P][2P] at the call's own P; nu_out [P][2].  Every
+ *   output is nullable, not all.  1 <= J <= 32, 0 <= known <= 32768 inside the live dimension, gate_ic finite in (0,
+ *   gate_new], 1 <= max_cand <= 4; otherwise EKF_ERR_INVALID before the device is looked at.
+ * ekf_dense64_jcbb_search: the search as it stands; no handle, no device.  reading_of [P] ascending, lm_of [P], nis [P] (the
+ *   caller's record: no decision reads it; nullable), W [2P][2P], nu [2P], gate_joint [J]; assign_out [J]: the candidate number
+ *   of each reading or -1.  report: n_cand = P, n_pairs, n_drop = J - n_pairs, n_new = 0, exhausted, nodes, d2.
+ * ekf_dense64_associate_jcbb, the whole rule:
+ *   1 pending rows are applied.  2 SCORE as step 1 of THE JOINT RULE.  3 candidates (max_cand = 4) and cross blocks, ONE
+ *   synchronisation, the search.  A reading of the chosen hypothesis is MATCH with its landmark; an unpaired reading with
+ *   is_new is NEW and takes a slot in ascending j while slot < n_max, exactly as step 3 of THE JOINT RULE hands them out
+ *   (the same kernel does it); every other reading is DROP.  Then steps 4 LIVE, 5 INIT and 6 CORRECT of THE JOINT RULE run
+ *   unchanged, through the same internal functions: the corrections use the WRAPPED bearing and the operands of
+ *   ekf_dense64_joint_operands from the then-current state.  The flags mean what they mean there.
+ *   gate_joint NULL: gate_joint[k - 1] = k gate_ic.  *known = 0: nothing is scored, every reading is NEW.
+ *   report: n_cand = P, n_pairs = the pairings of the hypothesis, n_new = the readings that got a slot, n_drop the rest.
+ *   TWIN CONTRACT: the state, Sigma, the pending rows and *known afterwards are bit for bit those of a twin handle on which
+ *   the host calls ekf_dense64_jcbb_candidates (max_cand = 4), ekf_dense64_jcbb_search, ekf_dense64_init_block per group,
+ *   then per group ekf_dense64_joint_operands and ekf_dense64_correct_sparse[_deferred], and sets the heading.
+ *   J = 1: the decision can differ from ekf_dense64_associate_joint's in the last bits of d2 (a Cholesky factor here, the
+ *   Gauss-Jordan elimination of the scoring kernel there, and gate_ic in place of gate_update); not claimed bit-equal.
+ *   FAILURES, checked before the device is looked at, in this order: NULL handle; NULL known or meas_xy; J outside [1, 32];
+ *   the checks of ekf_dense64_associate_landmarks in its order; n_max > 32768; gate_ic not finite, <= 0 or > gate_new; a
+ *   gate_joint entry not finite or <= 0; max_nodes outside [1, EKF_DENSE64_JCBB_MAX_NODES] -> EKF_ERR_INVALID, nothing changes.
+ *   Memory: one buffer of 18 KB of operands plus 512 KB of W, reserved by the first call for the maxima; besides it what
+ *   ekf_dense64_associate_joint reserves.  A failure returns EKF_ERR_NOMEM / EKF_ERR_HIP and leaves the handle as it was.
+ * ekf_dense64_associate_scan_jcbb: ekf_dense64_fit_scan(max_out = max_readings <= 32) in front, as
+ *   ekf_dense64_associate_scan_joint wraps the per-reading joint rule; gate_joint [max_readings] or NULL.
+ * ekf_dense64_jcbb_launch_info: the cross kernel's tile (blocks per side) and threads per workgroup. */
+#define EKF_DENSE64_JCBB_MAX_READINGS 32
+#define EKF_DENSE64_JCBB_MAX_CAND      4          /* P <= 128, W <= 256 x 256 */
+#define EKF_DENSE64_JCBB_MAX_NODES    (1 << 22)
+typedef struct { int n_cand, n_pairs, n_new, n_drop, exhausted; long long nodes; double d2; } ekf_dense64_jcbb_report;
+ekf_status ekf_dense64_jcbb_launch_info(ekf_dense64_handle h, int* tile, int* threads);
+ekf_status ekf_dense64_jcbb_candidates(ekf_dense64_handle h, const ekf_params* params, int J,
+                                       const double* meas_xy /* [J][2] */, int known, double gate_ic, int max_cand,
+                                       int* cand_count_out /* [J] */, int* cand_lm_out /* [J][max_cand] */,
+                                       double* cand_nis_out /* [J][max_cand] */, double* best_out /* [J] */,
+                                       int* is_new_out /* [J] */, int* P_out, double* W_out /* [2P][2P] */,
+                                       double* nu_out /* [P][2] raw */, double* elapsed_ms);
+ekf_status ekf_dense64_jcbb_search(int J, int P, const int* reading_of /* [P] */, const int* lm_of /* [P] */,
+                                   const double* nis /* [P] nullable */, const double* W /* [2P][2P] */,
+                                   const double* nu /* [2P] */, const double* gate_joint /* [J] */, long long max_nodes,
+                                   int* assign_out /* [J] */, ekf_dense64_jcbb_report* report /* nullable */);
+ekf_status ekf_dense64_associate_jcbb(ekf_dense64_handle h, const ekf_params* params, int J,
+                                      const double* meas_xy /* [J][2] */, int n_max, int* known /* IN/OUT */,
+                                      double gate_ic, const double* gate_joint /* [J] nullable */, long long max_nodes,
+                                      unsigned flags, int* assoc_out /* [J] nullable */, double* best_out /* [J] nullable */,
+                                      ekf_dense64_jcbb_report* report /* nullable */, int* n_groups_out /* nullable */,
+                                      double* elapsed_ms);
+ekf_status ekf_dense64_associate_scan_jcbb(ekf_dense64_handle h, const ekf_params* params,
+                                           const double* ranges /* [n_beams] */, int n_beams, int max_readings,
+                                           int n_max, int* known /* IN/OUT */, double gate_ic,
+                                           const double* gate_joint /* [max_readings] nullable */, long long max_nodes,
+                                           unsigned flags, int* count_out,
+                                           double* centres_out /* [max_readings][2] nullable */,
+                                           int* assoc_out /* [max_readings] nullable */,
+                                           double* best_out /* [max_readings] nullable */,
+                                           ekf_dense64_jcbb_report* report /* nullable */, double* elapsed_ms);
+
 /* The other two methods of rigid2d::EKF_SLAM on the handle's own state: prediction() (ekf_slam.cpp:55-106) and measurement()
  * (:108-197).  After ekf_dense64_associate_landmarks the heading lives on the device only -- it is corrected there and
  * nothing is read back -- so a caller of the model-free ekf_dense64_propagate_block would fetch state[0], evaluate four
