@@ -590,12 +590,14 @@ __global__ __launch_bounds__(TPB) void k_rank2_queue(double* __restrict__ sigma,
 // The factors of all corrections of the step come from k_call_factors (U = K, V = G, [b][2 kCallV][ld]; a filter's
 // corrections are slots 0 .. cnt[b] - 1, the state goes with the factor kernel); per element the expression is
 // rank2_tile's.  POL: ekf_rank2_plan.hpp (ChainPlan::policy).
+typedef double double8_t __attribute__((ext_vector_type(8)));
 template <int U, int POL>
 __global__ __launch_bounds__(256) void k_rank2_chain(double* sigma, const double* __restrict__ Uall,
                                                      const double* __restrict__ Vall, const int* __restrict__ cnt_all, int N,
                                                      int ld, size_t sigma_stride, int chunks, int row_blocks, int m, int C,
                                                      unsigned items_per_filter, unsigned total, unsigned* __restrict__ queue) {
     __shared__ unsigned sh_next[2];
+    static_assert(U % 8 == 0, "a full tile takes its K rows eight at a time");
     const int tiles = chunks * row_blocks, ld2n = ld >> 1, ld2a = (N + 1) >> 1;
     unsigned ahead = 0;
     if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
@@ -620,6 +622,17 @@ __global__ __launch_bounds__(256) void k_rank2_chain(double* sigma, const double
                 const int rows = min(U, N - r0);   // (uniform; > 0: r0 < N)
                 const double2_t g0 = Vb2[(size_t)(2 * c) * ld2n + c2], g1 = Vb2[(size_t)(2 * c + 1) * ld2n + c2];
                 double2_t* col = fsig + c2 + (size_t)r0 * ld2n;
+                // The tile's K rows come as 64-byte scalar loads (r0 and ld are multiples of 16 doubles, so all U rows lie inside
+                // the factor's row of ld entries; those of a short last tile beyond N - 1 feed lanes that are not stored), issued
+                // ahead of the tile's own loads so that their round trip is over when the tile arrives.  Row by row the compiler
+                // issued a pair of 8-byte scalar loads, waited for it and multiplied: sixteen round trips per sweep with nothing
+                // else in flight on the CU (tools/micro/strip_walk.hip chain waves: + 12.9 ms row by row, + 2.8 ms in bulk).
+                double8_t kq0[U / 8], kq1[U / 8];
+#pragma unroll
+                for (int h = 0; h < U / 8; h++) {
+                    kq0[h] = *reinterpret_cast<const double8_t*>(K0 + r0 + 8 * h);
+                    kq1[h] = *reinterpret_cast<const double8_t*>(K1 + r0 + 8 * h);
+                }
                 double2_t a[U];
                 if (first) {
 #pragma unroll
@@ -628,10 +641,13 @@ __global__ __launch_bounds__(256) void k_rank2_chain(double* sigma, const double
 #pragma unroll
                     for (int u = 0; u < U; u++) a[u] = ld2<(POL & 4) != 0>(col + (size_t)min(u, rows - 1) * ld2n);
                 }
+                // (the values must be in their registers HERE: the compiler may not sink the scalar loads below the wait for the
+                // tile, where their round trip would be paid with nothing else in flight)
+#pragma unroll
+                for (int h = 0; h < U / 8; h++) asm volatile("" : "+s"(kq0[h]), "+s"(kq1[h]));
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const int row = r0 + min(u, rows - 1);
-                    const double k0 = K0[row], k1 = K1[row];   // uniform address -> s_load
+                    const double k0 = kq0[u / 8][u % 8], k1 = kq1[u / 8][u % 8];
                     a[u].x = a[u].x - (k0 * g0.x + k1 * g1.x);
                     a[u].y = a[u].y - (k0 * g0.y + k1 * g1.y);
                 }

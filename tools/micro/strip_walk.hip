@@ -3,7 +3,7 @@
 //   strip-major : Sigma[b][strip][row][256 cols] -- a strip workgroup reads one contiguous block of N x 2 KB
 // One workgroup of 16 waves per (filter, strip), 8-row groups per wave, non-temporal loads, +1, non-temporal stores: what
 // k_flush_strip does to memory (ekf_delayed.hip).  160 KB of dynamic LDS keeps it at one workgroup per CU like the flush.
-// build: hipcc --offload-arch=gfx950 -O3 -o strip_walk strip_walk.hip      run: ./strip_walk [B=4096] [N=2003] [chain]
+// build: hipcc --offload-arch=gfx950 -O3 -o strip_walk strip_walk.hip      run: ./strip_walk [B=4096] [N=2003] [chain [waves]]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -218,65 +218,236 @@ __global__ __launch_bounds__(T) void k_tile_resident(double* __restrict__ sigma,
 // memory if a workgroup applied them batch by batch.  POL picks non-temporal (bit set) or plain per access set: 1 = first
 // sweep's loads, 2 = first sweep's stores, 4 = later sweeps' loads, 8 = later sweeps' stores.  sigma is not __restrict__ and m
 // is a run-time value, so every sweep's loads are real global loads.
-template <int RB, int POL>
+// OPS (bits): the walker also fetches what k_rank2_chain fetches (kv / gv: [b][2 x 8][ld] doubles of zeros, cnt[b] = sweeps).
+//   1 = a scalar count per item, loaded when the item starts; it bounds the sweeps      2 = two 16-byte G loads per lane and sweep
+//   4 = two scalar K loads per row and sweep at clamped rows, as the kernel spelled them before (the compiler issues a pair,
+//       waits for it, multiplies, issues the next pair: 16 scalar round trips per sweep)
+//   8 = the K values of a full tile as four 64-byte scalar loads issued together (the last, short tile keeps the clamped rows)
+//  16 = with 1: thread 0 fetches the NEXT item's count when that item's number is back (after the first sweep's loads) and
+//       hands it over with the number; with 2: the G values of the next sweep are loaded before this sweep's stores
+typedef double double8_t __attribute__((ext_vector_type(8)));
+template <int RB, int POL, int OPS = 0>
 __global__ __launch_bounds__(256) void k_chain(double* sigma, int N, int ld, int chunks, int row_blocks, int m, int sweeps,
-                                               unsigned items_per_filter, unsigned total, unsigned* __restrict__ queue) {
+                                               unsigned items_per_filter, unsigned total, unsigned* __restrict__ queue,
+                                               const double* __restrict__ kv, const double* __restrict__ gv,
+                                               const int* __restrict__ cnt) {
+    static_assert(RB % 8 == 0, "bulk K loads take 8 rows each");
     __shared__ unsigned sh_next[2];
+    __shared__ int sh_cnt[2];
     const int P = chunks * row_blocks;
     const size_t rs = ld >> 1;
+    constexpr bool kEarly = (OPS & 16) != 0;
     unsigned ahead = 0;
-    if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
+    int ahead_cnt = 0;
+    if (threadIdx.x == 0) {
+        ahead = atomicAdd(queue, 1u);
+        if (kEarly && (OPS & 1) && ahead < total) ahead_cnt = cnt[ahead / items_per_filter];
+    }
     for (int par = 0;; par ^= 1) {
-        if (threadIdx.x == 0) sh_next[par] = ahead;
+        if (threadIdx.x == 0) {
+            sh_next[par] = ahead;
+            if (kEarly && (OPS & 1)) sh_cnt[par] = ahead_cnt;
+        }
         __syncthreads();
         const unsigned s = __builtin_amdgcn_readfirstlane(sh_next[par]);
         if (s >= total) break;
         if (threadIdx.x == 0) ahead = atomicAdd(queue, 1u);
         const int b = s / items_per_filter, t0 = (s % items_per_filter) * m, t1 = t0 + m < P ? t0 + m : P;
         double2_t* base = reinterpret_cast<double2_t*>(sigma + (size_t)b * N * ld);
-        for (int sw = 0; sw < sweeps; sw++)
+        int nsw = sweeps;
+        if (OPS & 1) {
+            const int cb = kEarly ? __builtin_amdgcn_readfirstlane(sh_cnt[par]) : cnt[b];
+            nsw = cb < sweeps ? cb : sweeps;
+        }
+        const double2_t* gb = reinterpret_cast<const double2_t*>(gv + (size_t)b * 16 * ld);
+        auto c2_of = [&](int t) { const int c2 = (t % chunks) * 256 + (int)threadIdx.x; return c2 < (int)rs ? c2 : 0; };
+        double2_t g0 = {0.0, 0.0}, g1 = {0.0, 0.0}, gn0 = g0, gn1 = g0;
+        if (kEarly && (OPS & 2) && nsw > 0) { gn0 = gb[c2_of(t0)]; gn1 = gb[rs + c2_of(t0)]; }
+        for (int sw = 0; sw < nsw; sw++)
             for (int t = t0; t < t1; t++) {
                 const int c2 = (t % chunks) * 256 + threadIdx.x, r0 = (t / chunks) * RB;
-                if (c2 >= (ld >> 1)) continue;
+                const bool on = c2 < (int)(ld >> 1);
                 const int rows = N - r0 < RB ? N - r0 : RB;
-                double2_t* col = base + c2 + (size_t)r0 * rs;
+                double2_t* col = base + (on ? c2 : 0) + (size_t)r0 * rs;
                 double2_t a[RB];
+                const double* K0 = kv + ((size_t)b * 16 + 2 * sw) * ld;
+                if (kEarly) { g0 = gn0; g1 = gn1; }
+                else if (OPS & 2) { g0 = gb[(size_t)(2 * sw) * rs + c2_of(t)]; g1 = gb[(size_t)(2 * sw + 1) * rs + c2_of(t)]; }
                 if (sw == 0) {
 #pragma unroll
                     for (int u = 0; u < RB; u++) {
                         const double2_t* src = col + (size_t)(u < rows ? u : rows - 1) * rs;
                         a[u] = (POL & 1) ? __builtin_nontemporal_load(src) : *src;
                     }
-#pragma unroll
-                    for (int u = 0; u < RB; u++) a[u] += 1.0;
-#pragma unroll
-                    for (int u = 0; u < RB; u++)
-                        if (u < rows) { if (POL & 2) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
                 } else {
 #pragma unroll
                     for (int u = 0; u < RB; u++) {
                         const double2_t* src = col + (size_t)(u < rows ? u : rows - 1) * rs;
                         a[u] = (POL & 4) ? __builtin_nontemporal_load(src) : *src;
                     }
+                }
+                if (kEarly && (OPS & 2)) {   // the G values of the step after this one (same item), ahead of this step's stores
+                    const int tn = t + 1 < t1 ? t + 1 : t0, swn = t + 1 < t1 ? sw : sw + 1;
+                    if (swn < nsw) { gn0 = gb[(size_t)(2 * swn) * rs + c2_of(tn)]; gn1 = gb[(size_t)(2 * swn + 1) * rs + c2_of(tn)]; }
+                }
+                double k0[RB], k1[RB];
 #pragma unroll
-                    for (int u = 0; u < RB; u++) a[u] += 1.0;
+                for (int u = 0; u < RB; u++) k0[u] = k1[u] = 0.0;
+                if ((OPS & 8) && rows == RB) {
+#pragma unroll
+                    for (int h = 0; h < RB / 8; h++) {
+                        const double8_t x = *reinterpret_cast<const double8_t*>(K0 + r0 + 8 * h);        // uniform, 64-byte aligned
+                        const double8_t y = *reinterpret_cast<const double8_t*>(K0 + ld + r0 + 8 * h);
+#pragma unroll
+                        for (int u = 0; u < 8; u++) { k0[8 * h + u] = x[u]; k1[8 * h + u] = y[u]; }
+                    }
+                } else if (OPS & 12) {
+#pragma unroll
+                    for (int u = 0; u < RB; u++) {
+                        const int row = r0 + (u < rows ? u : rows - 1);
+                        k0[u] = K0[row];   // uniform address -> s_load
+                        k1[u] = K0[ld + row];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < RB; u++) {
+                    a[u] += 1.0;
+                    if (OPS & 14) a[u] -= k0[u] * g0 + k1[u] * g1;
+                }
+                if (sw == 0) {
 #pragma unroll
                     for (int u = 0; u < RB; u++)
-                        if (u < rows) { if (POL & 8) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
+                        if (u < rows && on) { if (POL & 2) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < RB; u++)
+                        if (u < rows && on) { if (POL & 8) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
                 }
+                if (kEarly && (OPS & 1) && sw == 0 && t == t0 && threadIdx.x == 0)
+                    ahead_cnt = ahead < total ? cnt[ahead / items_per_filter] : 0;
             }
     }
 }
 
-template <int RB, int POL>
-static float chain_run(double* s, int N, int ld, int B, int m, int sweeps, unsigned* queue, hipEvent_t e0, hipEvent_t e1) {
+// WAVE CLIENTS of the same queue: a workgroup is R waves that share nothing (no LDS, no barrier); every wave takes items
+// (the same batches of m tiles of 16 rows x 512 columns) by itself -- lane 0 asks an item ahead, readfirstlane hands the
+// number round -- and walks its item sub-tile by sub-tile: SR rows x 64 double2 columns (1 KB per row and wave instruction),
+// column groups fastest.  ALL sweeps of a sub-tile are done before the next one, so a stored line is re-loaded about a
+// microsecond later, and the R waves of a CU are each somewhere else in their load / add / store cycle.  POL as in
+// k_chain, but bit 2 / bit 8 tell the sweeps apart the way the kernel does: 2 = stores of every sweep but the last, 8 = the
+// last sweep's stores.  OPS as above; the count of the NEXT item is fetched when its number arrives (after the item's first
+// sub-tile), and a sub-tile's G values of all sweeps are loaded ahead of its first-sweep loads.
+template <int R, int SR, int POL, bool OPS>
+__global__ __launch_bounds__(64 * R) void k_chain_waves(double* sigma, int N, int ld, int chunks, int row_blocks, int m, int sweeps,
+                                                        unsigned items_per_filter, unsigned total, unsigned* __restrict__ queue,
+                                                        const double* __restrict__ kv, const double* __restrict__ gv,
+                                                        const int* __restrict__ cnt) {
+    constexpr int RB = 16, kSub = (RB / SR) * 4, kMaxSw = 2;   // sub-tiles of a tile; OPS keeps G of up to kMaxSw sweeps
+    const int P = chunks * row_blocks, lane = threadIdx.x & 63;
+    const size_t rs = ld >> 1;
+    auto take = [&]() { unsigned v = 0; if (lane == 0) v = atomicAdd(queue, 1u); return v; };
+    auto count_of = [&](unsigned s) { return s < total && OPS ? (cnt[s / items_per_filter] < sweeps ? cnt[s / items_per_filter] : sweeps) : sweeps; };
+    unsigned s = __builtin_amdgcn_readfirstlane(take());
+    int nsw = count_of(s);
+    while (s < total) {
+        unsigned ahead = take();
+        unsigned s_next = total;
+        int nsw_next = 0;
+        const int b = s / items_per_filter, t0 = (s % items_per_filter) * m, t1 = t0 + m < P ? t0 + m : P;
+        double2_t* base = reinterpret_cast<double2_t*>(sigma + (size_t)b * N * ld);
+        const int nq = (t1 - t0) * kSub;
+        for (int q = 0; q < nq; q++) {
+            const int t = t0 + q / kSub, sub = q % kSub;
+            const int c2 = (t % chunks) * 256 + (sub & 3) * 64 + lane, r0 = (t / chunks) * RB + (sub >> 2) * SR;
+            const int rows = N - r0 < SR ? N - r0 : SR;
+            if ((t % chunks) * 256 + (sub & 3) * 64 < (int)rs && rows > 0) {   // (uniform)
+                const bool on = c2 < (int)rs;
+                double2_t* col = base + (on ? c2 : 0) + (size_t)r0 * rs;
+                double2_t g0[kMaxSw], g1[kMaxSw];
+#pragma unroll
+                for (int sw = 0; sw < kMaxSw; sw++) {
+                    g0[sw] = g1[sw] = double2_t{0.0, 0.0};
+                    if (OPS && sw < nsw) {
+                        const double2_t* gb = reinterpret_cast<const double2_t*>(gv + ((size_t)b * 16 + 2 * sw) * ld);
+                        g0[sw] = gb[on ? c2 : 0];
+                        g1[sw] = gb[rs + (on ? c2 : 0)];
+                    }
+                }
+                double2_t a[SR];
+#pragma unroll
+                for (int sw = 0; sw < kMaxSw; sw++) {
+                    if (sw < nsw) {
+                        const bool last = sw == nsw - 1;
+                        const double* K0 = kv + ((size_t)b * 16 + 2 * sw) * ld;
+#pragma unroll
+                        for (int u = 0; u < SR; u++) {
+                            const double2_t* src = col + (size_t)(u < rows ? u : rows - 1) * rs;
+                            if (sw == 0) a[u] = (POL & 1) ? __builtin_nontemporal_load(src) : *src;
+                            else a[u] = (POL & 4) ? __builtin_nontemporal_load(src) : *src;
+                        }
+#pragma unroll
+                        for (int u = 0; u < SR; u++) {
+                            a[u] += 1.0;
+                            if (OPS) {
+                                const int row = r0 + (u < rows ? u : rows - 1);
+                                const double k0 = K0[row], k1 = K0[ld + row];   // uniform address -> s_load
+                                a[u] -= k0 * g0[sw] + k1 * g1[sw];
+                            }
+                        }
+                        if (last) {
+#pragma unroll
+                            for (int u = 0; u < SR; u++)
+                                if (u < rows && on) { if (POL & 8) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < SR; u++)
+                                if (u < rows && on) { if (POL & 2) __builtin_nontemporal_store(a[u], col + (size_t)u * rs); else col[(size_t)u * rs] = a[u]; }
+                        }
+                    }
+                }
+            }
+            if (q == 0) {   // the next item's number is back by now: fetch its count while this item is walked
+                s_next = __builtin_amdgcn_readfirstlane(ahead);
+                nsw_next = count_of(s_next);
+            }
+        }
+        s = s_next;
+        nsw = nsw_next;
+    }
+}
+
+struct ChainOps { const double* kv; const double* gv; const int* cnt; };
+
+template <int R, int SR, int POL, bool OPS>
+static float waves_run(double* s, int N, int ld, int B, int m, int sweeps, unsigned* queue, const ChainOps& o, hipEvent_t e0, hipEvent_t e1) {
+    const int chunks = (ld / 2 + 255) / 256, row_blocks = (N + 15) / 16, P = chunks * row_blocks;
+    const unsigned ipf = (unsigned)((P + m - 1) / m), total = ipf * (unsigned)B;
+    float best = 1e9f;
+    for (int rep = 0; rep < 3; rep++) {
+        hipMemsetAsync(queue, 0, sizeof(unsigned));
+        hipEventRecord(e0);
+        hipLaunchKernelGGL((k_chain_waves<R, SR, POL, OPS>), dim3(256), dim3(64 * R), 0, 0, s, N, ld, chunks, row_blocks, m, sweeps, ipf, total,
+                           queue, o.kv, o.gv, o.cnt);
+        hipEventRecord(e1);
+        hipEventSynchronize(e1);
+        float ms;
+        hipEventElapsedTime(&ms, e0, e1);
+        if (rep && ms < best) best = ms;
+    }
+    return best;
+}
+
+template <int RB, int POL, int OPS = 0>
+static float chain_run(double* s, int N, int ld, int B, int m, int sweeps, unsigned* queue, hipEvent_t e0, hipEvent_t e1,
+                       const ChainOps& o = ChainOps{nullptr, nullptr, nullptr}) {
     const int chunks = (ld / 2 + 255) / 256, row_blocks = (N + RB - 1) / RB, P = chunks * row_blocks;
     const unsigned ipf = (unsigned)((P + m - 1) / m), total = ipf * (unsigned)B;
     float best = 1e9f;
     for (int rep = 0; rep < 3; rep++) {
         hipMemsetAsync(queue, 0, sizeof(unsigned));
         hipEventRecord(e0);
-        hipLaunchKernelGGL((k_chain<RB, POL>), dim3(256), dim3(256), 0, 0, s, N, ld, chunks, row_blocks, m, sweeps, ipf, total, queue);
+        hipLaunchKernelGGL((k_chain<RB, POL, OPS>), dim3(256), dim3(256), 0, 0, s, N, ld, chunks, row_blocks, m, sweeps, ipf, total, queue,
+                           o.kv, o.gv, o.cnt);
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         float ms;
@@ -316,6 +487,66 @@ static void chain_table(double* s, int N, int ld, int B, size_t bytes, hipEvent_
     chain_rows<16, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(s, N, ld, B, bytes, queue, e0, e1);
     chain_rows<32, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(s, N, ld, B, bytes, queue, e0, e1);
     hipFree(queue);
+}
+
+template <int R, int SR>
+static void waves_row(double* s, int N, int ld, int B, unsigned* queue, const ChainOps& o, hipEvent_t e0, hipEvent_t e1) {
+    printf("%5d %8d %6d KB", R, SR, R * SR);
+    printf(" | %6.2f", waves_run<R, SR, 9, false>(s, N, ld, B, 1, 1, queue, o, e0, e1));
+    printf(" | %6.2f", waves_run<R, SR, 8, false>(s, N, ld, B, 1, 2, queue, o, e0, e1));
+    printf(" | %6.2f", waves_run<R, SR, 8, true>(s, N, ld, B, 1, 2, queue, o, e0, e1));
+    printf(" | %6.2f", waves_run<R, SR, 0, false>(s, N, ld, B, 1, 2, queue, o, e0, e1));
+    printf(" | %6.2f", waves_run<R, SR, 12, false>(s, N, ld, B, 1, 2, queue, o, e0, e1));
+    printf(" | %6.2f", waves_run<R, SR, 8, false>(s, N, ld, B, 5, 2, queue, o, e0, e1));
+    printf("\n");
+    fflush(stdout);
+}
+
+// wave clients (k_chain_waves) against the lockstep workgroup (k_chain<16, 8>, m = 1) in one run; ms, best of two after a
+// warm-up launch; "operands" = with the count, G and K fetches of the real kernel
+static int waves_table(double* s, int N, int ld, int B, hipEvent_t e0, hipEvent_t e1) {
+    unsigned* queue = nullptr;
+    double *kv = nullptr, *gv = nullptr;
+    int* cnt = nullptr;
+    const size_t fac = (size_t)B * 16 * ld * sizeof(double);
+    if (hipMalloc(&queue, sizeof(unsigned)) != hipSuccess || hipMalloc(&kv, fac) != hipSuccess || hipMalloc(&gv, fac) != hipSuccess ||
+        hipMalloc(&cnt, B * sizeof(int)) != hipSuccess) { printf("hipMalloc of the operands failed\n"); return 1; }
+    hipMemset(kv, 0, fac);
+    hipMemset(gv, 0, fac);
+    int* h = (int*)malloc(B * sizeof(int));
+    for (int i = 0; i < B; i++) h[i] = 2;
+    hipMemcpy(cnt, h, B * sizeof(int), hipMemcpyHostToDevice);
+    free(h);
+    const ChainOps o{kv, gv, cnt};
+    printf("wave clients, B = %d, N = %d, ld = %d: items of m tiles of 16 rows x 512 columns, 256 workgroups of R waves, one queue\n", B, N, ld);
+    printf("lockstep k_chain<16,8> m = 1: one sweep (policy 9) %.2f ms", chain_run<16, 9>(s, N, ld, B, 1, 1, queue, e0, e1));
+    printf(" | two sweeps %.2f ms\n", chain_run<16, 8>(s, N, ld, B, 1, 2, queue, e0, e1));
+    printf("  two sweeps + operands (1 count, 2 G, 4 K row by row, 8 K in bulk, 16 count and G ahead):\n");
+    printf("  count %.2f", chain_run<16, 8, 1>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | G %.2f", chain_run<16, 8, 2>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | K row by row %.2f", chain_run<16, 8, 4>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | K in bulk %.2f", chain_run<16, 8, 8>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | count + G %.2f", chain_run<16, 8, 3>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | count + G ahead %.2f\n", chain_run<16, 8, 19>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf("  all three as the kernel had them (7) %.2f", chain_run<16, 8, 7>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | count and G ahead (23) %.2f", chain_run<16, 8, 23>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | K in bulk (11) %.2f", chain_run<16, 8, 11>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | both (27) %.2f", chain_run<16, 8, 27>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | both, m = 2 %.2f ms\n", chain_run<16, 8, 27>(s, N, ld, B, 2, 2, queue, e0, e1, o));
+    printf("waves sub_rows  live/CU | 1 sweep | 2 sweeps, policy 8 | + operands | policy 0 | policy 12 | policy 8, m = 5\n");
+    waves_row<4, 8>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<4, 16>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<8, 8>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<8, 16>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<12, 8>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<12, 16>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<16, 8>(s, N, ld, B, queue, o, e0, e1);
+    waves_row<16, 16>(s, N, ld, B, queue, o, e0, e1);
+    printf("lockstep k_chain<16,8> m = 1 again: two sweeps %.2f ms", chain_run<16, 8>(s, N, ld, B, 1, 2, queue, e0, e1));
+    printf(" | + operands as the kernel had them (7) %.2f", chain_run<16, 8, 7>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    printf(" | count and G ahead, K in bulk (27) %.2f ms\n", chain_run<16, 8, 27>(s, N, ld, B, 1, 2, queue, e0, e1, o));
+    hipFree(queue); hipFree(kv); hipFree(gv); hipFree(cnt);
+    return 0;
 }
 
 template <int T, int RB, int MODE>
@@ -467,8 +698,9 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
-    if (argc > 3 && !strcmp(argv[3], "chain")) {   // only the chained-sweep table
-        chain_table(s, N, ld, B, bytes, e0, e1);
+    if (argc > 3 && !strcmp(argv[3], "chain")) {   // only the chained-sweep tables ("chain waves": only the wave clients')
+        if (!(argc > 4 && !strcmp(argv[4], "waves"))) chain_table(s, N, ld, B, bytes, e0, e1);
+        if (waves_table(s, N, ld, B, e0, e1)) return 1;
         if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) { printf("HIP error\n"); return 1; }
         hipFree(s);
         return 0;
