@@ -1690,6 +1690,69 @@ class DensePropagator64(_DensePropagatorBase):
         return (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0) | \
                (self.LM_JOSEPH if joseph else 0)
 
+    def _jcbb_args(self, jcbb, n, per, params):
+        """jcbb = (gate_ic, gate_joint, max_nodes) of a jcbb association call for up to n readings -> (the three arguments in
+        front of the flags (the pointer keeps its array), the report behind best); None, the other rules -> ([], None)"""
+        if jcbb is None:
+            return [], None
+        gate_ic, gate_joint, max_nodes = jcbb
+        g = None if gate_joint is None else np.ascontiguousarray(gate_joint, dtype=np.float64)
+        if g is not None and g.shape != (n,):
+            raise ValueError(f"gate_joint must hold one gate per {per}")
+        return [self._gate_ic(gate_ic, params), g.ctypes.data_as(_dp) if g is not None else None, int(max_nodes)], JcbbReport()
+
+    def _associate_readings(self, call, z, known, n_max, deferred, grow_live, params, joseph=False, jcbb=None, groups=True):
+        """The readings form of the three association rules: the C call named `call` on z (J, 2), checked by the caller.
+        jcbb: (gate_ic, gate_joint, max_nodes) for that rule, whose call also fills a report; groups: the call has
+        n_groups_out.  Returns (known, assoc (J,), best (J,), report or None, n_groups, elapsed_ms); an EkfError carries
+        .known, .assoc, .best and that rule's .report as they stood."""
+        J = z.shape[0]
+        k, ng, ms = C.c_int(int(known)), C.c_int(0), C.c_double()
+        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
+        gates, rep = self._jcbb_args(jcbb, J, "reading", params)
+        flags = self._lm_flags(deferred, grow_live, joseph)
+        tail = [C.byref(o) for o in (rep, ng if groups else None, ms) if o is not None]
+        try:
+            _check(getattr(self._lib, call)(
+                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
+                *gates, flags, assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), *tail))
+        except EkfError as e:
+            e.known, e.assoc, e.best = k.value, assoc, best
+            if rep is not None:
+                e.report = rep.as_dict()
+            raise
+        return k.value, assoc, best, rep, ng.value, ms.value
+
+    def _associate_scan(self, call, ranges, max_readings, most, known, n_max, deferred, grow_live, params, jcbb=None):
+        """The scan form of the three association rules: the C call named `call` on one scan and at most max_readings <= most
+        of its circles.  jcbb as in _associate_readings.  Returns (known, centres (k, 2), assoc (k,), best (k,), report or None) cut at the k
+        circles found; an EkfError carries .known, .centres, .assoc, .best and that rule's .report as they stood."""
+        r = self._scan(ranges)
+        max_readings = int(max_readings)
+        if not 1 <= max_readings <= most:
+            raise ValueError(f"1 <= max_readings <= {most}")
+        k, cnt = C.c_int(int(known)), C.c_int(0)
+        cen = np.zeros((max_readings, 2), dtype=np.float64)
+        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
+        gates, rep = self._jcbb_args(jcbb, max_readings, "reading of max_readings", params)
+        flags = self._lm_flags(deferred, grow_live)
+        tail = [C.byref(rep)] if rep is not None else []
+
+        def cut():
+            return tuple(a[:cnt.value].copy() for a in (cen, assoc, best))
+        try:
+            _check(getattr(self._lib, call)(
+                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
+                int(n_max), C.byref(k), *gates, flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
+                best.ctypes.data_as(_dp), *tail, None))
+        except EkfError as e:
+            e.known = k.value
+            e.centres, e.assoc, e.best = cut()
+            if rep is not None:
+                e.report = rep.as_dict()
+            raise
+        return (k.value,) + cut() + (rep,)
+
     def associate_landmarks(self, readings, known, n_max, deferred=False, grow_live=False, params=None, joseph=False):
         """data_association (ekf_slam.cpp:278-402) for the readings (J, 2) in order, on the handle's own state: per reading
         the known landmarks are scored, the reference's rule is applied on the device, a new landmark is initialised
@@ -1701,19 +1764,9 @@ class DensePropagator64(_DensePropagatorBase):
         z = np.ascontiguousarray(readings, dtype=np.float64)
         if z.ndim != 2 or z.shape[1] != 2 or z.shape[0] < 1:
             raise ValueError("readings must be J x 2 with J >= 1")
-        J = z.shape[0]
-        k = C.c_int(int(known))
-        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
-        flags = self._lm_flags(deferred, grow_live, joseph)
-        ms = C.c_double()
-        try:
-            _check(self._lib.ekf_dense64_associate_landmarks(
-                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
-                flags, assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), C.byref(ms)))
-        except EkfError as e:
-            e.known, e.assoc, e.best = k.value, assoc, best
-            raise
-        return k.value, assoc, best, ms.value
+        k, assoc, best, _, _, ms = self._associate_readings("ekf_dense64_associate_landmarks", z, known, n_max,
+                                                            deferred, grow_live, params, joseph, groups=False)
+        return k, assoc, best, ms
 
     @staticmethod
     def _scan(ranges):
@@ -1746,23 +1799,8 @@ class DensePropagator64(_DensePropagatorBase):
         cluster order, in one call: the landmarks node and the unknown_data_assoc node of the reference.  Returns (known,
         centres (k, 2), assoc (k,) int32, best (k,)); a scan without a circle gives k = 0 and writes nothing.  A refused call
         or a singular S raises EkfError; the exception carries .known, .centres, .assoc and .best as they stood."""
-        r = self._scan(ranges)
-        max_readings = int(max_readings)
-        if not 1 <= max_readings <= self.SCAN_MAX_CIRCLES:
-            raise ValueError(f"1 <= max_readings <= {self.SCAN_MAX_CIRCLES}")
-        k, cnt = C.c_int(int(known)), C.c_int(0)
-        cen = np.zeros((max_readings, 2), dtype=np.float64)
-        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
-        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
-        try:
-            _check(self._lib.ekf_dense64_associate_scan(
-                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
-                int(n_max), C.byref(k), flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
-                best.ctypes.data_as(_dp), None))
-        except EkfError as e:
-            e.known, e.centres, e.assoc, e.best = k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
-            raise
-        return k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+        return self._associate_scan("ekf_dense64_associate_scan", ranges, max_readings, self.SCAN_MAX_CIRCLES, known,
+                                    n_max, deferred, grow_live, params)[:4]
 
     @staticmethod
     def _readings(readings, most):
@@ -1818,41 +1856,16 @@ class DensePropagator64(_DensePropagatorBase):
         corrected / -1 dropped, best (J,), n_groups, elapsed_ms).  A refused call or a singular S raises EkfError; the
         exception carries .known, .assoc and .best as they stood."""
         z = self._readings(readings, self.JOINT_MAX_READINGS)
-        J = z.shape[0]
-        k, ng = C.c_int(int(known)), C.c_int(0)
-        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
-        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
-        ms = C.c_double()
-        try:
-            _check(self._lib.ekf_dense64_associate_joint(
-                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
-                flags, assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), C.byref(ng), C.byref(ms)))
-        except EkfError as e:
-            e.known, e.assoc, e.best = k.value, assoc, best
-            raise
-        return k.value, assoc, best, ng.value, ms.value
+        k, assoc, best, _, ng, ms = self._associate_readings("ekf_dense64_associate_joint", z, known, n_max, deferred,
+                                                             grow_live, params)
+        return k, assoc, best, ng, ms
 
     def associate_scan_joint(self, ranges, known, n_max, max_readings=64, deferred=False, grow_live=False, params=None):
         """fit_scan(ranges, max_readings) followed by associate_joint's path on the circles it finds, in one call.  Returns
         (known, centres (k, 2), assoc (k,) int32, best (k,)) as associate_scan does; the exception of a refused call or a
         singular S carries .known, .centres, .assoc and .best as they stood."""
-        r = self._scan(ranges)
-        max_readings = int(max_readings)
-        if not 1 <= max_readings <= self.SCAN_MAX_CIRCLES:
-            raise ValueError(f"1 <= max_readings <= {self.SCAN_MAX_CIRCLES}")
-        k, cnt = C.c_int(int(known)), C.c_int(0)
-        cen = np.zeros((max_readings, 2), dtype=np.float64)
-        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
-        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
-        try:
-            _check(self._lib.ekf_dense64_associate_scan_joint(
-                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
-                int(n_max), C.byref(k), flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
-                best.ctypes.data_as(_dp), None))
-        except EkfError as e:
-            e.known, e.centres, e.assoc, e.best = k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
-            raise
-        return k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
+        return self._associate_scan("ekf_dense64_associate_scan_joint", ranges, max_readings, self.SCAN_MAX_CIRCLES,
+                                    known, n_max, deferred, grow_live, params)[:4]
 
     def jcbb_launch_info(self):
         """(tile, threads) of the cross-block kernel: a workgroup computes tile x tile blocks W[p][q], a thread each"""
@@ -1920,53 +1933,18 @@ class DensePropagator64(_DensePropagatorBase):
         Returns (known, assoc (J,) int32, best (J,), report dict, n_groups, elapsed_ms); the exception of a refused call or
         a singular S carries .known, .assoc, .best and .report as they stood."""
         z = self._readings(readings, self.JCBB_MAX_READINGS)
-        J = z.shape[0]
-        k, ng, rep = C.c_int(int(known)), C.c_int(0), JcbbReport()
-        assoc, best = np.full(J, -2, dtype=np.int32), np.empty(J, dtype=np.float64)
-        g = None if gate_joint is None else np.ascontiguousarray(gate_joint, dtype=np.float64)
-        if g is not None and g.shape != (J,):
-            raise ValueError("gate_joint must hold one gate per reading")
-        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
-        ms = C.c_double()
-        try:
-            _check(self._lib.ekf_dense64_associate_jcbb(
-                self._h, C.byref(params) if params is not None else None, J, z.ctypes.data_as(_dp), int(n_max), C.byref(k),
-                self._gate_ic(gate_ic, params), g.ctypes.data_as(_dp) if g is not None else None, int(max_nodes), flags,
-                assoc.ctypes.data_as(_ip), best.ctypes.data_as(_dp), C.byref(rep), C.byref(ng), C.byref(ms)))
-        except EkfError as e:
-            e.known, e.assoc, e.best, e.report = k.value, assoc, best, rep.as_dict()
-            raise
-        return k.value, assoc, best, rep.as_dict(), ng.value, ms.value
+        k, assoc, best, rep, ng, ms = self._associate_readings("ekf_dense64_associate_jcbb", z, known, n_max, deferred,
+                                                               grow_live, params, jcbb=(gate_ic, gate_joint, max_nodes))
+        return k, assoc, best, rep.as_dict(), ng, ms
 
     def associate_scan_jcbb(self, ranges, known, n_max, max_readings=32, gate_ic=None, gate_joint=None, max_nodes=1 << 16,
                             deferred=False, grow_live=False, params=None, want_report=False):
         """fit_scan(ranges, max_readings <= 32) followed by associate_jcbb's path on the circles it finds, in one call.
         Returns (known, centres (k, 2), assoc (k,) int32, best (k,)) as associate_scan does, with want_report also the
         report dict (all zero for a scan without a circle); the exception carries .report too."""
-        r = self._scan(ranges)
-        max_readings = int(max_readings)
-        if not 1 <= max_readings <= self.JCBB_MAX_READINGS:
-            raise ValueError(f"1 <= max_readings <= {self.JCBB_MAX_READINGS}")
-        k, cnt = C.c_int(int(known)), C.c_int(0)
-        cen = np.zeros((max_readings, 2), dtype=np.float64)
-        assoc, best = np.full(max_readings, -2, dtype=np.int32), np.empty(max_readings, dtype=np.float64)
-        g = None if gate_joint is None else np.ascontiguousarray(gate_joint, dtype=np.float64)
-        if g is not None and g.shape != (max_readings,):
-            raise ValueError("gate_joint must hold one gate per reading of max_readings")
-        flags = (self.LM_DEFERRED if deferred else 0) | (self.LM_GROW_LIVE if grow_live else 0)
-        rep = JcbbReport()
-        try:
-            _check(self._lib.ekf_dense64_associate_scan_jcbb(
-                self._h, C.byref(params) if params is not None else None, r.ctypes.data_as(_dp), r.shape[0], max_readings,
-                int(n_max), C.byref(k), self._gate_ic(gate_ic, params), g.ctypes.data_as(_dp) if g is not None else None,
-                int(max_nodes), flags, C.byref(cnt), cen.ctypes.data_as(_dp), assoc.ctypes.data_as(_ip),
-                best.ctypes.data_as(_dp), C.byref(rep), None))
-        except EkfError as e:
-            e.known, e.centres, e.assoc, e.best = k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy()
-            e.report = rep.as_dict()
-            raise
-        out = (k.value, cen[:cnt.value].copy(), assoc[:cnt.value].copy(), best[:cnt.value].copy())
-        return out + (rep.as_dict(),) if want_report else out
+        out = self._associate_scan("ekf_dense64_associate_scan_jcbb", ranges, max_readings, self.JCBB_MAX_READINGS,
+                                   known, n_max, deferred, grow_live, params, jcbb=(gate_ic, gate_joint, max_nodes))
+        return out[:4] + (out[4].as_dict(),) if want_report else out[:4]
 
     def predict_landmarks(self, dtheta, dx, want_terms=False, params=None):
         """prediction() (ekf_slam.cpp:55-106) for the twist (dtheta, dx) on the handle's own state: Fr = I + A, Qr = q_pose I

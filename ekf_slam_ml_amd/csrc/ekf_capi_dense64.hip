@@ -280,8 +280,17 @@ ekf_status scan_fit(ekf_dense64_s* d, const char* fn, const double* ranges, int 
     return EKF_OK;
 }
 
+// the legs of a call with several synchronisations: behind each one the time between its events (0 when it failed before
+// reading them) joins the total, which *out (nullable; on entry the time of what ran before) follows
+struct LegTimer {
+    double* out;
+    double total, ms = 0.0;
+    explicit LegTimer(double* elapsed_ms) : out(elapsed_ms), total(elapsed_ms ? *elapsed_ms : 0.0) {}
+    double* pms() { return out ? &ms : nullptr; }
+    ekf_status operator()(ekf_status st) { total += ms; ms = 0.0; if (out) *out = total; return st; }
+};
+
 // ---- data_association (:278-402), shared by ekf_dense64_associate_landmarks and ekf_dense64_associate_scan -----------------
-// the argument checks both calls make, in their documented order, behind their own
 // the flags of the landmark front end: `allowed` is what the call knows; the Joseph form is eager only
 ekf_status lm_flags_ok(const std::string& fn, unsigned flags, unsigned allowed) {
     if (flags & ~allowed) return fail(EKF_ERR_INVALID, fn + ": unknown flag bits");
@@ -291,16 +300,6 @@ ekf_status lm_flags_ok(const std::string& fn, unsigned flags, unsigned allowed) 
     return EKF_OK;
 }
 Joseph lm_joseph(unsigned flags) { return (flags & EKF_DENSE64_LM_JOSEPH) ? Joseph::kUnweighted : Joseph::kNo; }
-
-ekf_status associate_checks(ekf_dense64_s* d, const std::string& fn, int n_max, const int* known, unsigned flags,
-                            unsigned allowed = EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE) {
-    if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
-        return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
-    if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
-    if (3 + 2 * *known > d->live)
-        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
-    return lm_flags_ok(fn, flags, allowed);
-}
 
 // what the loop below needs in memory
 ekf_status associate_reserve(ekf_dense64_s* d, const char* fnc, int n_max, bool deferred) {
@@ -323,10 +322,8 @@ ekf_status associate_readings(ekf_dense64_s* d, const char* fnc, const ekf::Para
     ekf::Dense64LmRecord* drec = d->lm_rec.as<ekf::Dense64LmRecord>();
     const IniInView ini = view(d->ini_in, L::ini_in_layout());
     const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
-    double total = elapsed_ms ? *elapsed_ms : 0.0, ms = 0.0;
-    double* pms = elapsed_ms ? &ms : nullptr;
-    // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
-    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    LegTimer leg(elapsed_ms);
+    double* pms = leg.pms();
     for (int j = 0; j < J; j++) {
         const double sx = meas_xy[2 * j], sy = meas_xy[2 * j + 1];
         const int k = *known;
@@ -413,16 +410,6 @@ void joint_correct_launch(ekf_dense64_s* d, const ekf::Params& p, const JointVie
     correct_sparse_launch(d, deferred, 2 * V, 3 + 2 * V, true);
     ekf::launch_dense64_lm_wrap(d->x, view(d->corr_out, L::corr_out_layout()).verdict, d->stream);   // :187 / :385
 }
-
-// the legs of a call with several synchronisations: behind each one the time between its events (0 when it failed before
-// reading them) joins the total, which *out (nullable; on entry the time of what ran before) follows
-struct LegTimer {
-    double* out;
-    double total, ms = 0.0;
-    explicit LegTimer(double* elapsed_ms) : out(elapsed_ms), total(elapsed_ms ? *elapsed_ms : 0.0) {}
-    double* pms() { return out ? &ms : nullptr; }
-    ekf_status operator()(ekf_status st) { total += ms; ms = 0.0; if (out) *out = total; return st; }
-};
 
 // Steps 4 LIVE, 5 INIT and 6 CORRECT of THE JOINT RULE (include/ekfslam.h) on a decision that is made: rec [J] the final
 // records (kind, win) on the host, n_new and n_pairs their counts, and on the device what k_djt_resolve leaves (jv.xb,
@@ -667,6 +654,125 @@ ekf_status associate_jcbb(ekf_dense64_s* d, const char* fnc, const ekf::Params& 
 ekf_status associate_jcbb_reserve(ekf_dense64_s* d, const char* fnc, int J, int n_max, bool deferred) {
     EKFC(associate_joint_reserve(d, fnc, J, n_max, deferred));
     return jcbb_reserve(d, fnc);
+}
+
+// ---- the six association entry points: a rule, and the readings form or the scan form of it ------------------------------
+// What tells the three rules apart in front of their run.  The jcbb members are the caller's arguments, unused by the others.
+enum class Rule { kSequential, kJoint, kJcbb };
+constexpr unsigned kLmFlags = EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE;
+struct AssocRule {
+    Rule rule;
+    int max_readings;    // the most readings a call takes (the scan form: at most a scan's circles)
+    unsigned allowed;    // the flag bits the call knows
+    bool n_max_capped;   // n_max <= 32768: a scoring launch holds every landmark against one reading
+    double gate_ic = 0.0;
+    const double* gate_joint = nullptr;
+    long long max_nodes = 0;
+    ekf_dense64_jcbb_report* report = nullptr;
+};
+static_assert(kJointReadings == kScanClusters && kJointReadings == 128 && kJcbbReadings == 32, "the texts of the range checks");
+
+// the argument checks in their documented order, behind the call's own (null pointers, the range of J or of the scan);
+// J: the readings the call may come to have
+ekf_status assoc_checks(ekf_dense64_s* d, const std::string& fn, const AssocRule& r, const ekf::Params& p, int J, int n_max,
+                        const int* known, unsigned flags) {
+    if (n_max < 0 || 3 + 2 * (long long)n_max > d->N)
+        return fail(EKF_ERR_INVALID, fn + ": n_max must lie in [0, (N - 3) / 2]");
+    if (*known < 0 || *known > n_max) return fail(EKF_ERR_INVALID, fn + ": *known must lie in [0, n_max]");
+    if (3 + 2 * *known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
+    EKFC(lm_flags_ok(fn, flags, r.allowed));
+    if (r.n_max_capped && n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
+    if (r.rule == Rule::kJcbb) EKFC(jcbb_gates_ok(fn, p, J, r.gate_ic, r.gate_joint, r.max_nodes));
+    return EKF_OK;
+}
+
+// what the rule needs in memory for up to J readings
+ekf_status assoc_reserve(ekf_dense64_s* d, const char* fnc, const AssocRule& r, int J, int n_max, bool deferred) {
+    switch (r.rule) {
+        case Rule::kSequential: return associate_reserve(d, fnc, n_max, deferred);
+        case Rule::kJoint: return associate_joint_reserve(d, fnc, J, n_max, deferred);
+        default: return associate_jcbb_reserve(d, fnc, J, n_max, deferred);
+    }
+}
+
+// the rule on J readings; *elapsed_ms (nullable) holds the time of what ran before
+ekf_status assoc_run(ekf_dense64_s* d, const char* fnc, const AssocRule& r, const ekf::Params& p, int J, const double* xy,
+                     int n_max, int* known, unsigned flags, int* assoc_out, double* best_out, int* n_groups_out,
+                     double* elapsed_ms) {
+    switch (r.rule) {
+        case Rule::kSequential:
+            return associate_readings(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
+        case Rule::kJoint:
+            return associate_joint(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, n_groups_out, elapsed_ms);
+        default:
+            return associate_jcbb(d, fnc, p, J, xy, n_max, known, r.gate_ic, r.gate_joint, r.max_nodes, flags, assoc_out,
+                                  best_out, r.report, n_groups_out, elapsed_ms);
+    }
+}
+
+// Both forms between their own checks and their first launch: the remaining checks, behind the last of them the presets of
+// every output (a refused call has written to none), the device, the memory for `cap` readings.
+ekf_status assoc_begin(ekf_dense64_s* d, const char* fnc, const AssocRule& r, const ekf::Params& p, int cap, int n_max,
+                       const int* known, unsigned flags, int* count_out, double* centres_out, int* assoc_out,
+                       double* best_out, int* n_groups_out, double* elapsed_ms) {
+    EKFC(assoc_checks(d, fnc, r, p, cap, n_max, known, flags));
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    if (count_out) *count_out = 0;
+    if (n_groups_out) *n_groups_out = 0;
+    if (r.report) *r.report = ekf_dense64_jcbb_report{0, 0, 0, 0, 0, 0, 0.0};
+    for (int j = 0; j < cap; j++) {
+        if (assoc_out) assoc_out[j] = -2;
+        if (best_out) best_out[j] = p.gate_new;
+        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
+    }
+    HIPC(hipSetDevice(d->device));
+    return assoc_reserve(d, fnc, r, cap, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0);
+}
+
+// The readings form: J readings from the caller.  The sequential rule without the Joseph form is inside a region's terms.
+ekf_status assoc_readings_form(ekf_dense64_s* d, const char* fnc, const AssocRule& r, const ekf_params* params, int J,
+                               const double* meas_xy, int n_max, int* known, unsigned flags, int* assoc_out,
+                               double* best_out, int* n_groups_out, double* elapsed_ms) {
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const bool in_terms = r.rule == Rule::kSequential && !(flags & EKF_DENSE64_LM_JOSEPH);
+    const RegionLeave leaving(in_terms ? nullptr : d);   // outside a region's terms: it ends behind this call's checks and e0
+    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (J < 1 || J > r.max_readings)
+        return fail(EKF_ERR_INVALID, fn + (r.max_readings == INT_MAX         ? ": J must be at least 1"
+                                           : r.max_readings == kJcbbReadings ? ": J must lie in [1, 32]"
+                                                                             : ": J must lie in [1, 128]"));
+    const ekf::Params p = landmark_params(params);
+    EKFC(assoc_begin(d, fnc, r, p, J, n_max, known, flags, nullptr, nullptr, assoc_out, best_out, n_groups_out, elapsed_ms));
+    return assoc_run(d, fnc, r, p, J, meas_xy, n_max, known, flags, assoc_out, best_out, n_groups_out, elapsed_ms);
+}
+
+// The scan form: ekf_dense64_fit_scan, then the rule on the first min(count, max_readings) centres.  Checked and reserved
+// for max_readings, whatever the scan turns out to hold; the fit's time is the first leg of *elapsed_ms.
+ekf_status assoc_scan_form(ekf_dense64_s* d, const char* fnc, const AssocRule& r, const ekf_params* params,
+                           const double* ranges, int n_beams, int max_readings, int n_max, int* known, unsigned flags,
+                           int* count_out, double* centres_out, int* assoc_out, double* best_out, double* elapsed_ms) {
+    const std::string fn = fnc;
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    const int most = std::min(r.max_readings, kScanClusters);
+    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > most)
+        return fail(EKF_ERR_INVALID, fn + (most == kJcbbReadings ? ": n_beams must lie in [1, 1024] and max_readings in [1, 32]"
+                                                                 : ": n_beams must lie in [1, 1024] and max_readings in [1, 128]"));
+    const ekf::Params p = landmark_params(params);
+    EKFC(assoc_begin(d, fnc, r, p, max_readings, n_max, known, flags, count_out, centres_out, assoc_out, best_out, nullptr,
+                     elapsed_ms));
+    ScanRecord rec{};
+    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
+    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
+    *count_out = J;
+    if (J == 0) return EKF_OK;
+    double xy[2 * kScanClusters];   // the rule's launches leave d->scan_rec alone; a copy keeps that out of the argument
+    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
+    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
+    return assoc_run(d, fnc, r, p, J, xy, n_max, known, flags, assoc_out, best_out, nullptr, elapsed_ms);
 }
 
 }  // namespace
@@ -1673,9 +1779,8 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     HIPC(hipSetDevice(d->device));
     if (deferred) EKFC(pend_reserve(d, fnc));
     const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
-    double total = 0.0, ms = 0.0;
-    double* pms = elapsed_ms ? &ms : nullptr;
-    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    LegTimer leg(elapsed_ms);
+    double* pms = leg.pms();
     HIPC(hipEventRecord(d->e0, d->stream));
     d->finish_leave();   // (a region that is being left ends here)
     ekf::launch_dense64_pair_terms(d->x, lo, hi, r_merge, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
@@ -1724,23 +1829,9 @@ ekf_status ekf_dense64_score_landmarks(ekf_dense64_handle d, const ekf_params* p
 ekf_status ekf_dense64_associate_landmarks(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy,
                                            int n_max, int* known, unsigned flags, int* assoc_out, double* best_out,
                                            double* elapsed_ms) {
-    const char* fnc = "ekf_dense64_associate_landmarks";
-    const std::string fn = fnc;
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    const RegionLeave leaving((flags & EKF_DENSE64_LM_JOSEPH) ? d : nullptr);   // the Joseph form is outside a region's terms
-    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
-    if (J < 1) return fail(EKF_ERR_INVALID, fn + ": J must be at least 1");
-    EKFC(associate_checks(d, fn, n_max, known, flags,
-                          EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE | EKF_DENSE64_LM_JOSEPH));
-    const ekf::Params p = landmark_params(params);
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    for (int j = 0; j < J; j++) {
-        if (assoc_out) assoc_out[j] = -2;
-        if (best_out) best_out[j] = p.gate_new;
-    }
-    HIPC(hipSetDevice(d->device));
-    EKFC(associate_reserve(d, fnc, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
-    return associate_readings(d, fnc, p, J, meas_xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
+    const AssocRule r{Rule::kSequential, INT_MAX, kLmFlags | EKF_DENSE64_LM_JOSEPH, false};
+    return assoc_readings_form(d, "ekf_dense64_associate_landmarks", r, params, J, meas_xy, n_max, known, flags, assoc_out,
+                               best_out, nullptr, elapsed_ms);
 }
 
 // ---- a laser scan as the handle's input --------------------------------------------------------------------------------
@@ -1771,33 +1862,9 @@ ekf_status ekf_dense64_fit_scan(ekf_dense64_handle d, const double* ranges, int 
 ekf_status ekf_dense64_associate_scan(ekf_dense64_handle d, const ekf_params* params, const double* ranges, int n_beams,
                                       int max_readings, int n_max, int* known, unsigned flags, int* count_out,
                                       double* centres_out, int* assoc_out, double* best_out, double* elapsed_ms) {
-    const char* fnc = "ekf_dense64_associate_scan";
-    const std::string fn = fnc;
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
-    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
-    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kScanClusters)
-        return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 128]");
-    EKFC(associate_checks(d, fn, n_max, known, flags));
-    const ekf::Params p = landmark_params(params);
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    *count_out = 0;
-    for (int j = 0; j < max_readings; j++) {
-        if (assoc_out) assoc_out[j] = -2;
-        if (best_out) best_out[j] = p.gate_new;
-        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
-    }
-    HIPC(hipSetDevice(d->device));
-    EKFC(associate_reserve(d, fnc, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
-    ScanRecord rec{};
-    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
-    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
-    *count_out = J;
-    if (J == 0) return EKF_OK;
-    double xy[2 * kScanClusters];   // the loop's launches leave d->scan_rec alone; a copy keeps that out of the argument
-    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
-    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
-    return associate_readings(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, elapsed_ms);
+    const AssocRule r{Rule::kSequential, INT_MAX, kLmFlags, false};
+    return assoc_scan_form(d, "ekf_dense64_associate_scan", r, params, ranges, n_beams, max_readings, n_max, known, flags,
+                           count_out, centres_out, assoc_out, best_out, elapsed_ms);
 }
 
 // ---- a whole scan at once: every reading against one state, one assignment, one stacked correction ----------------------
@@ -1874,24 +1941,9 @@ ekf_status ekf_dense64_joint_operands(ekf_dense64_handle d, const ekf_params* pa
 ekf_status ekf_dense64_associate_joint(ekf_dense64_handle d, const ekf_params* params, int J, const double* meas_xy,
                                        int n_max, int* known, unsigned flags, int* assoc_out, double* best_out,
                                        int* n_groups_out, double* elapsed_ms) {
-    const char* fnc = "ekf_dense64_associate_joint";
-    const std::string fn = fnc;
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
-    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
-    if (J < 1 || J > kJointReadings) return fail(EKF_ERR_INVALID, fn + ": J must lie in [1, 128]");
-    EKFC(associate_checks(d, fn, n_max, known, flags));
-    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
-    const ekf::Params p = landmark_params(params);
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_groups_out) *n_groups_out = 0;
-    for (int j = 0; j < J; j++) {
-        if (assoc_out) assoc_out[j] = -2;
-        if (best_out) best_out[j] = p.gate_new;
-    }
-    HIPC(hipSetDevice(d->device));
-    EKFC(associate_joint_reserve(d, fnc, J, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
-    return associate_joint(d, fnc, p, J, meas_xy, n_max, known, flags, assoc_out, best_out, n_groups_out, elapsed_ms);
+    const AssocRule r{Rule::kJoint, kJointReadings, kLmFlags, true};
+    return assoc_readings_form(d, "ekf_dense64_associate_joint", r, params, J, meas_xy, n_max, known, flags, assoc_out,
+                               best_out, n_groups_out, elapsed_ms);
 }
 
 // ekf_dense64_fit_scan, then the path of ekf_dense64_associate_joint on the first min(count, max_readings) centres
@@ -1899,34 +1951,9 @@ ekf_status ekf_dense64_associate_scan_joint(ekf_dense64_handle d, const ekf_para
                                             int n_beams, int max_readings, int n_max, int* known, unsigned flags,
                                             int* count_out, double* centres_out, int* assoc_out, double* best_out,
                                             double* elapsed_ms) {
-    const char* fnc = "ekf_dense64_associate_scan_joint";
-    const std::string fn = fnc;
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
-    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
-    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kScanClusters)
-        return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 128]");
-    EKFC(associate_checks(d, fn, n_max, known, flags));
-    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
-    const ekf::Params p = landmark_params(params);
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    *count_out = 0;
-    for (int j = 0; j < max_readings; j++) {
-        if (assoc_out) assoc_out[j] = -2;
-        if (best_out) best_out[j] = p.gate_new;
-        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
-    }
-    HIPC(hipSetDevice(d->device));
-    EKFC(associate_joint_reserve(d, fnc, max_readings, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
-    ScanRecord rec{};
-    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
-    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
-    *count_out = J;
-    if (J == 0) return EKF_OK;
-    double xy[2 * kScanClusters];
-    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
-    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
-    return associate_joint(d, fnc, p, J, xy, n_max, known, flags, assoc_out, best_out, nullptr, elapsed_ms);
+    const AssocRule r{Rule::kJoint, kJointReadings, kLmFlags, true};
+    return assoc_scan_form(d, "ekf_dense64_associate_scan_joint", r, params, ranges, n_beams, max_readings, n_max, known,
+                           flags, count_out, centres_out, assoc_out, best_out, elapsed_ms);
 }
 
 // ---- joint compatibility: the candidates and their cross blocks on the device, the search on the host -------------------
@@ -2000,27 +2027,9 @@ ekf_status ekf_dense64_associate_jcbb(ekf_dense64_handle d, const ekf_params* pa
                                       int* known, double gate_ic, const double* gate_joint, long long max_nodes,
                                       unsigned flags, int* assoc_out, double* best_out, ekf_dense64_jcbb_report* report,
                                       int* n_groups_out, double* elapsed_ms) {
-    const char* fnc = "ekf_dense64_associate_jcbb";
-    const std::string fn = fnc;
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
-    if (!known || !meas_xy) return fail(EKF_ERR_INVALID, fn + ": null argument");
-    if (J < 1 || J > kJcbbReadings) return fail(EKF_ERR_INVALID, fn + ": J must lie in [1, 32]");
-    EKFC(associate_checks(d, fn, n_max, known, flags));
-    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
-    const ekf::Params p = landmark_params(params);
-    EKFC(jcbb_gates_ok(fn, p, J, gate_ic, gate_joint, max_nodes));
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    if (n_groups_out) *n_groups_out = 0;
-    if (report) *report = ekf_dense64_jcbb_report{0, 0, 0, 0, 0, 0, 0.0};
-    for (int j = 0; j < J; j++) {
-        if (assoc_out) assoc_out[j] = -2;
-        if (best_out) best_out[j] = p.gate_new;
-    }
-    HIPC(hipSetDevice(d->device));
-    EKFC(associate_jcbb_reserve(d, fnc, J, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
-    return associate_jcbb(d, fnc, p, J, meas_xy, n_max, known, gate_ic, gate_joint, max_nodes, flags, assoc_out, best_out, report,
-                          n_groups_out, elapsed_ms);
+    const AssocRule r{Rule::kJcbb, kJcbbReadings, kLmFlags, true, gate_ic, gate_joint, max_nodes, report};
+    return assoc_readings_form(d, "ekf_dense64_associate_jcbb", r, params, J, meas_xy, n_max, known, flags, assoc_out,
+                               best_out, n_groups_out, elapsed_ms);
 }
 
 // ekf_dense64_fit_scan, then the path of ekf_dense64_associate_jcbb on the first min(count, max_readings) centres
@@ -2029,37 +2038,9 @@ ekf_status ekf_dense64_associate_scan_jcbb(ekf_dense64_handle d, const ekf_param
                                            long long max_nodes, unsigned flags, int* count_out, double* centres_out,
                                            int* assoc_out, double* best_out, ekf_dense64_jcbb_report* report,
                                            double* elapsed_ms) {
-    const char* fnc = "ekf_dense64_associate_scan_jcbb";
-    const std::string fn = fnc;
-    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
-    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
-    if (!ranges || !count_out || !known) return fail(EKF_ERR_INVALID, fn + ": null argument");
-    if (n_beams < 1 || n_beams > kScanBeams || max_readings < 1 || max_readings > kJcbbReadings)
-        return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024] and max_readings in [1, 32]");
-    EKFC(associate_checks(d, fn, n_max, known, flags));
-    if (n_max > kSparseRows / 2) return fail(EKF_ERR_INVALID, fn + ": n_max must not exceed 32768");
-    const ekf::Params p = landmark_params(params);
-    EKFC(jcbb_gates_ok(fn, p, max_readings, gate_ic, gate_joint, max_nodes));
-    if (elapsed_ms) *elapsed_ms = 0.0;
-    *count_out = 0;
-    if (report) *report = ekf_dense64_jcbb_report{0, 0, 0, 0, 0, 0, 0.0};
-    for (int j = 0; j < max_readings; j++) {
-        if (assoc_out) assoc_out[j] = -2;
-        if (best_out) best_out[j] = p.gate_new;
-        if (centres_out) centres_out[2 * j] = centres_out[2 * j + 1] = 0.0;
-    }
-    HIPC(hipSetDevice(d->device));
-    EKFC(associate_jcbb_reserve(d, fnc, max_readings, n_max, (flags & EKF_DENSE64_LM_DEFERRED) != 0));
-    ScanRecord rec{};
-    EKFC(scan_fit(d, fnc, ranges, n_beams, max_readings, false, elapsed_ms, &rec));
-    const int J = rec.count;   // (the kernel keeps the first max_readings circles in cluster order)
-    *count_out = J;
-    if (J == 0) return EKF_OK;
-    double xy[2 * kJcbbReadings];
-    std::memcpy(xy, rec.centres, sizeof(double) * 2 * J);
-    if (centres_out) std::memcpy(centres_out, xy, sizeof(double) * 2 * J);
-    return associate_jcbb(d, fnc, p, J, xy, n_max, known, gate_ic, gate_joint, max_nodes, flags, assoc_out, best_out, report,
-                          nullptr, elapsed_ms);
+    const AssocRule r{Rule::kJcbb, kJcbbReadings, kLmFlags, true, gate_ic, gate_joint, max_nodes, report};
+    return assoc_scan_form(d, "ekf_dense64_associate_scan_jcbb", r, params, ranges, n_beams, max_readings, n_max, known,
+                           flags, count_out, centres_out, assoc_out, best_out, elapsed_ms);
 }
 
 // ---- the reference's prediction() and measurement() on the handle's own state ------------------------------------------
@@ -2108,10 +2089,8 @@ ekf_status ekf_dense64_measure_landmarks(ekf_dense64_handle d, const ekf_params*
     const LmMeasureView mv = view(d->sps.p, l);
     const CorrSparseView cin = view(d->corr_in, L::corr_sparse_layout(d->ld));
     if (init) HIPC(hipMemcpyAsync(mv.xy, sensor_xy, sizeof(double) * 2 * n_lm, hipMemcpyHostToDevice, d->stream));
-    double total = 0.0, ms = 0.0;
-    double* pms = elapsed_ms ? &ms : nullptr;
-    // behind each synchronisation: the time between its events (0 when it failed before reading them) joins the total
-    auto leg = [&](ekf_status st) { total += ms; ms = 0.0; if (elapsed_ms) *elapsed_ms = total; return st; };
+    LegTimer leg(elapsed_ms);
+    double* pms = leg.pms();
     HIPC(hipEventRecord(d->e0, d->stream));
     d->finish_leave();   // (a region that is being left ends here)
     ekf::launch_dense64_model_snapshot(d->x, mv.pose, d->stream);                        // :109-111

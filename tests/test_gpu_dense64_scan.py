@@ -289,6 +289,68 @@ def test_scan_refusals_change_nothing(hip):
     d.close(); ref.close()
 
 
+def test_joseph_flag_is_known_to_associate_landmarks_alone(hip):
+    """EKF_DENSE64_LM_JOSEPH through the C ABI of all six association calls, each on a fresh handle (N = 23, 4 known
+    landmarks, 2 rows pending) with otherwise valid arguments (J = 1; a 360-beam scan with one circle): associate_landmarks
+    takes it, to the other five it is an unknown bit, and their refusal leaves state, Sigma, the pending count and every
+    output as they were"""
+    n, known0, OK = 10, 4, 0
+    x, S = lc.spiral_map(n)
+    x[3:5] = x[:3][1:] + np.array([1.25, 0.0])
+    scan = sc.circles_scan(1)
+    ref = _handle(hip, x, S, 2)
+    cen, _, _ = ref.fit_scan(scan)
+    assert len(cen) == 1
+    want = _snapshot(ref)
+    ref.close()
+    joseph = hip.DensePropagator64.LM_JOSEPH
+    r = (C.c_double * 360)(*scan)
+    z = (C.c_double * 2)(*cen[0])
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+
+    def outputs():
+        """every output preset to a value no call writes"""
+        return {"known": C.c_int(known0), "count": C.c_int(-7), "groups": C.c_int(-7), "ms": C.c_double(-7.0),
+                "centres": np.full((32, 2), -7.0), "assoc": np.full(32, -7, dtype=np.int32), "best": np.full(32, -7.0),
+                "report": hip.JcbbReport(-7, -7, -7, -7, -7, -7, -7.0)}
+
+    def frozen(o):
+        return [v.tobytes() if isinstance(v, np.ndarray) else bytes(v) for v in o.values()]
+
+    def readings(name, jcbb, groups):
+        def call(lib, h, o):
+            tail = ([C.byref(o["report"])] if jcbb else []) + ([C.byref(o["groups"])] if groups else [])
+            return getattr(lib, name)(h, None, 1, z, n, C.byref(o["known"]), *((1.0, None, 1 << 10) if jcbb else ()), joseph,
+                                      o["assoc"].ctypes.data_as(ip), o["best"].ctypes.data_as(dp), *tail, C.byref(o["ms"]))
+        return call
+
+    def scans(name, jcbb):
+        def call(lib, h, o):
+            return getattr(lib, name)(h, None, r, 360, 32, n, C.byref(o["known"]), *((1.0, None, 1 << 10) if jcbb else ()),
+                                      joseph, C.byref(o["count"]), o["centres"].ctypes.data_as(dp),
+                                      o["assoc"].ctypes.data_as(ip), o["best"].ctypes.data_as(dp),
+                                      *([C.byref(o["report"])] if jcbb else []), C.byref(o["ms"]))
+        return call
+
+    d = _handle(hip, x, S, 2)
+    o = outputs()
+    st = readings("ekf_dense64_associate_landmarks", False, False)(d._lib, d._h, o)
+    assert st == OK, (st, d._lib.ekf_last_error())
+    assert o["assoc"][0] != -7 and o["best"][0] != -7.0 and o["ms"].value >= 0.0   # the call ran: its outputs are written
+    d.close()
+    for call in (scans("ekf_dense64_associate_scan", False), readings("ekf_dense64_associate_joint", False, True),
+                 scans("ekf_dense64_associate_scan_joint", False), readings("ekf_dense64_associate_jcbb", True, True),
+                 scans("ekf_dense64_associate_scan_jcbb", True)):
+        d = _handle(hip, x, S, 2)
+        o = outputs()
+        before = frozen(o)
+        st, text = call(d._lib, d._h, o), d._lib.ekf_last_error()
+        assert st == INVALID and b"unknown flag bits" in text, (st, text)
+        assert frozen(o) == before
+        _same(_snapshot(d), want)
+        d.close()
+
+
 # ---- 7. the two nodes of the reference, end to end ---------------------------------------------------------------------------
 
 def test_scan_to_filter_pipeline(hip, oracle):
