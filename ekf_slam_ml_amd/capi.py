@@ -61,6 +61,8 @@ SYMBOLS = [
     "ekf_dense64_region_begin", "ekf_dense64_region_end", "ekf_dense64_region_info", "ekf_dense64_region_launch_info",
     "ekf_dense64_get_padded",
     "ekf_dense64_pairs_launch_info", "ekf_dense64_score_landmark_pairs", "ekf_dense64_merge_landmarks",
+    "ekf_dense64_remove_landmark",
+    "ekf_dense64_evidence_launch_info", "ekf_dense64_scan_evidence", "ekf_dense64_evidence_update",
     "ekf_dense64_health_launch_info", "ekf_dense64_health", "ekf_dense64_symmetrize",
     "ekf_dense64_value_launch_info", "ekf_dense64_value_operands", "ekf_dense64_rank_landmarks",
     "ekf_dense64_factor_launch_info", "ekf_dense64_factor", "ekf_dense64_get_factor", "ekf_dense64_whiten",
@@ -110,6 +112,42 @@ class ValueBest(C.Structure):
     """ekf_dense64_value_best (include/ekfslam.h)"""
     _fields_ = [("i_trace", C.c_int), ("i_pose", C.c_int), ("i_det", C.c_int), ("reserved", C.c_int),
                 ("v_trace", C.c_double), ("v_pose", C.c_double), ("v_det", C.c_double)]
+
+
+class EvidenceReport(C.Structure):
+    """ekf_dense64_evidence_report (include/ekfslam.h)"""
+    _fields_ = [("n_candidates", C.c_int), ("n_on_tube", C.c_int), ("n_unexplained", C.c_int), ("n_invalid", C.c_int)]
+
+
+class ScanEvidence:
+    """What scan_evidence() returns: per landmark n_expected, n_agree, n_through, n_short (count,) int32 and tol (count,);
+    per beam expected (n_beams,), hit (n_beams,) int32 (the landmark index, -1 for the wall or range_max) and cls
+    (n_beams,) uint8 (0 wall / range_max, 1 agree, 2 through, 3 short, 4 invalid); report = {n_candidates, n_on_tube,
+    n_unexplained, n_invalid}; first_lm; ms."""
+
+    def __init__(self, first_lm, n_expected, n_agree, n_through, n_short, tol, expected, hit, cls, report, ms):
+        self.first_lm, self.n_expected, self.n_agree, self.n_through, self.n_short = first_lm, n_expected, n_agree, n_through, n_short
+        self.tol, self.expected, self.hit, self.cls, self.ms = tol, expected, hit, cls, ms
+        self.report = {name: getattr(report, name) for name, _ in EvidenceReport._fields_}
+
+
+def evidence_update(logodds, n_expected, n_agree, n_through, min_beams=3, w_hit=0.4, w_miss=0.85, l_min=-4.0, l_max=4.0):
+    """ekf_dense64_evidence_update (no handle, no device): per landmark with n_expected >= min_beams a hit (2 n_agree >=
+    n_expected: l += w_hit) or a miss (2 n_through > n_expected: l -= w_miss), then the clamp to [l_min, l_max].  logodds
+    (count,) float64 is updated IN PLACE; returns verdict (count,) int32: +1 hit, -1 miss, 0 neither."""
+    if not (isinstance(logodds, np.ndarray) and logodds.dtype == np.float64 and logodds.ndim == 1 and logodds.flags.c_contiguous):
+        raise ValueError("logodds must be a contiguous float64 array of one dimension (it is updated in place)")
+    n = logodds.shape[0]
+    cnt = [np.ascontiguousarray(a, dtype=np.int32) for a in (n_expected, n_agree, n_through)]
+    if any(a.shape != (n,) for a in cnt):
+        raise ValueError("the counters must hold one entry per log-odds value")
+    verdict = np.zeros(n, dtype=np.int32)
+    if n == 0:
+        return verdict
+    _check(load().ekf_dense64_evidence_update(n, cnt[0].ctypes.data_as(_ip), cnt[1].ctypes.data_as(_ip),
+                                              cnt[2].ctypes.data_as(_ip), int(min_beams), float(w_hit), float(w_miss),
+                                              float(l_min), float(l_max), _d(logodds), verdict.ctypes.data_as(_ip)))
+    return verdict
 
 
 class ObservationValue:
@@ -329,6 +367,12 @@ def load():
         "ekf_dense64_score_landmark_pairs": [h, C.c_int, C.c_double, C.c_double, _ip, _dp, C.POINTER(C.c_longlong),
                                              C.POINTER(C.c_longlong), _dp],
         "ekf_dense64_merge_landmarks": [h, C.POINTER(Params), C.c_int, C.c_int, C.c_double, _ip, C.c_int, _ip, _dp, _dp],
+        "ekf_dense64_remove_landmark": [h, C.POINTER(Params), C.c_int, _ip, C.c_uint, _ip, _dp],
+        "ekf_dense64_evidence_launch_info": [h, _ip, _ip, _ip],
+        "ekf_dense64_scan_evidence": [h, C.POINTER(Params), C.POINTER(LidarParams), _dp, C.c_int, C.c_int, C.c_double,
+                                      C.c_double, _ip, _ip, _ip, _ip, _dp, _dp, _ip, _bp, C.POINTER(EvidenceReport), _dp],
+        "ekf_dense64_evidence_update": [C.c_int, _ip, _ip, _ip, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        _dp, _ip],
         "ekf_dense64_health_launch_info": [h, _ip, _ip],
         "ekf_dense64_health": [h, C.POINTER(HealthReport), _dp],
         "ekf_dense64_symmetrize": [h, C.POINTER(C.c_longlong), _dp, _dp],
@@ -1274,6 +1318,59 @@ class DensePropagator64(_DensePropagatorBase):
                                                      C.byref(k), flags, C.byref(moved), C.byref(d2), C.byref(ms)))
         return k.value, moved.value, d2.value, ms.value
 
+    def remove_landmark(self, i, known, flags=0, params=None):
+        """Remove landmark i of the `known` ones, the removal half of merge_landmarks(): swap_blocks(i, last) unless i is
+        the last, init_block(last, W = sigma0 I) and known - 1; with LM_GROW_LIVE (the only flag) also live = 3 + 2 known.
+        Bit for bit that sequence spelled.  Returns (known, moved_from: the old index of the landmark that now sits in
+        slot i, or -1; elapsed_ms)."""
+        i, known, flags = int(i), int(known), int(flags)
+        if not 0 <= known <= (self.N - 3) // 2:
+            raise ValueError("0 <= known <= (N - 3) // 2")
+        if not 0 <= i < known:
+            raise ValueError("i must be a landmark in [0, known)")
+        if flags & ~self.LM_GROW_LIVE:
+            raise ValueError("flags: LM_GROW_LIVE")
+        k, moved, ms = C.c_int(known), C.c_int(-1), C.c_double()
+        _check(self._lib.ekf_dense64_remove_landmark(self._h, C.byref(params) if params is not None else None, i,
+                                                     C.byref(k), flags, C.byref(moved), C.byref(ms)))
+        return k.value, moved.value, ms.value
+
+    def evidence_launch_info(self):
+        """{beam_tile, lm_chunk, threads}: the beams of a workgroup of scan_evidence(), the candidates it stages in LDS at
+        a time and its workgroup size (test hook)"""
+        self._open()
+        bt, lc, th = C.c_int(), C.c_int(), C.c_int()
+        _check(self._lib.ekf_dense64_evidence_launch_info(self._h, C.byref(bt), C.byref(lc), C.byref(th)))
+        return {"beam_tile": bt.value, "lm_chunk": lc.value, "threads": th.value}
+
+    def scan_evidence(self, ranges, lidar=None, first_lm=0, count=None, tol_abs=0.05, kappa=2.0, params=None):
+        """One scan cast against the handle's own map (ekf_dense64_scan_evidence, include/ekfslam.h): per beam the range
+        the landmarks [first_lm, first_lm + count) predict (clean ray geometry of `lidar`, default_lidar() if None) and
+        the landmark it should stop on; per landmark how many of its beams agree with `ranges`, went through it, stopped
+        short of it, under tol = tol_abs + kappa sqrt(range variance of the landmark under Sigma).  ranges None: the
+        expected scan only (lidar.n_beams beams).  count None: every landmark from first_lm inside the live dimension.
+        Read-only, nothing is flushed.  Returns a ScanEvidence."""
+        self._open()
+        lp = lidar if lidar is not None else default_lidar()
+        if ranges is not None:
+            r = self._scan(ranges)
+            if r.shape[0] != lp.n_beams:
+                if lidar is not None:
+                    raise ValueError("ranges must hold lidar.n_beams beams")
+                lp.n_beams = r.shape[0]
+        first_lm, count = self._value_range(first_lm, count)
+        n, nb = max(count, 0), max(min(int(lp.n_beams), self.SCAN_MAX_BEAMS), 0)
+        ne, na, nt, ns = (np.zeros(n, dtype=np.int32) for _ in range(4))
+        tol, exp = np.empty(n, dtype=np.float64), np.empty(nb, dtype=np.float64)
+        hit, cls = np.empty(nb, dtype=np.int32), np.empty(nb, dtype=np.uint8)
+        rep, ms = EvidenceReport(), C.c_double()
+        _check(self._lib.ekf_dense64_scan_evidence(
+            self._h, C.byref(params) if params is not None else None, C.byref(lp), _d(r) if ranges is not None else None,
+            first_lm, count, float(tol_abs), float(kappa), ne.ctypes.data_as(_ip), na.ctypes.data_as(_ip),
+            nt.ctypes.data_as(_ip), ns.ctypes.data_as(_ip), _d(tol), _d(exp), hit.ctypes.data_as(_ip),
+            cls.ctypes.data_as(_bp), C.byref(rep), C.byref(ms)))
+        return ScanEvidence(first_lm, ne, na, nt, ns, tol, exp, hit, cls, rep, ms.value)
+
     def _open(self):
         if not getattr(self, "_h", None):
             raise ValueError("the handle is closed")
@@ -2160,6 +2257,8 @@ class DenseEKFSLAM:
         d.live = 3 if self.grow_live else 3 + 2 * self.n
         self._known, self._init_flag = 0, False
         self.jcbb_report = None   # the report of the last jcbb_association() / scan_association(joint="jcbb")
+        self._logodds = np.zeros(0, dtype=np.float64)   # scan_evidence()'s verdicts so far, one per mapped landmark
+        self.evidence = None      # the ScanEvidence of the last scan_evidence() / scan_association(evidence=True)
 
     def close(self):
         self.handle.close()
@@ -2215,10 +2314,18 @@ class DenseEKFSLAM:
             raise
         return assoc
 
-    def scan_association(self, ranges, joint=False):
+    def scan_association(self, ranges, joint=False, evidence=False, lidar=None):
         """one LaserScan through the landmarks node (circle fitting) into data_association() -- or, with joint=True, into
         joint_association(), with joint="jcbb" into jcbb_association() (at most 32 circles, the default gates) -- in one
-        call; returns (centres (k, 2), assoc (k,) int32) of the k circles found"""
+        call; returns (centres (k, 2), assoc (k,) int32) of the k circles found.  evidence=True: scan_evidence(ranges,
+        lidar) with its defaults runs behind the association, on the corrected map (lidar: the sensor's LidarParams,
+        default_lidar() -- with its square wall -- if None; evidence=False: today's launches and nothing else)"""
+        out = self._scan_association(ranges, joint)
+        if evidence:
+            self.scan_evidence(ranges, lidar)
+        return out
+
+    def _scan_association(self, ranges, joint):
         if isinstance(joint, str):
             if joint != "jcbb":
                 raise ValueError('joint must be False, True or "jcbb"')
@@ -2262,8 +2369,82 @@ class DenseEKFSLAM:
         """fuse the known landmarks a and b and remove the higher (merge_landmarks on the object's paths); the last known
         landmark moves into its slot.  Returns (moved_from, d2)"""
         flags = self.handle._lm_flags(self.deferred, self.grow_live, self.joseph)
+        l = self.logodds
         self._known, moved, d2, _ = self.handle.merge_landmarks(a, b, r_merge, self._known, flags, self.params)
+        self._logodds_removed(l, max(int(a), int(b)), moved)
         return moved, d2
+
+    # ---- scan evidence: which landmark is spurious -----------------------------------------------------------------------
+    @property
+    def logodds(self):
+        """(mapped landmarks,) float64: the log-odds scan_evidence() keeps per landmark, 0 for one it has not judged yet.
+        The array is the object's own and follows the landmarks through merge(), remove(), prune(), join(), clone() and
+        submap()."""
+        k = self._mapped()
+        if self._logodds.shape[0] != k:
+            grown = np.zeros(k, dtype=np.float64)
+            m = min(k, self._logodds.shape[0])
+            grown[:m] = self._logodds[:m]
+            self._logodds = grown
+        return self._logodds
+
+    def _logodds_removed(self, l, slot, moved):
+        """the bookkeeping of a removal: the landmark `moved` (the old last one, -1: none) sits in `slot`, the last is gone"""
+        if moved >= 0:
+            l[slot] = l[moved]
+        self._logodds = l[:-1].copy()
+
+    def scan_evidence(self, ranges, lidar=None, tol_abs=0.05, kappa=2.0, min_beams=3, w_hit=0.4, w_miss=0.85,
+                      l_min=-4.0, l_max=4.0):
+        """one LaserScan cast against the map (DensePropagator64.scan_evidence over the mapped landmarks) and its verdicts
+        added to .logodds (evidence_update): a landmark most of whose beams stop on it gains w_hit, one most of whose
+        beams go through the place where it should stand loses w_miss.  Read-only on the filter.  Returns verdict
+        (mapped,) int32: +1, -1 or 0; the counts are in .evidence."""
+        k = self._mapped()
+        if k < 1:
+            self.evidence = None
+            return np.zeros(0, dtype=np.int32)
+        self.evidence = ev = self.handle.scan_evidence(ranges, lidar, 0, k, tol_abs, kappa, self.params)
+        return evidence_update(self.logodds, ev.n_expected, ev.n_agree, ev.n_through, min_beams, w_hit, w_miss, l_min, l_max)
+
+    def add_landmark(self, xy, W=None):
+        """a landmark the caller knows of by other means (a surveyed tube, a map from an earlier run) becomes the next known
+        landmark: init_block(s = 0) puts it at xy in the state's frame with the covariance block W (2 x 2, default the
+        landmark prior), uncorrelated with everything else.  Its log-odds start at 0.  Returns its index."""
+        if self._init_flag:
+            raise ValueError("add_landmark() appends behind the known landmarks of data_association(); measurement() placed all n")
+        if self._known >= self.n:
+            raise ValueError(f"the map is full: n = {self.n}")
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+        if xy.shape != (2,):
+            raise ValueError("xy must be one position")
+        prior = (self.params if self.params is not None else default_params()).sigma0_landmark
+        W = prior * np.eye(2) if W is None else np.ascontiguousarray(W, dtype=np.float64)
+        d, i = self.handle, self._known
+        if d.live < 3 + 2 * (i + 1):
+            d.live = 3 + 2 * (i + 1)
+        d.init_block(3 + 2 * i, W=W, xb=xy)
+        self._known = i + 1
+        return i
+
+    def remove(self, i):
+        """remove the known landmark i (DensePropagator64.remove_landmark on the object's paths); the last known landmark
+        moves into its slot, and its log-odds with it.  Returns moved_from (-1: i was the last)"""
+        if self._init_flag:
+            raise ValueError("remove() drops a known landmark of data_association(); measurement() placed all n")
+        l = self.logodds
+        flags = self.handle.LM_GROW_LIVE if self.grow_live else 0
+        self._known, moved, _ = self.handle.remove_landmark(i, self._known, flags, self.params)
+        self._logodds_removed(l, int(i), moved)
+        return moved
+
+    def prune(self, threshold):
+        """remove every known landmark whose log-odds are < threshold, highest index first (so the landmark that moves
+        into a freed slot has been judged already); returns the indices removed, as they were before the call"""
+        doomed = [int(i) for i in np.nonzero(self.logodds < threshold)[0][::-1]]
+        for i in doomed:
+            self.remove(i)
+        return doomed
 
     def health(self):
         """DensePropagator64.health() of the live corner: is the covariance still one?"""
@@ -2340,6 +2521,7 @@ class DenseEKFSLAM:
             raise ValueError(f"{self._known} + {other._known} landmarks do not fit n = {self.n}")
         live, W = d.live, 3 + 2 * self._known
         src_live, Wb = src.live, 3 + 2 * other._known
+        self.logodds   # (sized for the known landmarks before the other map's are appended)
         if W > live or Wb > src_live:
             raise ValueError("the map reaches beyond the live dimension")
         for h, w, lv in ((d, W, live), (src, Wb, src_live)):
@@ -2356,6 +2538,7 @@ class DenseEKFSLAM:
                 src.live = src_live
             if d.live < live:
                 d.live = live
+        self._logodds = np.concatenate([self._logodds, other.logodds])
         self._known += other._known
         return ms
 
@@ -2387,6 +2570,7 @@ class DenseEKFSLAM:
         t = self._copy_target(into)
         t.handle.extract_map(self.handle)
         t._known, t._init_flag = self._known, self._init_flag
+        t._logodds = self.logodds.copy()
         return t
 
     def restore(self, snap):
@@ -2418,6 +2602,7 @@ class DenseEKFSLAM:
         t = self._copy_target(into)
         t.handle.extract_map(self.handle, a)
         t._known, t._init_flag = int(a.size), False
+        t._logodds = self.logodds[a].copy()
         W, full = 3 + 2 * int(a.size), 3 + 2 * t.n
         if not t.grow_live and W < full:
             if t.handle.coupling(W)[0] != 0:

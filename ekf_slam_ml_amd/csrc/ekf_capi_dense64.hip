@@ -9,7 +9,7 @@
 // (ekf_dense64_factor.hip), the Joseph form of the sparse update with per-state gain weights (ekf_dense64_joseph.hip), the
 // map re-expressed in another frame (ekf_dense64_frame.hip), a second handle's map joined onto it (ekf_dense64_join.hip), a map
 // or a submap copied into a second handle (ekf_dense64_extract.hip), what observing each landmark would gain
-// (ekf_dense64_value.hip), and
+// (ekf_dense64_value.hip), a laser scan cast against the map for evidence on each landmark (ekf_dense64_evidence.hip), and
 // the deferred form of the sparse update: pending rows of K and T that the sparse calls
 // read through and every other call that touches Sigma applies first (flush_pending) -- unless the caller lets
 // propagate_block, init_block, swap_blocks and the block readout carry them (ekf_dense64_set_carry, ekf_dense64_carry.hip).
@@ -17,6 +17,7 @@
 // cut for it, and nothing at an index from it on is read or written; ekf_dense64_coupling (ekf_dense64_live.hip) measures
 // what ties the live corner to the rest.  Where an operand sits in its buffer is ekf_dense64_layout.hpp's business; the
 // entry points see the typed views of ekf_dense_handle.hpp only.
+#include "ekf_dense64_evidence.hpp"
 #include "ekf_dense64_jcbb.hpp"
 #include "ekf_dense_handle.hpp"
 
@@ -1757,8 +1758,25 @@ ekf_status ekf_dense64_score_landmark_pairs(ekf_dense64_handle d, int n_lm, doub
     return EKF_OK;
 }
 
-// [terms | the sparse correction, eager or deferred] and its synchronisation, then -- through the public calls, so that
-// carry, pending rows and live behave as in the spelled sequence -- [swap_blocks] init_block [set_live].
+// The removal of landmark i of *known ("Removing a landmark") -- through the public calls, so that carry,
+// pending rows and live behave as in the spelled sequence --: [swap_blocks] init_block [set_live].  Shared by the merge and
+// by ekf_dense64_remove_landmark; the arguments are the caller's to check.
+namespace {
+ekf_status remove_landmark_legs(ekf_dense64_s* d, const ekf::Params& p, int i, int* known, bool shrink, int* moved_from,
+                                LegTimer& leg) {
+    const int last = *known - 1;
+    double* pms = leg.pms();
+    const double W[4] = {p.sigma0_landmark, 0.0, 0.0, p.sigma0_landmark};
+    if (i != last) EKFC(leg(ekf_dense64_swap_blocks(d, 3 + 2 * i, 3 + 2 * last, 2, pms)));
+    EKFC(leg(ekf_dense64_init_block(d, 3 + 2 * last, 2, 0, nullptr, nullptr, W, nullptr, pms)));
+    *known = last;
+    if (moved_from) *moved_from = i != last ? last : -1;
+    if (shrink) EKFC(ekf_dense64_set_live(d, 3 + 2 * last));
+    return EKF_OK;
+}
+}  // namespace
+
+// [terms | the sparse correction, eager or deferred] and its synchronisation, then the removal of hi.
 ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* params, int a, int b, double r_merge,
                                        int* known, int flags, int* moved_from, double* d2_out, double* elapsed_ms) {
     const char* fnc = "ekf_dense64_merge_landmarks";
@@ -1774,7 +1792,7 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     EKFC(lm_flags_ok(fn, (unsigned)flags, EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE | EKF_DENSE64_LM_JOSEPH));
     const bool deferred = (flags & EKF_DENSE64_LM_DEFERRED) != 0;
     const ekf::Params p = landmark_params(params);
-    const int lo = std::min(a, b), hi = std::max(a, b), last = *known - 1;
+    const int lo = std::min(a, b), hi = std::max(a, b);
     if (elapsed_ms) *elapsed_ms = 0.0;
     HIPC(hipSetDevice(d->device));
     if (deferred) EKFC(pend_reserve(d, fnc));
@@ -1786,13 +1804,117 @@ ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle d, const ekf_params* p
     ekf::launch_dense64_pair_terms(d->x, lo, hi, r_merge, cin.cols, cin.Hc, cin.R, cin.nu, d->stream);
     correct_sparse_launch(d, deferred, 2, 4, true, lm_joseph((unsigned)flags));
     EKFC(leg(correct_sparse_finish(d, fnc, deferred, 2, d2_out, pms)));   // singular: nothing was written, *known stands
-    // the removal of hi ("Removing a landmark")
-    const double W[4] = {p.sigma0_landmark, 0.0, 0.0, p.sigma0_landmark};
-    if (hi != last) EKFC(leg(ekf_dense64_swap_blocks(d, 3 + 2 * hi, 3 + 2 * last, 2, pms)));
-    EKFC(leg(ekf_dense64_init_block(d, 3 + 2 * last, 2, 0, nullptr, nullptr, W, nullptr, pms)));
-    *known = last;
-    if (moved_from) *moved_from = hi != last ? last : -1;
-    if (flags & EKF_DENSE64_LM_GROW_LIVE) EKFC(ekf_dense64_set_live(d, 3 + 2 * last));
+    return remove_landmark_legs(d, p, hi, known, (flags & EKF_DENSE64_LM_GROW_LIVE) != 0, moved_from, leg);
+}
+
+// The removal alone.  Inside an open region the three calls behave as they do when the caller spells them.
+ekf_status ekf_dense64_remove_landmark(ekf_dense64_handle d, const ekf_params* params, int i, int* known, unsigned flags,
+                                       int* moved_from, double* elapsed_ms) {
+    const std::string fn = "ekf_dense64_remove_landmark";
+    if (!d) return fail(EKF_ERR_INVALID, fn + ": null handle");
+    if (!known) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (*known < 0 || 3 + 2 * (long long)*known > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the known landmarks must lie inside the live dimension");
+    if (i < 0 || i >= *known) return fail(EKF_ERR_INVALID, fn + ": i must be a landmark in [0, *known)");
+    EKFC(lm_flags_ok(fn, flags, EKF_DENSE64_LM_GROW_LIVE));
+    const ekf::Params p = landmark_params(params);
+    if (elapsed_ms) *elapsed_ms = 0.0;
+    LegTimer leg(elapsed_ms);
+    return remove_landmark_legs(d, p, i, known, (flags & EKF_DENSE64_LM_GROW_LIVE) != 0, moved_from, leg);
+}
+
+// ---- a scan cast against the map: evidence for and against landmarks (ekf_dense64_evidence.hip, ekf_dense64_evidence.hpp) --
+ekf_status ekf_dense64_evidence_launch_info(ekf_dense64_handle d, int* beam_tile, int* lm_chunk, int* threads) {
+    if (!d || !beam_tile || !lm_chunk || !threads)
+        return fail(EKF_ERR_INVALID, "ekf_dense64_evidence_launch_info: null argument");
+    *beam_tile = ekf::kDense64EvidenceBeamTile;
+    *lm_chunk = ekf::kDense64EvidenceLmChunk;
+    *threads = ekf::kDense64EvidenceThreads;
+    return EKF_OK;
+}
+
+// The checks in the documented order; the workspace, the ring and (kappa > 0) the candidates' buffer reserved; the ranges up
+// through a slot of the ring and the counters zeroed; behind e0 the end of a region that is being left, per chunk of
+// landmarks [terms | the sparse scoring kernel, reading through the pending rows | tolerances], the two launches of the cast;
+// everything asked for back behind the one synchronisation.
+ekf_status ekf_dense64_scan_evidence(ekf_dense64_handle d, const ekf_params* params, const ekf_lidar_params* lidar,
+                                     const double* ranges, int first_lm, int count, double tol_abs, double kappa,
+                                     int* n_expected, int* n_agree, int* n_through, int* n_short, double* tol_out,
+                                     double* expected_out, int* hit_out, unsigned char* class_out,
+                                     ekf_dense64_evidence_report* report, double* elapsed_ms) {
+    const char* fnc = "ekf_dense64_scan_evidence";
+    const std::string fn = fnc;
+    if (!d || !lidar) return fail(EKF_ERR_INVALID, fn + ": null handle or lidar");
+    const RegionLeave leaving(d);   // outside a region's terms: it ends behind this call's checks and e0
+    if (!n_expected && !n_agree && !n_through && !n_short && !tol_out && !expected_out && !hit_out && !class_out && !report)
+        return fail(EKF_ERR_INVALID, fn + ": every output is NULL");
+    if (count < 1 || first_lm < 0) return fail(EKF_ERR_INVALID, fn + ": count >= 1 and first_lm >= 0");
+    if (3 + 2 * ((long long)first_lm + count) > d->live)
+        return fail(EKF_ERR_INVALID, fn + ": the landmarks must lie inside the live dimension");
+    const int nb = lidar->n_beams;
+    if (nb < 1 || nb > kScanBeams) return fail(EKF_ERR_INVALID, fn + ": n_beams must lie in [1, 1024]");
+    if (!std::isfinite(lidar->tube_radius) || !(lidar->tube_radius > 0.0) || !std::isfinite(lidar->range_max) ||
+        !(lidar->range_max > 0.0))
+        return fail(EKF_ERR_INVALID, fn + ": tube_radius and range_max must be finite and > 0");
+    if (!(tol_abs >= 0.0) || !(kappa >= 0.0)) return fail(EKF_ERR_INVALID, fn + ": tol_abs and kappa must be >= 0");
+    if (lidar->model != 0) return fail(EKF_ERR_INVALID, fn + ": only the clean ray geometry (model 0) is cast");
+    const ekf::Params p = landmark_params(params);
+    HIPC(hipSetDevice(d->device));
+    const ekf::Dense64EvidencePlan pl = ekf::dense64_evidence_plan(first_lm, count);
+    const bool scored = kappa > 0.0;
+    const int chunk = std::min(count, kSparseRows / 2);
+    EKFC(d->evidence.reserve(d->mem, pl.bytes, false, fnc, "the scan evidence's workspace"));
+    if (scored) EKFC(sps_reserve(d, L::sps_layout(chunk, 2, 5, true, true).bytes, fnc));
+    char* ws = d->evidence.as<char>();
+    if (ranges) {
+        for (Staging& sg : d->scan_up.slot) EKFC(sg.reserve(sizeof(double) * kScanBeams));
+        Staging& sg = d->scan_up.acquire();
+        EKFC(sg.wait());
+        std::memcpy(sg.host, ranges, sizeof(double) * nb);
+        HIPC(hipMemcpyAsync(ws + pl.off_ranges, sg.host, sizeof(double) * nb, hipMemcpyHostToDevice, d->stream));
+        EKFC(sg.mark(d->stream));
+    }
+    HIPC(hipMemsetAsync(ws + pl.off_report, 0, pl.zero_bytes, d->stream));
+    HIPC(hipEventRecord(d->e0, d->stream));
+    d->finish_leave();   // (a region that is being left ends here: its global update moves the landmarks the beams are cast at)
+    if (scored) {
+        for (int at = 0; at < count; at += chunk) {
+            const int n = std::min(chunk, count - at);
+            const SpsView v = view(d->sps.p, L::sps_layout(n, 2, 5, true, true), true);
+            ekf::launch_dense64_lm_terms(d->x, d->x, 0.0, 0.0, first_lm + at, n, 0, p.r_meas, v.cols, v.Hc, v.R, v.nu,
+                                         d->stream);
+            score_sparse_launch(d, v, n, 2, 5, true, false, false);   // (S and the flag do not depend on the reading)
+            ekf::launch_dense64_evidence_tol(pl, at, n, v.S, v.flag, tol_abs, kappa, ws, d->stream);
+        }
+    } else {
+        ekf::launch_dense64_evidence_tol(pl, 0, count, nullptr, nullptr, tol_abs, kappa, ws, d->stream);
+    }
+    ekf::launch_dense64_evidence(pl, d->x, nb, lidar->range_max, lidar->border_width, lidar->tube_radius, tol_abs,
+                                 ranges != nullptr, ws, d->stream);
+    int rep[4] = {0, 0, 0, 0};
+    const size_t ci = sizeof(int) * (size_t)count;
+    EKFC(finish_timed(d, elapsed_ms, {{rep, ws + pl.off_report, sizeof(rep)},
+                                      {n_expected, ws + pl.off_counts, ci},
+                                      {n_agree, ws + pl.off_counts + ci, ci},
+                                      {n_through, ws + pl.off_counts + 2 * ci, ci},
+                                      {n_short, ws + pl.off_counts + 3 * ci, ci},
+                                      {tol_out, ws + pl.off_tol, sizeof(double) * count},
+                                      {expected_out, ws + pl.off_expected, sizeof(double) * nb},
+                                      {hit_out, ws + pl.off_hit, sizeof(int) * nb},
+                                      {class_out, ws + pl.off_class, (size_t)nb}}));
+    if (report) *report = ekf_dense64_evidence_report{rep[0], rep[1], rep[2], rep[3]};
+    return EKF_OK;
+}
+
+ekf_status ekf_dense64_evidence_update(int count, const int* n_expected, const int* n_agree, const int* n_through,
+                                       int min_beams, double w_hit, double w_miss, double l_min, double l_max,
+                                       double* logodds, int* verdict_out) {
+    const std::string fn = "ekf_dense64_evidence_update";
+    if (!n_expected || !n_agree || !n_through || !logodds) return fail(EKF_ERR_INVALID, fn + ": null argument");
+    if (count < 1 || min_beams < 1) return fail(EKF_ERR_INVALID, fn + ": count >= 1 and min_beams >= 1");
+    if (!(w_hit >= 0.0) || !(w_miss >= 0.0) || !(l_min <= l_max))
+        return fail(EKF_ERR_INVALID, fn + ": w_hit and w_miss must be >= 0 and l_min <= l_max, none of them a NaN");
+    ekf::evidence_update(count, n_expected, n_agree, n_through, min_beams, w_hit, w_miss, l_min, l_max, logodds, verdict_out);
     return EKF_OK;
 }
 

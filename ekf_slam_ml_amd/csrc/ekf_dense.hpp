@@ -302,6 +302,31 @@ void launch_dense64_pairs(const Dense64PairsPlan& p, const double* Sigma, const 
 void launch_dense64_pair_terms(const double* state, int lo, int hi, double r_merge, int* cols, double* Hc, double* R,
                                double* nu, hipStream_t st);
 
+// ---- a laser scan cast against the handle's own map (ekf_dense64_evidence.hip; the definitions are include/ekfslam.h's,
+// ekf_dense64_scan_evidence).  Three launches behind the tolerances: the landmarks within reach of the pose compacted in
+// ascending index (one workgroup, ballots), a workgroup per kDense64EvidenceBeamTile beams that walks the candidates through
+// LDS kDense64EvidenceLmChunk at a time and classes its beams, integer atomics for every count.
+constexpr int kDense64EvidenceBeamTile = 64;
+constexpr int kDense64EvidenceLmChunk = 128;
+constexpr int kDense64EvidenceThreads = 64;
+// the workspace of a call, byte offsets: report (4 ints) | the four counters [4][count] ints -- zero before the launches,
+// zero_bytes from off_report -- | tol [count] | the candidates' indices [count] and offsets from the pose [count][2] |
+// ranges, expected [kDense64ScanMaxBeams] doubles each | hit [kDense64ScanMaxBeams] ints | class [kDense64ScanMaxBeams] bytes
+struct Dense64EvidencePlan {
+    int first_lm, count;
+    size_t off_report, off_counts, zero_bytes, off_tol, off_cand_idx, off_cand_xy, off_ranges, off_expected, off_hit,
+        off_class, bytes;
+};
+Dense64EvidencePlan dense64_evidence_plan(int first_lm, int count);
+// tol [at, at + n) = flag ? +Inf : tol_abs + kappa sqrt(max(S[j][0][0], 0)) for S [n][2][2], flag [n] as the sparse scoring
+// kernel left them; S == nullptr: tol_abs.
+void launch_dense64_evidence_tol(const Dense64EvidencePlan& p, int at, int n, const double* S, const int* flag,
+                                 double tol_abs, double kappa, void* ws, hipStream_t st);
+// The two launches of the cast; have_ranges = 0: the expected scan only.  Reads the state below 3 + 2 (first_lm + count).
+void launch_dense64_evidence(const Dense64EvidencePlan& p, const double* state, int n_beams, double range_max,
+                             double border_width, double tube_radius, double tol_abs, int have_ranges, void* ws,
+                             hipStream_t st);
+
 // ---- the health of the live corner and its exact symmetrisation (ekf_dense64_health.hip; the definitions of every figure
 // are include/ekfslam.h's, ekf_dense64_health_report).  A workgroup per tile pair (A <= B) of kDense64HealthTile states a
 // side: Sigma[A rows, B cols] along rows from memory, Sigma[B rows, A cols] along rows through an LDS transpose.

@@ -118,7 +118,8 @@ struct ekf_dense64_s : ekfrt::DenseHandle<double> {
     ekfrt::DeviceBuf frame;      // Dense64FramePlan (ekf_dense64_map_congruence, ekf_dense64_reframe_landmarks), a function of ld
     ekfrt::DeviceBuf join;       // Dense64JoinPlan (ekf_dense64_join_congruence, ekf_dense64_join_map) of the DESTINATION, grows with Nb
     ekfrt::DeviceBuf extract;    // Dense64ExtractPlan (ekf_dense64_extract_map) of the DESTINATION: the list and the run flags, grows with k
-    ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan`
+    ekfrt::DeviceBuf evidence;   // Dense64EvidencePlan (ekf_dense64_scan_evidence), grows with count
+    ekfrt::StagingRing scan_up;  // pinned: a scan's ranges on their way up, reserved with `scan` or `evidence`
     std::vector<double> scan_rec; // the record of a scan as it came down (ScanLayout from head on)
     std::vector<double> host_in; // the dense correction's operands, packed for their three uploads
     std::vector<int> host_stamp; // [N] the duplicate check of the index lists

@@ -1345,6 +1345,87 @@ ekf_status ekf_dense64_score_landmark_pairs(ekf_dense64_handle h, int n_lm, doub
 ekf_status ekf_dense64_merge_landmarks(ekf_dense64_handle h, const ekf_params* params, int a, int b, double r_merge,
                                        int* known, int flags /* EKF_DENSE64_LM_DEFERRED | EKF_DENSE64_LM_GROW_LIVE */,
                                        int* moved_from, double* d2_out, double* elapsed_ms);
+/* ekf_dense64_remove_landmark: the removal half of ekf_dense64_merge_landmarks as a call of its own -- landmark i of *known
+ * is dropped by the recipe of ekf_dense64_swap_blocks: swap_blocks(i, last) unless i is the last known landmark,
+ * init_block(last, s = 0, W = sigma0_landmark I), --*known; with EKF_DENSE64_LM_GROW_LIVE (the only flag it knows) also
+ * ekf_dense64_set_live(3 + 2 *known).  The same internal function as the merge's: carry, pending rows and live behave as in
+ * that sequence spelled by the caller, the result is its result bit for bit, and inside an open region the three calls do
+ * what they do when spelled there.  *moved_from (nullable) as in the merge: the old index of the landmark that now sits in
+ * slot i, -1 when i was the last.  A NULL handle (first) or known, the known landmarks outside the live dimension, an i
+ * outside [0, *known), unknown flag bits return EKF_ERR_INVALID before the device is looked at and change nothing.  params:
+ * NULL = the reference's constants (only sigma0_landmark is used).  elapsed_ms (nullable) = HIP-event time of every leg. */
+ekf_status ekf_dense64_remove_landmark(ekf_dense64_handle h, const ekf_params* params, int i, int* known /* IN/OUT */,
+                                       unsigned flags /* EKF_DENSE64_LM_GROW_LIVE */, int* moved_from, double* elapsed_ms);
+
+/* WHICH landmark is spurious: a laser scan cast against the handle's own map.  A landmark that stands where no tube is (a
+ * noise cluster, a tube that was moved, a reading taken at a drifted pose) is never observed again and never goes away; the
+ * scan that arrives every tick says so: a beam that returns from BEHIND the place where a mapped tube should stand has seen
+ * through it, a beam that returns from its surface supports it, a beam that returns short of it says nothing (something
+ * unmapped is in the way).  The beams carry this where the circle pipeline cannot: a cluster needs more than 6 points, which
+ * at 360 beams a tube of radius 0.0762 m gives only within about 1.25 m, and the lidar reaches 3.5 m.
+ * ekf_dense64_scan_evidence, for the landmarks [first_lm, first_lm + count) and lidar->n_beams beams:
+ * GEOMETRY (model 0 of ekf_lidar_params on the state; the definitions and the order of operations of ekf_simulate_scans
+ *   with range_std = 0): beam b leaves (x, y) = state[1..2] in direction th = state[0] + 2 pi b / n_beams (not wrapped),
+ *   d = (cos th, sin th); half = border_width / 2 (INFINITY: no wall);  wall_x = (half - x) / d_x for d_x > 0,
+ *   (-half - x) / d_x for d_x < 0, +Inf otherwise, wall_y likewise;  r = fmin(fmin(wall_x, wall_y), range_max);  then for the
+ *   landmarks j in ascending index  f = (x, y) - m_j,  bq = f_x d_x + f_y d_y,  cq = f_x f_x + f_y f_y - tube_radius^2,
+ *   disc = bq bq - cq,  and where disc > 0 the root t = -bq - sqrt(disc) replaces r when 0 < t < r.  Products and sums are
+ *   rounded separately.  expected_out[b] = r;  hit_out[b] = the landmark whose root stands, -1 for the wall or range_max.  The
+ *   comparison is strict: of equal roots the LOWEST INDEX wins (two landmarks with identical coordinates give every beam to
+ *   the lower one), a NaN root never wins, a pose inside a tube has no positive nearest root and so no hit.
+ * TOLERANCE  tol_out[i] = tol_abs + kappa sqrt(max(S00_i, 0)), S00_i the range variance of landmark first_lm + i under the
+ *   current Sigma, pending rows included: the [0][0] entry of the S ekf_dense64_score_landmarks returns for it, bit for bit
+ *   (that call's launches run; R = params->r_meas I, NULL: the reference's constants).  A landmark whose score flag is 1 gets
+ *   +Inf: all its beams agree and none count against it.  kappa == 0: tol_abs, the scoring kernel is not launched and Sigma
+ *   is not read.  kappa is what keeps a miss on a poorly localised landmark from counting as a miss.
+ * CLASSES    class_out[b], with obs = ranges[b], exp = expected_out[b], tol = tol_out[hit_out[b] - first_lm], every
+ *   comparison on rounded doubles as written:
+ *     4  invalid: obs is a NaN or <= 0 (whatever the beam expects)
+ *     0  exp is the wall or range_max; such a beam with obs < exp - tol_abs counts in report->n_unexplained
+ *     1  agree: |obs - exp| <= tol        2  through: obs - exp > tol        3  short: exp - obs > tol
+ *   n_expected, n_agree, n_through, n_short [count]: per landmark its beams of classes {1, 2, 3}, 1, 2, 3; invalid beams
+ *   count in none.  ranges == NULL: the expected scan only, every class and every counter 0.  report: n_candidates = the
+ *   landmarks with |f|^2 <= (range_max + tube_radius)^2 (1 + 1e-12) (the only ones a beam can reach; the rest are not walked),
+ *   n_on_tube = beams with hit_out >= 0 (invalid ones included, counted without ranges too), n_unexplained, n_invalid.
+ * Counters are integers, there are no floating-point atomics and no floating-point sum: a landmark's four counters, its tol
+ * and every beam's outputs are the same bits on every run, for any capacity N >= live, for any slice [first_lm, first_lm +
+ * count) that holds the landmarks in reach of the beams concerned, and whatever out-of-reach landmarks the map also holds.
+ * The call is READ-ONLY and opt-in: the state, Sigma, the pending rows and the factor snapshot keep their bits; NOTHING IS
+ * FLUSHED (the deferred path corrects the state at once, the scoring kernel reads through the pending rows); no other
+ * entry point launches anything different because it exists.  Inside an open region it behaves as
+ * ekf_dense64_rank_landmarks: the region ends first, behind the checks.  It runs on the live corner.  CHECKS, in this order,
+ * each EKF_ERR_INVALID before the device is looked at, nothing changed: 1. a NULL handle or lidar; 2. every output NULL;
+ * 3. count < 1 or first_lm < 0; 4. 3 + 2 (first_lm + count) > live; 5. n_beams outside [1, EKF_DENSE64_SCAN_MAX_BEAMS];
+ * 6. tube_radius or range_max not finite or not > 0; 7. tol_abs or kappa negative or a NaN; 8. model != 0.
+ * The ranges go up through the pinned ring of ekf_dense64_fit_scan; the workspace (44 bytes per landmark and 21 KB) is
+ * reserved by the first call from the handle's ledger and grows with count; a failure there returns EKF_ERR_NOMEM and
+ * leaves the handle as it was.  Launches: per 32768 landmarks (kappa > 0 only) the terms, the scoring kernel and the
+ * tolerances, else the tolerances alone; the compaction of the landmarks in reach (one workgroup); a workgroup per
+ * beam_tile beams that walks them through LDS lm_chunk at a time (ekf_dense64_evidence_launch_info).  ONE synchronisation,
+ * every output comes down behind it.  elapsed_ms (nullable) = HIP-event time of the launches.
+ * ekf_dense64_evidence_update: the bookkeeping, no handle and no device.  logodds [count] is the caller's (the library
+ * keeps no landmark ids: the array follows *moved_from on merge and remove).  Per landmark with n_expected >= min_beams:
+ * a HIT when 2 n_agree >= n_expected: l = l + w_hit, verdict +1; a MISS when 2 n_through > n_expected: l = l - w_miss,
+ * verdict -1; otherwise verdict 0; then every l is clamped to [l_min, l_max].  Integer decisions, plain fp64 sums in
+ * index order.  verdict_out nullable.  NULL arrays, count < 1, min_beams < 1, a negative or NaN weight, l_min > l_max or a
+ * NaN bound return EKF_ERR_INVALID. */
+typedef struct ekf_dense64_evidence_report {
+    int n_candidates;    /* landmarks within reach of the pose                       */
+    int n_on_tube;       /* beams whose expected first hit is a landmark             */
+    int n_unexplained;   /* beams expected on wall / range_max that came back short  */
+    int n_invalid;       /* observed ranges that are NaN or <= 0                     */
+} ekf_dense64_evidence_report;
+ekf_status ekf_dense64_evidence_launch_info(ekf_dense64_handle h, int* beam_tile, int* lm_chunk, int* threads);
+ekf_status ekf_dense64_scan_evidence(ekf_dense64_handle h, const ekf_params* params, const ekf_lidar_params* lidar,
+                                     const double* ranges /* [n_beams], nullable */, int first_lm, int count,
+                                     double tol_abs, double kappa, int* n_expected, int* n_agree, int* n_through,
+                                     int* n_short /* [count] each, nullable */, double* tol_out /* [count] */,
+                                     double* expected_out /* [n_beams] */, int* hit_out /* [n_beams] */,
+                                     unsigned char* class_out /* [n_beams] */, ekf_dense64_evidence_report* report,
+                                     double* elapsed_ms);
+ekf_status ekf_dense64_evidence_update(int count, const int* n_expected, const int* n_agree, const int* n_through,
+                                       int min_beams, double w_hit, double w_miss, double l_min, double l_max,
+                                       double* logodds /* IN/OUT [count] */, int* verdict_out /* [count], nullable */);
 
 /* Is Sigma still a covariance, and the exact repair of its symmetry.  Every call above keeps the contract "Sigma is never
  * symmetrised" (T = H Sigma is taken from rows, U = Sigma H^T from columns), so rounding lets Sigma[i][j] and Sigma[j][i]
